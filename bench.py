@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - SDF query-points/sec at vox_res=128 (BASELINE.json metric) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1 either way: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` the
     ranks read RANK / LOCAL_RANK / WORLD_SIZE from the environment; started plainly with WORLD_SIZE unset,
     bench.py starts those N workers itself as a CHILD process - decided before anything touches the GPU - and
@@ -23,6 +23,13 @@ seeded N(0,1).
 csrc/sdf_decoder_split.hip: operands carried as two fp16 halves, ~2^-21 relative; max |logit
 difference| to the exact-fp32 kernel ~3e-6 with no occupancy flip on the 129^3 grid - BASELINE.json's
 contract is 1e-4 and its own config names bf16) or "f32" (exact-fp32 MFMA, csrc/sdf_decoder.hip).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR: the occupancy
+grids the step returned, DIR/occupancy.npy in float32 - the whole [batch, G, G, G] tensor up to 64 MiB, else a fixed
+seeded sample of its points; the inputs are seeded, so two builds compare output for output) and prints the line:
+metric / value / unit / higher_is_better / dtype / ms_per_step, the timed steps' own roofline and the calibration.
+Everything else below takes runs of its own and comes only with --full (exact_f32, image_check, logit_scale_sweep,
+roofline.power, cpu_baseline and the legs; --no-cpu-baseline / --no-extras / --skip-legs trim a --full run).
 
 Extra objects on the JSON line:
   roofline     - the fused decoder kernel against the dense MFMA peak of its dtype (fp16/bf16 2,500 /
@@ -136,6 +143,25 @@ def power_under_load(launch, seconds=1.6):
             "how": "rocm-smi every 0.15 s over %.1f s of back-to-back decoder launches" % seconds}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, occ):
+    """--dump-outputs: what the last timed step returned - the occupancy grids [batch, G, G, G] - as DIR/occupancy.npy in
+    float32: the whole tensor when it fits in 64 MiB, else a fixed seeded sample of its points in memory order."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    flat = occ.detach().reshape(-1)
+    if flat.numel() * 4 > DUMP_LIMIT_BYTES:
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_LIMIT_BYTES // 8))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    out = flat.float().cpu().numpy()
+    if out.size == occ.numel():
+        out = out.reshape(tuple(occ.shape))
+    np.save(os.path.join(path, "occupancy.npy"), out)
+
+
 def self_launch(n_gpus, argv):
     """`python bench.py --gpus N` with WORLD_SIZE unset: run the N ranks under torch.distributed.run as a child
     process (never an exec: this process must not have initialised HIP, and it has not - torch is not even imported
@@ -161,9 +187,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--vox-res", type=int, default=VOX_RES)
     ap.add_argument("--precision", choices=("f16x3", "f32"), default="f16x3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's occupancy grids to DIR/occupancy.npy (float32, at most 64 MiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the exact-fp32 contract, the image-check A/B, power, "
+                         "the CPU baseline and the legs of tools/bench_legs.py (a plain run times the steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the Chamfer / pose-search / evaluation / encoder / training legs (tools/bench_legs.py)")
+                    help="--full without the image-check A/B, the power reading and the Chamfer / pose-search / evaluation / "
+                         "encoder / training legs (tools/bench_legs.py)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--skip-legs", default="",
                     help="comma-separated extra legs to leave out (names of the line's objects, plus 'chamfer_l1_vox128' for the "
@@ -270,11 +302,13 @@ def main():
     assert occ.shape == (batch, G, G, G)
     points_per_step = batch * G ** 3
     value = points_per_step * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, occ)
 
     # what prepare()'s per-image output check (on by default since round 4; Implicit._launch_image_check) costs the step:
     # the same timed loop without it (round 3's behaviour)
     image_check = None
-    if world == 1 and precision_run == "f16x3" and getattr(net, "image_check", False) and not args.no_extras:
+    if args.full and world == 1 and precision_run == "f16x3" and getattr(net, "image_check", False) and not args.no_extras:
         net.image_check = False
         for _ in range(max(1, args.warmup)):
             step()
@@ -310,14 +344,14 @@ def main():
 
     roofline = roofline_of(precision_run, kern_ms)          # the launches of the timed steps themselves
     roofline["launch_ms_source"] = "HIP events around the decoder launch inside each of the %d timed steps" % args.steps
-    st = net.prepare(latent)
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
+        st = net.prepare(latent)
         roofline["power"] = power_under_load(
             lambda: net.query_grid_range(latent, axis, b, e, apply_sigmoid=True, state=st))
 
     exact_f32 = None
     logit_sweep = None
-    if precision_run == "f16x3" and world == 1:
+    if args.full and precision_run == "f16x3" and world == 1:
         # the SAME timed contract in the reference's own arithmetic (options/shape.yaml:96 amp false; implicit.py:251-288 is
         # fp32): `warmup` untimed + `steps` timed steps of prologue + exact-fp32 launch + sigmoid between the same barriers, the
         # launch event-timed inside each step - the like-for-like-precision number, driver-checkable (ms_per_step x steps)
@@ -334,7 +368,7 @@ def main():
         r32 = roofline_of("f32", ms32)
         r32["launch_ms_source"] = "HIP events around the decoder launch inside each of the %d timed fp32 steps" % args.steps
         st32 = net.prepare(latent, "f32")
-        lg = net.query_grid(latent, axis, apply_sigmoid=False, state=st)
+        lg = net.query_grid(latent, axis, apply_sigmoid=False, state=net.prepare(latent))
         lg32 = net.query_grid(latent, axis, apply_sigmoid=False, state=st32)
         flips = (lg > 0) != (lg32 > 0)
         exact_f32 = {"value": round(points_per_step * args.steps / dt32, 1), "unit": "points/s",
@@ -354,7 +388,7 @@ def main():
                 logit_sweep = {"error": "%s: %s" % (type(ex).__name__, ex)}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import decoder_ref
         grid = decoder_ref.dense_grid(RANGE[0], RANGE[1], N)
         lat_c = latent[:1].cpu()
@@ -399,7 +433,7 @@ def main():
             cpu_baseline["full_grids"] = full
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras and N == VOX_RES:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and N == VOX_RES:
         from tools import bench_legs as legs
         cpu = not args.no_cpu_baseline
         skip = set(args.skip_legs.split(","))

@@ -43,3 +43,26 @@ def test_under_torchrun_it_is_a_rank_and_failures_propagate():
     # a world size that contradicts --gpus is an error, and the self-launcher relays a worker's failure
     bad = _run([sys.executable, "bench.py", "--gpus", "2"], {"WORLD_SIZE": "3", "RANK": "0"})
     assert bad.returncode != 0
+
+
+def test_plain_and_full_runs_take_the_same_launch_path():
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--full", "--dump-outputs", "unused"])
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert _line(out) == {"rendezvous_only": True, "n_gpus": 1, "steps": 2}
+
+
+def test_dump_outputs_writes_float32_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    occ = torch.rand(2, 9, 9, 9, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path / "whole"), occ)
+    whole = np.load(tmp_path / "whole" / "occupancy.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, occ.numpy())
+    # above the limit: a seeded sample of the points, in memory order, the same in every run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    bench.dump_outputs(str(tmp_path / "a"), occ)
+    bench.dump_outputs(str(tmp_path / "b"), occ)
+    a, b = np.load(tmp_path / "a" / "occupancy.npy"), np.load(tmp_path / "b" / "occupancy.npy")
+    assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.nbytes <= 4096 and np.array_equal(a, b)
+    assert np.isin(a, occ.numpy().reshape(-1)).all()

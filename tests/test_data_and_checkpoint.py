@@ -104,7 +104,7 @@ def test_checkpoint_roundtrip_in_reference_layout(big_tmp_path):
     assert torch.equal(c.graph.coord_encoder.encoder.conv1.weight, before)
 
 
-def test_pix3d_and_omniobj3d_shaped_items():
+def test_pix3d_and_omniobj3d_shaped_items(tmp_path):
     """Sample-dict keys of the reference's data/pix3d.py:86-113 and data/omniobj3d.py:129-165, and the
     Pix3D camera convention: the GT cloud reaches the view frame only through the xy flip of
     utils/eval_3D.py:122-123 (oracle/geometry check on the CPU; the HIP path runs it in
@@ -139,8 +139,8 @@ def test_pix3d_and_omniobj3d_shaped_items():
     view = gt @ base["pose_gt"].numpy()[:, :3].T.astype(np.float64) + base["pose_gt"].numpy()[:, 3]
     np.testing.assert_allclose(flipped, view, atol=1e-5)               # = the render's own view-frame cloud
     assert np.abs(rot + base["pose_gt"].numpy()[:, 3] - view).max() > 0.1      # ... and only with the flip
-    pix.id_filename_mapping(opt, "/tmp/zs_pix3d_map.txt")
-    assert len(open("/tmp/zs_pix3d_map.txt").read().strip().split("\n")[0].split(" ")) == 4
+    pix.id_filename_mapping(opt, str(tmp_path / "pix3d_map.txt"))
+    assert len(open(tmp_path / "pix3d_map.txt").read().strip().split("\n")[0].split(" ")) == 4
 
 
 def test_stand_in_datasets_need_an_opt_in(monkeypatch, capsys):

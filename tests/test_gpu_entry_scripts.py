@@ -153,13 +153,13 @@ def test_demo_script_shape_and_depth(tmp_path, encoder_sd, seeded_sd):
 
 
 def test_bench_line_contract():
-    """`python bench.py` (short run, no CPU legs): ONE JSON line with the driver's keys, the roofline object consistent
+    """`python bench.py --full` (short run, no CPU legs): ONE JSON line with the driver's keys, the roofline object consistent
     with itself (achieved = points x algorithmic flop / launch time, frac = achieved / peak) and with the timed
     region, measured traffic only from a profile of the current kernel source, and the evaluation legs."""
     import json
     # (the legs with tests of their own - the 304-iteration training run of test_gpu_trained_weights.py, the CPU-oracle pipeline
     # at vox 128 of test_gpu_eval_pipeline.py, the logit-scale sweeps - are left out: the suite must fit the driver's limit)
-    out = run("bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    out = run("bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--skip-legs", "trained_weights,chamfer_l1_vox128,logit_scale_sweep,vox256,encoder_att")
     lines = [ln for ln in out.strip().split("\n") if ln.startswith("{")]
     assert len(lines) == 1
@@ -193,6 +193,33 @@ def test_bench_line_contract():
     assert wr["graphs"] == 6 and wr["buckets_issued_after_each_replay"][-1] == wr["buckets"] and 0.8 < wr["compute_side_bound"] < 1.05
     assert d["inference"]["vox64"]["points"] == 65 ** 3 and 0 < d["inference"]["vox64"]["ms"] < d["inference"]["vox128"]["ms"]
     assert d["pose_search"]["pruned_equals_exhaustive"] is True and d["chamfer_l1"]["chamfer_l1_vs_oracle_pipeline_vox16"] < 1e-4
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """A plain `python bench.py` does the headline only: the line's keys, --steps timed steps, none of --full's objects; and
+    --dump-outputs writes the occupancy grid the last timed step returned - whole at vox 128, a fixed sample (<= 64 MiB,
+    the same points in every run) of the 257^3 grid at vox 256."""
+    import json
+    out = run("bench.py", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "v128"))
+    lines = [ln for ln in out.strip().split("\n") if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "calibration"):
+        assert k in d, k
+    assert d["metric"] == "sdf_query_points_per_sec_vox128" and d["unit"] == "points/s" and d["higher_is_better"] is True
+    assert d["steps"] == 2 and d["dtype"] == "f16x3" and d["cpu_baseline"] is None and "power" not in d["roofline"]
+    for k in ("exact_f32", "image_check", "logit_scale_sweep", "chamfer", "virtual_ranks_8", "train_step"):
+        assert k not in d, k
+    pts = 129 ** 3
+    assert abs(d["value"] - pts / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    occ = np.load(tmp_path / "v128" / "occupancy.npy")
+    assert occ.dtype == np.float32 and occ.shape == (1, 129, 129, 129)
+    assert np.isfinite(occ).all() and occ.min() >= 0 and occ.max() <= 1 and occ.std() > 0
+    for name in ("a", "b"):
+        run("bench.py", "--steps", "1", "--warmup", "0", "--vox-res", "256", "--dump-outputs", str(tmp_path / name))
+    a, b = np.load(tmp_path / "a" / "occupancy.npy"), np.load(tmp_path / "b" / "occupancy.npy")
+    assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.nbytes <= 64 << 20 and a.size > 4 * 10 ** 6
+    assert a.shape == b.shape and float(np.abs(a - b).max()) <= 1e-6
 
 
 def test_bench_two_ranks_rehearsed_on_one_gpu():

@@ -84,3 +84,27 @@ def test_compat_aliases_cover_what_the_reference_scripts_import():
                 sys.modules.pop(k, None)
             else:
                 sys.modules[k] = v
+
+
+def test_repack_scan_survives_a_weight_collected_mid_scan(monkeypatch):
+    """A weight that dies while _refresh_all_packs walks the registry (the garbage collector runs on an allocation inside the
+    walk, and the weight's weakref callback drops its record) must not break the scan: a training step used to fail with
+    'dictionary changed size during iteration' right after an earlier model had been dropped."""
+    from zeroshape_amd.nn import autograd as A
+
+    class Registry(dict):
+        def items(self):            # a collection in the middle of any walk over the live registry
+            for n, kv in enumerate(dict.items(self)):
+                if n == 1:
+                    A._drop_pack((2, 4, 4, False, None))
+                yield kv
+
+    monkeypatch.setattr(A, "_PACKS", Registry())
+    monkeypatch.setattr(A, "_PACK_FAST", {})
+    weights = [torch.zeros(4, 4) for _ in range(3)]
+    for i, w in enumerate(weights):
+        rec = A._PackRec()
+        rec.key, rec.stamp, rec.ref = (i, 4, 4, False, None), None, (lambda w=w: w)
+        A._PACKS[rec.key] = rec
+    A._refresh_all_packs_only(torch.device("cuda", 0))      # CPU weights: nothing to re-pack on cuda:0, nothing launched
+    assert len(A._PACKS) == 3

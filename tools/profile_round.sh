@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="python3 $ROOT/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-extras"
 EVAL="python3 $ROOT/tools/prof_eval_kernels.py"
 run() {  # name, command..., then counters
     local name=$1; shift

@@ -286,7 +286,9 @@ def _refresh_all_packs(device):
                 fast["generation"] = GENERATION[0]
                 return
     recs = []
-    for key, rec in list(_PACKS.items()):
+    # iterate over a copy: a weight collected while the loop allocates fires its weakref callback (_drop_pack) mid-loop
+    packs = _PACKS.copy()
+    for key, rec in packs.items():
         w = rec.ref()
         if w is None:
             _drop_pack(key)
@@ -294,7 +296,7 @@ def _refresh_all_packs(device):
             recs.append((rec, w))
     if not recs:
         return
-    complete = len(recs) == sum(1 for rec in _PACKS.values() if rec.ref() is not None and rec.ref().device == device)
+    complete = len(recs) == sum(1 for rec in _PACKS.copy().values() if rec.ref() is not None and rec.ref().device == device)
     entries = []
     standardize_all([(w, rec.key[4]) for rec, w in recs if rec.key[4] is not None and w.device == device])
     for rec, w in recs:
@@ -429,7 +431,7 @@ def _amp_splits_operands():
 def _presplit_all(device):
     """Split every registered packed operand on `device` (call right after they were re-packed)."""
     lib = _lib.load()
-    recs = [rec for rec in _PACKS.values() if rec.ref() is not None and rec.packed.device == device and
+    recs = [rec for rec in _PACKS.copy().values() if rec.ref() is not None and rec.packed.device == device and
             not (rec.inline_split and rec.split is not None and rec.split_stamp == rec.stamp)]   # (split by the re-pack itself)
     if not recs:
         return
