@@ -372,6 +372,7 @@ def test_repack_of_all_operands_in_one_launch_equals_the_single_packs():
     sub-ranges, ragged channel counts."""
     from zeroshape_amd import _lib
     from zeroshape_amd.nn import autograd as A
+    from zeroshape_amd.nn.operands import CACHE
     g = torch.Generator().manual_seed(5)
     shapes = [(3072, 768, 1, 1), (768, 3072, 1, 1), (256, 256, 3, 3), (64, 3, 7, 7), (10, 6, 3, 3), (130, 70, 1, 1),
               (32, 128, 3, 3), (1, 32, 1, 1), (96, 67, 2, 2)]
@@ -383,12 +384,12 @@ def test_repack_of_all_operands_in_one_launch_equals_the_single_packs():
     sub = weights[2]
     keys.append((sub, 64, 128, False))           # channels [64, 192) of 256, like the decoder's concatenated inputs
     keys.append((sub, 64, 128, True))
-    first = [A._pack(w, c0, c, d).clone() for w, c0, c, d in keys]
+    first = [CACHE.pack(w, c0, c, d).packed.clone() for w, c0, c, d in keys]
     with torch.no_grad():
         for w in weights:
             w.copy_(torch.randn(w.shape, generator=g).cuda())
     A.bump_generation()
-    again = [A._pack(w, c0, c, d) for w, c0, c, d in keys]          # the first call re-packs every stale operand
+    again = [CACHE.pack(w, c0, c, d).packed for w, c0, c, d in keys]          # the first call re-packs every stale operand
     lib = _lib.load()
     for (w, c0, c, d), old, new in zip(keys, first, again):
         want = torch.empty_like(new)
@@ -405,11 +406,12 @@ def test_standardize_all_equals_the_single_launches():
     """zs_standardize_weight_multi (one launch for every stale StdConv weight after an optimiser step) writes exactly what
     zs_standardize_weight writes per weight; fresh weights are skipped, a repeated weight is standardised once."""
     from zeroshape_amd.nn import autograd as A
-    A.clear_pack_cache()
+    from zeroshape_amd.nn.operands import CACHE, stamp
+    CACHE.clear()
     g = torch.Generator().manual_seed(9)
     shapes = [(64, 3, 7, 7), (256, 64, 1, 1), (64, 64, 3, 3), (1024, 512, 1, 1), (10, 6, 3, 3), (1, 32, 1, 1)]
     ws = [torch.nn.Parameter(torch.randn(s, generator=g).cuda()) for s in shapes]
-    want = [A.standardize(w, 1e-8).clone() for w in ws]                    # single launches
+    want = [CACHE.standardize(w, 1e-8).clone() for w in ws]                    # single launches
     with torch.no_grad():
         for w in ws:
             w.mul_(1.5).add_(0.25)
@@ -418,10 +420,10 @@ def test_standardize_all_equals_the_single_launches():
     for w in ws:
         m = w.detach().reshape(w.shape[0], -1)
         want2.append(((m - m.mean(1, keepdim=True)) / torch.sqrt(m.var(1, unbiased=False, keepdim=True) + 1e-8)).reshape(w.shape))
-    A.standardize_all([(w, 1e-8) for w in ws] + [(ws[1], 1e-8)])           # one launch (ws[1] listed twice)
+    CACHE.standardize_all([(w, 1e-8) for w in ws] + [(ws[1], 1e-8)])           # one launch (ws[1] listed twice)
     for w, old, ref in zip(ws, want, want2):
-        got = A._STD[id(w)][2]
-        assert A._STD[id(w)][3] == A._stamp(w)
+        got = CACHE.std[id(w)].buffer
+        assert CACHE.std[id(w)].stamp == stamp(w)
         assert not torch.equal(got, old) or w.shape[0] == 1
         single = torch.empty_like(got)
         from zeroshape_amd import _lib
@@ -430,7 +432,7 @@ def test_standardize_all_equals_the_single_launches():
                                                          _lib.current_stream_ptr(w.device)), "zs_standardize_weight")
         assert torch.equal(got, single), tuple(w.shape)
         close(got, ref.cpu(), rtol=1e-5, what="standardised weight")
-    A.clear_pack_cache()
+    CACHE.clear()
 
 
 @pytest.mark.gpu
@@ -442,28 +444,29 @@ def test_repack_writes_the_fp16_halves_itself(fwd, bwd, monkeypatch):
     channel counts, 7x7) are split by the launch behind it as before."""
     from zeroshape_amd import _lib
     from zeroshape_amd.nn import autograd as A
-    A.clear_pack_cache()
+    from zeroshape_amd.nn.operands import CACHE, SWITCHES
+    CACHE.clear()
     A.set_forward_precision(fwd)
     A.set_backward_precision(bwd)
     try:
-        assert A._inline_split_mode() == (2 if bwd == "f16x3" else 1)
+        assert SWITCHES.inline_split_mode() == (2 if bwd == "f16x3" else 1)
         g = torch.Generator().manual_seed(6)
         shapes = [(3072, 768, 1, 1), (768, 3072, 1, 1), (256, 256, 3, 3), (64, 3, 7, 7), (10, 6, 3, 3), (130, 70, 1, 1),
                   (32, 128, 3, 3), (48, 32, 1, 1), (96, 64, 2, 2)]
         weights = [torch.nn.Parameter(torch.randn(s, generator=g).cuda()) for s in shapes]
         keys = [(w, 0, w.shape[1], d) for w in weights for d in (False, True)]
         keys += [(weights[2], 64, 128, False), (weights[2], 64, 128, True)]
-        first = [A._pack(w, c0, c, d).clone() for w, c0, c, d in keys]
+        first = [CACHE.pack(w, c0, c, d).packed.clone() for w, c0, c, d in keys]
         with torch.no_grad():
             for w in weights:
                 w.copy_(torch.randn(w.shape, generator=g).cuda())
         A.bump_generation()
-        A._pack(*keys[0])                       # re-packs (and splits) every stale operand
+        CACHE.pack(*keys[0])                       # re-packs (and splits) every stale operand
         lib = _lib.load()
         inline = 0
         for (w, c0, c, d), old in zip(keys, first):
-            packed = A._pack(w, c0, c, d)
-            rec = A._rec_of(packed)
+            rec = CACHE.pack(w, c0, c, d)
+            packed = rec.packed
             kh, kw = w.shape[2], w.shape[3]
             want, want_split = torch.empty_like(packed), torch.empty_like(packed)
             cout, cin = (c, w.shape[0]) if d else (w.shape[0], c)      # the operand's N and K-side channel counts
@@ -473,8 +476,8 @@ def test_repack_writes_the_fp16_halves_itself(fwd, bwd, monkeypatch):
                                                    1 if d else 0, st), "zs_pack_conv_weight")
                 _lib.check(lib.zs_conv2d_presplit_weight(_lib.ptr(want), _lib.ptr(want_split), (cin + 3) // 4 * 4, cout, kh, kw,
                                                          st), "zs_conv2d_presplit_weight")
-            assert A._split_of(packed) is not None, (tuple(w.shape), c0, c, d)
-            assert torch.equal(A._split_of(packed).view(torch.int32), want_split.view(torch.int32)), (tuple(w.shape), c0, c, d)
+            assert CACHE.split_of(rec) is not None, (tuple(w.shape), c0, c, d)
+            assert torch.equal(CACHE.split_of(rec).view(torch.int32), want_split.view(torch.int32)), (tuple(w.shape), c0, c, d)
             eligible = bool(lib.zs_pack_entry_inline_split(w.shape[0], c, kh * kw, 1 if d else 0))
             assert rec.inline_split == eligible
             inline += eligible
@@ -487,7 +490,7 @@ def test_repack_writes_the_fp16_halves_itself(fwd, bwd, monkeypatch):
         A.set_forward_precision("f32")
         A.set_backward_precision("f32")
         for (w, c0, c, d) in keys[:6]:
-            packed = A._pack(w, c0, c, d)
+            packed = CACHE.pack(w, c0, c, d).packed
             want = torch.empty_like(packed)
             with torch.cuda.device(w.device):
                 _lib.check(lib.zs_pack_conv_weight(_lib.ptr(w.detach()), _lib.ptr(want), w.shape[0], c, c0, w.shape[1],
@@ -497,7 +500,7 @@ def test_repack_writes_the_fp16_halves_itself(fwd, bwd, monkeypatch):
     finally:
         A.set_forward_precision("f32")
         A.set_backward_precision("f32")
-        A.clear_pack_cache()
+        CACHE.clear()
 
 
 @pytest.mark.gpu
@@ -507,9 +510,10 @@ def test_split_operand_follows_in_place_weight_updates(presplit_all, monkeypatch
     weight changed by torch without bump_generation() - load_state_dict, w.mul_() under no_grad, a torch optimiser - kept computing
     with the old split.  The split now lives on the pack record and is stamped with the pack it was made from."""
     from zeroshape_amd.nn import autograd as A
-    monkeypatch.setattr(A, "FWD_CONV_PRECISION", "f16x3")
-    monkeypatch.setattr(A, "PRESPLIT_ALL", presplit_all)
-    monkeypatch.setattr(A, "PRESPLIT_MIN_TILES", 1)            # every layer takes the pre-split path
+    from zeroshape_amd.nn.operands import SWITCHES
+    monkeypatch.setattr(SWITCHES, "forward", "f16x3")
+    monkeypatch.setattr(SWITCHES, "presplit_all", presplit_all)
+    monkeypatch.setattr(SWITCHES, "presplit_min_tiles", 1)            # every layer takes the pre-split path
     g = torch.Generator().manual_seed(5)
     x = torch.randn(2, 16, 16, 32, generator=g).cuda()          # channels-last
     w = (torch.randn(64, 32, 3, 3, generator=g) / 17.0).cuda().requires_grad_(True)

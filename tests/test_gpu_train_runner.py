@@ -259,6 +259,7 @@ def test_optim_amp_runs_the_forward_convolutions_in_split_fp16(tmp_path, encoder
     forward GEMMs on the 16-bit matrix pipe with split operands, everything else fp32 - same loss to 1e-4 relative,
     the step updates the weights, and a runner built without the flag is back on fp32."""
     from zeroshape_amd.nn import autograd as A
+    from zeroshape_amd.nn.operands import SWITCHES
     from zeroshape_amd.utils import util
     from zeroshape_amd.utils.options import EasyDict as edict
     losses = {}
@@ -266,7 +267,7 @@ def test_optim_amp_runs_the_forward_convolutions_in_split_fp16(tmp_path, encoder
         for amp in (False, True):
             opt = train_opt(tmp_path, *(["--optim.amp"] if amp else []))
             r = make_runner(opt, encoder_sd, seeded_sd, n_train=4)
-            assert A.FWD_CONV_PRECISION == A.BWD_DATA_PRECISION == ("f16x3" if amp else "f32")
+            assert SWITCHES.forward == SWITCHES.backward == ("f16x3" if amp else "f32")
             assert hasattr(r, "scaler") == amp
             r.graph.train()
             batch = next(iter(torch.utils.data.DataLoader(r.train_data, batch_size=4, shuffle=False)))

@@ -97,37 +97,38 @@ def test_inline_split_mode_follows_the_precisions_and_a_change_re_packs_everythi
     forward AND data gradients read the halves, and any precision change moves the generation (stale fp32 operands must not
     be served after switching back)."""
     from zeroshape_amd.nn import autograd as A
+    from zeroshape_amd.nn.operands import SWITCHES
     try:
         A.set_forward_precision("f32")
         A.set_backward_precision("f32")
-        assert A._inline_split_mode() == 0
+        assert SWITCHES.inline_split_mode() == 0
         g0 = A.GENERATION[0]
         A.set_forward_precision("f16x3")
-        assert A.GENERATION[0] == g0 + 1 and A._inline_split_mode() == 1
+        assert A.GENERATION[0] == g0 + 1 and SWITCHES.inline_split_mode() == 1
         A.set_forward_precision("f16x3")                    # no change: no re-pack
         assert A.GENERATION[0] == g0 + 1
         A.set_backward_precision("f16x3")
-        assert A.GENERATION[0] == g0 + 2 and A._inline_split_mode() == 2
+        assert A.GENERATION[0] == g0 + 2 and SWITCHES.inline_split_mode() == 2
         A.set_forward_precision("f32")
-        assert A._inline_split_mode() == 1                  # the data gradients still read halves, the forward reads fp32
+        assert SWITCHES.inline_split_mode() == 1                  # the data gradients still read halves, the forward reads fp32
     finally:
         A.set_forward_precision("f32")
         A.set_backward_precision("f32")
 
 
 def test_operand_form_switches_are_part_of_the_stamp():
-    """flipping PRESPLIT_ALL / INLINE_SPLIT at run time (tools, A/B tests) must make every packed operand stale -
+    """flipping presplit_all / inline_split at run time (tools, A/B tests) must make every packed operand stale -
     in inline-split mode 2 the fp32 form has not been rewritten since the mode was entered."""
-    from zeroshape_amd.nn import autograd as A
+    from zeroshape_amd.nn.operands import SWITCHES, stamp
     w = torch.zeros(4, 4)
-    keep = (A.PRESPLIT_ALL, A.INLINE_SPLIT)
+    keep = (SWITCHES.presplit_all, SWITCHES.inline_split)
     try:
-        s0 = A._stamp(w)
-        A.PRESPLIT_ALL = not keep[0]
-        s1 = A._stamp(w)
-        A.INLINE_SPLIT = not keep[1]
-        s2 = A._stamp(w)
+        s0 = stamp(w)
+        SWITCHES.presplit_all = not keep[0]
+        s1 = stamp(w)
+        SWITCHES.inline_split = not keep[1]
+        s2 = stamp(w)
         assert len({s0, s1, s2}) == 3
     finally:
-        A.PRESPLIT_ALL, A.INLINE_SPLIT = keep
-    assert A._stamp(w) == s0
+        SWITCHES.presplit_all, SWITCHES.inline_split = keep
+    assert stamp(w) == s0

@@ -86,25 +86,50 @@ def test_compat_aliases_cover_what_the_reference_scripts_import():
                 sys.modules[k] = v
 
 
-def test_repack_scan_survives_a_weight_collected_mid_scan(monkeypatch):
-    """A weight that dies while _refresh_all_packs walks the registry (the garbage collector runs on an allocation inside the
+def test_repack_scan_survives_a_weight_collected_mid_scan():
+    """A weight that dies while the re-pack scan walks the registry (the garbage collector runs on an allocation inside the
     walk, and the weight's weakref callback drops its record) must not break the scan: a training step used to fail with
     'dictionary changed size during iteration' right after an earlier model had been dropped."""
-    from zeroshape_amd.nn import autograd as A
+    from zeroshape_amd.nn import operands
 
     class Registry(dict):
         def items(self):            # a collection in the middle of any walk over the live registry
             for n, kv in enumerate(dict.items(self)):
                 if n == 1:
-                    A._drop_pack((2, 4, 4, False, None))
+                    cache.drop((2, 4, 4, False, None))
                 yield kv
 
-    monkeypatch.setattr(A, "_PACKS", Registry())
-    monkeypatch.setattr(A, "_PACK_FAST", {})
+    cache = operands.OperandCache()
+    cache.packs = Registry()
     weights = [torch.zeros(4, 4) for _ in range(3)]
     for i, w in enumerate(weights):
-        rec = A._PackRec()
+        rec = operands._PackRec()
         rec.key, rec.stamp, rec.ref = (i, 4, 4, False, None), None, (lambda w=w: w)
-        A._PACKS[rec.key] = rec
-    A._refresh_all_packs_only(torch.device("cuda", 0))      # CPU weights: nothing to re-pack on cuda:0, nothing launched
-    assert len(A._PACKS) == 3
+        cache.packs[rec.key] = rec
+    cache.repack(torch.device("cuda", 0))      # CPU weights: nothing to re-pack on cuda:0, nothing launched
+    assert len(cache.packs) == 3
+
+
+def test_a_collected_weight_moves_the_epoch_and_refuses_the_fast_replay():
+    """The replay of the last complete re-pack (the optimiser-step path) is only valid for the same set of records: a weight
+    that dies takes its record with it through the weakref callback, the epoch moves and the replay is refused."""
+    import gc
+    import weakref
+    from zeroshape_amd.nn import operands
+    cache = operands.OperandCache()
+    device = torch.device("cpu")
+    weights = [torch.zeros(4, 4) for _ in range(2)]
+    for w in weights:
+        rec = operands._PackRec()
+        rec.key, rec.stamp = (id(w), 0, 4, False, None), None
+        rec.ref = weakref.ref(w, lambda _r, k=rec.key: cache.drop(k))       # as OperandCache.pack() registers it
+        cache.packs[rec.key] = rec
+    recs = list(cache.packs.values())
+    cache.fast[device] = dict(epoch=cache.epoch, generation=operands.GENERATION[0] - 1, recs=recs,
+                              ptrs=[w.data_ptr() for w in weights])
+    assert [w for _, w in cache.replayable(device)] == weights
+    epoch = cache.epoch
+    del w, weights[1]
+    gc.collect()
+    assert len(cache.packs) == 1 and cache.epoch == epoch + 1
+    assert cache.replayable(device) is None

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from ...nn import autograd as A
+from ...nn.operands import weights_stamp
 from ...nn import blocks, ops, pack, train_blocks
 from ...nn import branch
 from ...nn.branch import Branch
@@ -44,7 +45,7 @@ class _IntrHead(HipModule):
     def _tensors_key(self):
         g = self._graph
         ts = list(g.intr_head.parameters()) + list(g.intr_head.buffers()) + list(g.intr_proj.parameters())
-        return (A.GENERATION[0],) + tuple((t.data_ptr(), t._version) for t in ts)
+        return weights_stamp(ts)
 
     def state_dict(self, *a, **k):
         g = self._graph
@@ -168,10 +169,8 @@ class Graph(nn.Module):
         if not self._use_hip_graph:
             return run(rgb, mask)
         from ...nn.capture import CapturedCall
-        from ...nn import autograd as A
-        wkey = (A.GENERATION[0],) + tuple((t.data_ptr(), t._version) for m in (self.dpt_depth, self.intr_head,
-                                                                                self.intr_proj, self.coord_encoder)
-                                          for t in list(m.parameters()) + list(m.buffers()))
+        wkey = weights_stamp(t for m in (self.dpt_depth, self.intr_head, self.intr_proj, self.coord_encoder)
+                             for t in list(m.parameters()) + list(m.buffers()))
         key = (tuple(rgb.shape), str(rgb.device), dsp, resnet)
         hit = self._captured.get(key)
         if hit is None or hit[0] != wkey:

@@ -34,6 +34,7 @@ import torch.nn as nn
 from ... import _lib
 from ... import program as P
 from ...nn import autograd as A
+from ...nn.operands import weights_stamp
 from ...utils.pos_embed import get_2d_sincos_pos_embed
 
 
@@ -212,7 +213,8 @@ class Implicit(nn.Module):
                                       "at least one attention block" % (c["num_patches"] + 1))
 
     def _weights_key(self):
-        return (A.GENERATION[0], bool(self.pos_perlayer)) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        key = weights_stamp(self.parameters())
+        return key[:1] + (bool(self.pos_perlayer),) + key[1:]
 
     def packed(self, device):
         """(template program [PROGRAM_FLOATS], lat_params) on ``device``; repacked when any

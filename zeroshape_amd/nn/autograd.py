@@ -4,68 +4,30 @@ Every op here is a torch.autograd.Function whose forward AND backward are launch
 libzeroshape_hip.so; torch supplies the tape, the tensor memory and the stream, nothing else.
 Activations are fp32 channels-last ([B,H,W,C]; token matrices [B,L,C]), parameters stay in the
 reference's torch layout ([Cout,Cin,kh,kw] / [Cout,Cin]) and are re-packed on the GPU when they
-change (zs_pack_conv_weight), so optimiser steps need no host work.
+change (zs_pack_conv_weight; nn/operands.py owns the packed forms), so optimiser steps need no host work.
 
 Reference behaviour reproduced: what torch.autograd gives train.py for Graph.forward(training=True)
 (model/compute_graph/graph_shape.py:115-204) and Loss.shape_loss (utils/loss.py:18-28).
 """
-import contextlib
 import os
 
 import torch
 
 from .. import _lib
+# The packed / standardised / split forms of the weights and the switches that choose among them have one owner, nn/operands.py;
+# the second line of names is here for the callers outside nn/ (engines, optimiser, checkpoint loading, tools).
+from .operands import CACHE, CONV_F16X3, CONV_IN_DILATE2, CONV_IN_RELU, SWITCHES, ceil4
+from .operands import GENERATION, bump_generation, refresh_packs, set_backward_precision, set_forward_precision  # noqa: F401
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_CLAMP1, ACT_SOFTPLUS = 0, 1, 2, 3, 4
-_CONV_IN_RELU, _CONV_IN_DILATE2 = 1, 8
-_CONV_F16X3 = 16
-# Bumped whenever parameters are updated through raw pointers (the fused optimiser): tensor
-# ._version does not see those writes, so every pack cache also keys on this counter.
-GENERATION = [0]
-# Arithmetic of the FORWARD convolutions / linear layers of the training path: "f32" (default) or
-# "f16x3" = split-fp16 (opt-in: 15.4 -> 14.4 ms forward per step at batch 4, but the 1e-6 forward
-# differences are amplified by the batch-statistics BatchNorms to ~2e-3 relative in some gradients,
-# beyond this repository's gradient parity bar).
-FWD_CONV_PRECISION = os.environ.get("ZS_TRAIN_FWD_PRECISION", "f32")
-
-
-def set_forward_precision(p):
-    """"f32" | "f16x3": arithmetic of the forward convolutions / linear layers under autograd (optim.amp selects
-    "f16x3": the 16-bit matrix pipe with split operands, fp32 accumulation)."""
-    global FWD_CONV_PRECISION
-    if p not in ("f32", "f16x3"):
-        raise ValueError("forward precision must be 'f32' or 'f16x3', got %r" % (p,))
-    if p != FWD_CONV_PRECISION:
-        GENERATION[0] += 1      # operands re-packed under the other setting may hold only the form that one reads
-    FWD_CONV_PRECISION = p
-
-# Data gradients (dx = dy * W^T through the same convolution engine).  "f16x3" needs the incoming gradients inside
-# fp16's range: the Runner multiplies the loss by a dynamic power of two (optim.LossScaler, torch's GradScaler
-# rules) and the optimiser divides it out, an overflow (inf / nan in any gradient) skips the step and halves the
-# scale.  Weight gradients stay exact fp32 (they sum over every pixel of the batch).
-BWD_DATA_PRECISION = os.environ.get("ZS_TRAIN_BWD_PRECISION", "f32")
-
-
-# ... and of the weight-gradient GEMMs (zs_conv2d_wgrad with ZS_CONV_F16X3: wgrad_split_kernel, round 3).  Follows the
-# data-gradient setting (optim.amp) unless ZS_TRAIN_WGRAD_PRECISION pins it (A/B measurements).
+# Arithmetic of the weight-gradient GEMMs (zs_conv2d_wgrad with ZS_CONV_F16X3: wgrad_split_kernel, round 3).  Follows the
+# data-gradient setting (optim.amp) unless ZS_TRAIN_WGRAD_PRECISION pins it (A/B measurements).  It stays beside its one reader,
+# _Conv.backward: a weight gradient reads activations and gradients, no cached operand, so no operand's stamp depends on it.
 BWD_WGRAD_PRECISION = os.environ.get("ZS_TRAIN_WGRAD_PRECISION")
 
 
 def wgrad_precision():
-    return BWD_WGRAD_PRECISION or BWD_DATA_PRECISION
-
-
-def set_backward_precision(p):
-    global BWD_DATA_PRECISION
-    if p not in ("f32", "f16x3"):
-        raise ValueError("data-gradient precision must be 'f32' or 'f16x3', got %r" % (p,))
-    if p != BWD_DATA_PRECISION:
-        GENERATION[0] += 1
-    BWD_DATA_PRECISION = p
-
-
-def bump_generation():
-    GENERATION[0] += 1
+    return BWD_WGRAD_PRECISION or SWITCHES.backward
 
 
 def _stream(t):
@@ -109,304 +71,6 @@ def scratch(device, name, nbytes):
     return buf
 
 
-def _ceil4(n):
-    return (n + 3) // 4 * 4
-
-
-def _stamp(w):
-    # ... and the switches that decide WHICH forms of a packed operand are kept current (in mode 2 the re-pack
-    # writes only the fp16 halves; a tool or test that flips PRESPLIT_ALL / INLINE_SPLIT at run time must find every record
-    # stale, not a fresh-looking stamp over an fp32 operand nobody has rewritten since)
-    return (w.data_ptr(), w._version, GENERATION[0], _operand_forms())
-
-
-def _operand_forms():
-    g = globals()
-    return (bool(g.get("PRESPLIT_ALL", True)), bool(g.get("INLINE_SPLIT", True)), FWD_CONV_PRECISION == "f16x3", BWD_DATA_PRECISION == "f16x3")
-
-
-_STD = {}       # id(weight) -> [weakref, eps, buffer, stamp]: standardised weights in persistent buffers
-
-
-def standardize(weight, eps):
-    """timm StdConv2d weight standardisation of a Parameter, refreshed when the weight changes."""
-    import weakref
-    rec = _STD.get(id(weight))
-    if rec is None or rec[0]() is not weight or rec[1] != float(eps):
-        rec = [weakref.ref(weight, lambda _r, k=id(weight): _STD.pop(k, None)), float(eps),
-               torch.empty_like(weight.detach()), None]
-        _STD[id(weight)] = rec
-    if rec[3] != _stamp(weight):
-        lib = _lib.load()
-        w = weight.detach()
-        with _lib.on(w.device):
-            _lib.check(lib.zs_standardize_weight(_lib.ptr(w), _lib.ptr(rec[2]), w.shape[0], w[0].numel(), float(eps),
-                                                 _stream(w)), "zs_standardize_weight")
-        rec[3] = _stamp(weight)
-    return rec[2]
-
-
-_STD_TABLE = {}     # device -> (signature, entry table, row prefix, entries, rows): the launch table of standardize_all
-
-
-def standardize_all(pairs):
-    """standardize() for a list of (weight, eps) in ONE launch (zs_standardize_weight_multi): the stale ones of the list go
-    through a cached device table - after an optimiser step that is every StdConv weight of the model (52 launches before)."""
-    import numpy as np
-    import weakref
-    todo, seen = [], set()
-    for weight, eps in pairs:
-        rec = _STD.get(id(weight))
-        if rec is None or rec[0]() is not weight or rec[1] != float(eps):
-            rec = [weakref.ref(weight, lambda _r, k=id(weight): _STD.pop(k, None)), float(eps),
-                   torch.empty_like(weight.detach()), None]
-            _STD[id(weight)] = rec
-        if rec[3] != _stamp(weight) and id(weight) not in seen:
-            seen.add(id(weight))
-            todo.append((weight, rec))
-    if not todo:
-        return
-    if len(todo) == 1:
-        standardize(todo[0][0], todo[0][1][1])
-        return
-    lib = _lib.load()
-    device = todo[0][0].device
-    sig = tuple((w.data_ptr(), rec[2].data_ptr(), w.shape[0], w[0].numel(), rec[1]) for w, rec in todo)
-    cached = _STD_TABLE.get(device)
-    if cached is None or cached[0] != sig:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("the set of standardised weights changed inside a stream capture; call "
-                               "zeroshape_amd.nn.autograd.refresh_packs(device) before capturing")
-        dt = np.dtype([("w", "<u8"), ("out", "<u8"), ("rows", "<i4"), ("n", "<i4"), ("eps", "<f4"), ("pad", "<i4")])
-        assert dt.itemsize == 32
-        tab = np.zeros(len(sig), dt)
-        prefix, total = [], 0
-        for i, e in enumerate(sig):
-            tab[i] = e + (0,)
-            prefix.append(total)
-            total += e[2]
-        cached = (sig, torch.from_numpy(tab.view(np.uint8).reshape(-1)).to(device),
-                  torch.tensor(prefix, dtype=torch.int32).to(device), len(sig), total)
-        _STD_TABLE[device] = cached
-    _, tab_d, pre_d, n, total = cached
-    with _lib.on(device):
-        _lib.check(lib.zs_standardize_weight_multi(_lib.ptr(tab_d), _lib.ptr(pre_d), n, total, _lib.current_stream_ptr(device)),
-                   "zs_standardize_weight_multi")
-    for w, rec in todo:
-        rec[3] = _stamp(w)
-
-
-# ---- packed GEMM operands: persistent buffers, re-packed for ALL layers in one launch ----
-class _PackRec(object):
-    # split / split_stamp: the operand's fp16 halves (optim.amp) and the stamp of the pack they were made from - a re-pack
-    # (in-place weight update, load_state_dict, optimiser step) moves `stamp` and so invalidates the split with it; the
-    # buffer dies with the record (ADVICE r03: a cache keyed by packed.data_ptr() + generation served stale weights)
-    # inline_split: the multi re-pack writes this operand's halves itself (zs_pack_conv_weight_multi_split)
-    __slots__ = ("ref", "key", "packed", "stamp", "dims", "split", "split_stamp", "inline_split", "__weakref__")
-
-
-_PACKS = {}     # (id(weight), cin0, cin, dgrad, std_eps) -> _PackRec
-_PACK_TABLE = {}    # device -> (signature, table tensors)
-_PACK_EPOCH = [0]   # bumped whenever _PACKS gains or loses a record
-_PACK_FAST = {}     # device -> dict(epoch, generation, recs, std): the last complete re-pack, for its replay
-
-
-def _drop_pack(key):
-    if _PACKS.pop(key, None) is not None:
-        _PACK_EPOCH[0] += 1
-
-
-def clear_pack_cache():
-    _PACKS.clear()
-    _STD.clear()
-    _STD_TABLE.clear()
-    _PACK_TABLE.clear()
-    _PACK_FAST.clear()
-    _PACK_EPOCH[0] += 1
-
-
-def _pack_dims(w, cin, dgrad):
-    cout, cintot = w.shape[0], w.shape[1]
-    kh, kw = (w.shape[2], w.shape[3]) if w.dim() == 4 else (1, 1)
-    taps = kh * kw
-    kc, n = (_ceil4(cout), cin) if dgrad else (_ceil4(cin), cout)
-    return cout, cintot, kh, kw, taps, (taps * kc + 15) // 16 * 16, (n + 127) // 128 * 128
-
-
-INLINE_SPLIT = os.environ.get("ZS_TRAIN_INLINE_SPLIT", "1") != "0"      # A/B switch
-
-
-def _inline_split_mode():
-    """0: re-pack only.  1: the re-pack also writes the fp16 halves.  2: ... and leaves the fp32 operands of those entries
-    alone (forward AND data gradients read the halves: nothing reads the fp32 form until the precision changes, which
-    bumps the generation and so re-packs everything)."""
-    if not (INLINE_SPLIT and _amp_splits_operands()):
-        return 0
-    return 2 if FWD_CONV_PRECISION == "f16x3" and BWD_DATA_PRECISION == "f16x3" else 1
-
-
-def _launch_multi_pack(lib, device, recs):
-    _, tab_d, ce_d, cs_d, n, split_d, _splits = _PACK_TABLE[device]
-    with _lib.on(device):
-        if split_d is None:
-            _lib.check(lib.zs_pack_conv_weight_multi(_lib.ptr(tab_d), _lib.ptr(ce_d), _lib.ptr(cs_d), n,
-                                                     _lib.current_stream_ptr(device)), "zs_pack_conv_weight_multi")
-        else:
-            _lib.check(lib.zs_pack_conv_weight_multi_split(_lib.ptr(tab_d), _lib.ptr(ce_d), _lib.ptr(cs_d), n,
-                                                           _lib.ptr(split_d), 1 if _PACK_TABLE[device][0][-1] == 2 else 0,
-                                                           _lib.current_stream_ptr(device)),
-                       "zs_pack_conv_weight_multi_split")
-
-
-def _mark_inline_splits(device, recs):
-    """After the launch and the new stamps: the halves written by the re-pack are those of the current operand."""
-    if _PACK_TABLE[device][5] is not None:
-        for rec in recs:
-            if rec.inline_split and rec.split is not None:
-                rec.split_stamp = rec.stamp
-
-
-def _refresh_all_packs(device):
-    """Re-pack every registered operand on `device` whose weight changed, in ONE launch."""
-    import numpy as np
-    lib = _lib.load()
-    # The state after an optimiser step (every step of a training run): the same records as the last time, all of
-    # them stale because the generation moved.  Replay that re-pack - standardise the StdConv weights into their
-    # persistent buffers, launch over the cached table - without rebuilding the entry list.
-    fast = _PACK_FAST.get(device)
-    if fast is not None and fast["epoch"] == _PACK_EPOCH[0] and fast["generation"] != GENERATION[0]:
-        live = [(rec, rec.ref()) for rec in fast["recs"]]
-        if all(w is not None and w.data_ptr() == ptr for (rec, w), ptr in zip(live, fast["ptrs"])):
-            standardize_all([(w, rec.key[4]) for rec, w in live if rec.key[4] is not None])
-            if _PACK_TABLE[device][0][-1] == _inline_split_mode():
-                _launch_multi_pack(lib, device, [rec for rec, _ in live])
-                for rec, w in live:
-                    rec.stamp = _stamp(w)
-                _mark_inline_splits(device, [rec for rec, _ in live])
-                fast["generation"] = GENERATION[0]
-                return
-    recs = []
-    # iterate over a copy: a weight collected while the loop allocates fires its weakref callback (_drop_pack) mid-loop
-    packs = _PACKS.copy()
-    for key, rec in packs.items():
-        w = rec.ref()
-        if w is None:
-            _drop_pack(key)
-        elif w.device == device and rec.stamp != _stamp(w):
-            recs.append((rec, w))
-    if not recs:
-        return
-    complete = len(recs) == sum(1 for rec in _PACKS.copy().values() if rec.ref() is not None and rec.ref().device == device)
-    entries = []
-    standardize_all([(w, rec.key[4]) for rec, w in recs if rec.key[4] is not None and w.device == device])
-    for rec, w in recs:
-        _, cin0, cin, dgrad, std_eps = rec.key
-        src = standardize(w, std_eps) if std_eps is not None else w.detach()
-        cout, cintot, kh, kw, taps, K16, NPad = rec.dims
-        entries.append((src.data_ptr(), rec.packed.data_ptr(), cout, cin, cin0, cintot * taps, taps, 1 if dgrad else 0,
-                        K16, NPad))
-    mode = _inline_split_mode()
-    sig = tuple(entries) + (mode,)
-    cached = _PACK_TABLE.get(device)
-    if cached is None or cached[0] != sig:
-        if torch.cuda.is_current_stream_capturing():
-            # the table would travel by a host-to-device copy from pageable memory: not capturable (the graph
-            # would keep the host address).  refresh_packs() before the capture builds it.
-            raise RuntimeError("the set of packed operands changed inside a stream capture; call "
-                               "zeroshape_amd.nn.autograd.refresh_packs(device) before capturing")
-        dt = np.dtype([("src", "<u8"), ("dst", "<u8")] + [(n, "<i4") for n in ("Cout", "Cin", "cin0", "ld", "taps", "dgrad",
-                                                                             "K16", "NPad")])
-        assert dt.itemsize == 48
-        tab = np.zeros(len(entries), dt)
-        ce, cs = [], []
-        for i, e in enumerate(entries):
-            tab[i] = e
-            n_chunks = lib.zs_pack_entry_chunks(e[2], e[3], e[6], e[7], e[8], e[9])
-            _lib.check(1 if n_chunks > 0 else 0, "zs_pack_entry_chunks")
-            starts = np.arange(n_chunks, dtype=np.uint64)
-            ce.append(np.full(len(starts), i, np.int32))
-            cs.append(starts)
-        ce, cs = np.concatenate(ce), np.concatenate(cs)
-        # optim.amp: the halves of every operand whose tiles hold whole K = 16 groups leave the same launch (split_d: one
-        # pointer per entry, 0 = the operand is split by _presplit_all's launch behind this one)
-        split_d, splits = None, []
-        if mode:
-            ptrs = []
-            for (rec, _), e in zip(recs, entries):
-                rec.inline_split = bool(lib.zs_pack_entry_inline_split(e[2], e[3], e[6], e[7]))
-                if rec.inline_split:
-                    if rec.split is None or rec.split.numel() != rec.packed.numel() or rec.split.device != device:
-                        rec.split = torch.empty_like(rec.packed)
-                    ptrs.append(rec.split.data_ptr())
-                    splits.append(rec.split)
-                else:
-                    ptrs.append(0)
-            split_d = torch.tensor(ptrs, dtype=torch.int64).to(device)
-        else:
-            for rec, _ in recs:
-                rec.inline_split = False
-        cached = (sig, torch.from_numpy(tab.view(np.uint8).reshape(-1)).to(device), torch.from_numpy(ce).to(device),
-                  torch.from_numpy(cs.view(np.int64)).to(device), len(ce), split_d, splits)
-        _PACK_TABLE[device] = cached
-    _launch_multi_pack(lib, device, [rec for rec, _ in recs])
-    for rec, w in recs:
-        rec.stamp = _stamp(w)
-    _mark_inline_splits(device, [rec for rec, _ in recs])
-    if complete:
-        _PACK_FAST[device] = dict(epoch=_PACK_EPOCH[0], generation=GENERATION[0], recs=[rec for rec, _ in recs],
-                                  ptrs=[w.data_ptr() for _, w in recs])
-    else:
-        _PACK_FAST.pop(device, None)
-
-
-_refresh_all_packs_only = _refresh_all_packs
-
-
-def _refresh_all_packs(device):      # noqa: F811 - the re-pack, then (optim.amp) the split of every operand
-    _refresh_all_packs_only(device)
-    if _amp_splits_operands():
-        _presplit_all(device)
-
-
-def refresh_packs(device):
-    """Re-pack every registered operand on `device` now (and leave the launch table of that set cached): what a
-    stream capture of a training step must do first, so that the re-pack inside the capture finds its table."""
-    bump_generation()
-    _refresh_all_packs(torch.device(device) if not isinstance(device, torch.device) else device)
-
-
-def _pack(weight, cin0, cin, dgrad, std_eps=None):
-    """Packed GEMM operand of `weight` (torch layout [Cout, CinTot(, kh, kw)], optionally
-    standardised first) for the forward product (dgrad=False) or the data gradient.  Operands live
-    in persistent buffers; the first use of a layer packs it alone, afterwards a stale operand
-    triggers ONE launch that re-packs every registered operand whose weight changed (the state after
-    an optimiser step), instead of ~450 small launches per training step."""
-    import weakref
-    key = (id(weight), cin0, cin, bool(dgrad), std_eps)
-    rec = _PACKS.get(key)
-    if rec is not None and rec.ref() is weight:
-        if rec.stamp != _stamp(weight):
-            _refresh_all_packs(weight.device)
-        return rec.packed
-    lib = _lib.load()
-    w = standardize(weight, std_eps) if std_eps is not None else weight.detach()
-    dims = _pack_dims(w, cin, dgrad)
-    cout, cintot, kh, kw, taps, K16, NPad = dims
-    rec = _PackRec()
-    rec.ref = weakref.ref(weight, lambda _r, k=key: _drop_pack(k))
-    rec.key, rec.dims = key, dims
-    rec.packed = torch.empty(K16 * NPad, dtype=torch.float32, device=w.device)
-    rec.split, rec.split_stamp, rec.inline_split = None, None, False
-    rec.packed._zs_rec = weakref.ref(rec)              # _conv_launch finds the record (and its split) from the operand
-    with _lib.on(w.device):
-        _lib.check(lib.zs_pack_conv_weight(_lib.ptr(w), _lib.ptr(rec.packed), cout, cin, cin0, cintot, kh, kw,
-                                           1 if dgrad else 0, _stream(w)), "zs_pack_conv_weight")
-    rec.stamp = _stamp(weight)
-    _PACKS[key] = rec
-    _PACK_EPOCH[0] += 1
-    return rec.packed
-
-
 def _out_size(n, k, stride, padding):
     if padding == "same":
         out = -(-n // stride)
@@ -414,100 +78,11 @@ def _out_size(n, k, stride, padding):
     return (n + 2 * padding - k) // stride + 1, padding
 
 
-_CONV_W_PRESPLIT = 128
-_PRESPLIT_TABLE = {}    # device -> (signature, device arrays of zs_conv2d_presplit_weight_multi, n, total pairs, splits)
-# ONE launch right behind the re-pack splits every registered operand (zs_conv2d_presplit_weight_multi), so every split-fp16
-# kernel reads ready halves and the 40 per-layer split launches go.  Round 3 measured this SLOWER (29.75 -> 30.1 ms: the
-# small-tile kernels are latency-bound and the split of 192 M parameters moves 1.5 GB); since round 4 the few-row pointwise
-# layers with a split operand take the streaming GEMM kernel (csrc/nn_gemm_stream.hip; batch 4 = 788 token rows) and it pays:
-# optim.amp step 29.71 -> 28.87 ms on the same box.  ZS_TRAIN_PRESPLIT_ALL=0: only the >= 192-tile layers, per layer.
-PRESPLIT_ALL = os.environ.get("ZS_TRAIN_PRESPLIT_ALL", "1") != "0"
-
-
-def _amp_splits_operands():
-    return PRESPLIT_ALL and (FWD_CONV_PRECISION == "f16x3" or BWD_DATA_PRECISION == "f16x3")
-
-
-def _presplit_all(device):
-    """Split every registered packed operand on `device` (call right after they were re-packed)."""
-    lib = _lib.load()
-    recs = [rec for rec in _PACKS.copy().values() if rec.ref() is not None and rec.packed.device == device and
-            not (rec.inline_split and rec.split is not None and rec.split_stamp == rec.stamp)]   # (split by the re-pack itself)
-    if not recs:
-        return
-    sig = tuple((rec.packed.data_ptr(), rec.packed.numel()) for rec in recs)
-    cached = _PRESPLIT_TABLE.get(device)
-    if cached is None or cached[0] != sig:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("the set of packed operands changed inside a stream capture; call "
-                               "zeroshape_amd.nn.autograd.refresh_packs(device) before capturing")
-        splits, src, dst, cps, prefix, tot = [], [], [], [], [0], 0
-        for rec in recs:
-            K16, NPad = rec.dims[5], rec.dims[6]
-            sp = rec.split
-            if sp is None or sp.numel() != rec.packed.numel() or sp.device != device:
-                sp = torch.empty_like(rec.packed)
-            splits.append(sp)
-            src.append(rec.packed.data_ptr()); dst.append(sp.data_ptr()); cps.append(NPad)
-            tot += K16 // 16 * 2 * NPad
-            prefix.append(tot)
-        cached = (sig, torch.tensor(src, dtype=torch.int64).to(device), torch.tensor(dst, dtype=torch.int64).to(device),
-                  torch.tensor(cps, dtype=torch.int32).to(device), torch.tensor(prefix, dtype=torch.int64).to(device),
-                  len(recs), tot, splits)
-        _PRESPLIT_TABLE[device] = cached
-    _, src_d, dst_d, cp_d, pre_d, n, tot, splits = cached
-    with _lib.on(device):
-        _lib.check(lib.zs_conv2d_presplit_weight_multi(_lib.ptr(src_d), _lib.ptr(dst_d), _lib.ptr(cp_d), _lib.ptr(pre_d), n, tot,
-                                                       _lib.current_stream_ptr(device)), "zs_conv2d_presplit_weight_multi")
-    for rec, sp in zip(recs, splits):
-        rec.split, rec.split_stamp = sp, rec.stamp
-# optim.amp: layers large enough for the LDS-DMA GEMM kernel or the 3x3 input-patch kernels (>= 192 tiles of 128 x 128,
-# channels a multiple of 16, no input affine) get their packed operand split into fp16 halves once per optimiser step
-# (zs_conv2d_presplit_weight), which is what those kernels consume; the other layers split on the fly as before.
-PRESPLIT_MIN_TILES = int(os.environ.get("ZS_TRAIN_PRESPLIT_MIN_TILES", "192"))
-
-
-def _rec_of(packed):
-    ref = getattr(packed, "_zs_rec", None)
-    return ref() if ref is not None else None
-
-
-def _split_of(packed):
-    """The operand's current fp16 halves, or None (never split, or split from an older pack)."""
-    rec = _rec_of(packed)
-    if rec is not None and rec.split is not None and rec.split_stamp == rec.stamp and rec.split.numel() == packed.numel():
-        return rec.split
-    return None
-
-
-def _presplit(packed, C, Co, kh, kw, device):
-    lib = _lib.load()
-    split = _split_of(packed)
-    if split is None:
-        rec = _rec_of(packed)
-        split = rec.split if rec is not None and rec.split is not None and rec.split.numel() == packed.numel() \
-            else torch.empty_like(packed)
-        with _lib.on(device):
-            _lib.check(lib.zs_conv2d_presplit_weight(_lib.ptr(packed), _lib.ptr(split), C, Co, kh, kw,
-                                                     _lib.current_stream_ptr(device)), "zs_conv2d_presplit_weight")
-        if rec is not None:                    # an operand without a record (none today) is split on every use
-            rec.split, rec.split_stamp = split, rec.stamp
-    return split
-
-
-def _conv_launch(x, packed, shift, res1, res2, out, kh, kw, stride, pt, pl, flags, in_scale, in_shift, act):
+def _conv_launch(x, rec, shift, res1, res2, out, kh, kw, stride, pt, pl, flags, in_scale, in_shift, act):
     lib = _lib.load()
     B, H, W, C = x.shape
     _, Ho, Wo, Co = out.shape
-    if flags & _CONV_F16X3:
-        split = _split_of(packed) if _amp_splits_operands() else None
-        if split is not None:
-            packed = split                         # split with every other operand right after the re-pack
-            flags |= _CONV_W_PRESPLIT
-        elif not (flags & _CONV_IN_DILATE2) and C % 16 == 0 and in_scale == 1.0 and in_shift == 0.0 and \
-                -(-(B * Ho * Wo) // 128) * -(-Co // 128) >= PRESPLIT_MIN_TILES:
-            packed = _presplit(packed, C, Co, kh, kw, x.device)
-            flags |= _CONV_W_PRESPLIT
+    packed, flags = CACHE.operand(rec, flags, B * Ho * Wo, C, Co, kh, kw, in_scale, in_shift)
     with _lib.on(x.device):
         _lib.check(lib.zs_conv2d_nhwc(_lib.ptr(x), _lib.ptr(packed), None, _lib.ptr(shift), _lib.ptr(res1),
                                       _lib.ptr(res2), _lib.ptr(out), B, H, W, C, Ho, Wo, Co, kh, kw, stride, pt, pl,
@@ -588,45 +163,6 @@ def cut(*tensors):
     return out[0] if len(out) == 1 else tuple(out)
 
 
-# Weight gradients on a side stream (see _Conv.backward).  Off unless the caller of backward() switches it on AND joins
-# afterwards: a gradient tensor handed to autograd is written later, on another stream.
-SIDE_WGRAD = [False]
-_SIDE_STREAMS = {}
-_SIDE_KEEP = []
-
-
-def _side_wgrad_stream(device):
-    st = _SIDE_STREAMS.get(str(device))
-    if st is None:
-        st = _SIDE_STREAMS[str(device)] = torch.cuda.Stream(device=device)
-    return st
-
-
-def join_side_wgrads():
-    """The current stream of every device with weight gradients in flight waits for them; their operands may be freed."""
-    for dev, st in _SIDE_STREAMS.items():
-        torch.cuda.current_stream(torch.device(dev)).wait_stream(st)
-    _SIDE_KEEP.clear()
-
-
-class side_wgrads(object):
-    """with side_wgrads(on): loss.backward()  - weight gradients overlap the data-gradient chain, joined on exit."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.prev = SIDE_WGRAD[0]
-        SIDE_WGRAD[0] = self.on
-        return self
-
-    def __exit__(self, *exc):
-        SIDE_WGRAD[0] = self.prev
-        if self.on:
-            join_side_wgrads()
-        return False
-
-
 def segment_has_work(s):
     """Does segment s have anything to differentiate (a cut tensor it produced that collected a gradient)?"""
     return any(seg == s and leaf.grad is not None for seg, _, leaf in SEGMENTS["cuts"])
@@ -690,13 +226,13 @@ class _Conv(torch.autograd.Function):
         kh, kw = (weight.shape[2], weight.shape[3]) if weight.dim() == 4 else (1, 1)
         cin0 = cfg.get("cin0", 0)
         cin = cfg.get("cin") or weight.shape[1]
-        assert Cx == _ceil4(cin), "input has %d channels, layer expects %d (padded to 4)" % (Cx, cin)
+        assert Cx == ceil4(cin), "input has %d channels, layer expects %d (padded to 4)" % (Cx, cin)
         std_eps = cfg.get("std_eps")
         Ho, pt = _out_size(H, kh, stride, padding)
         Wo, pl = _out_size(W, kw, stride, padding)
         out = torch.empty(B, Ho, Wo, cout, dtype=torch.float32, device=x.device)
-        flags = (_CONV_IN_RELU if cfg.get("in_relu") else 0) | (_CONV_F16X3 if FWD_CONV_PRECISION == "f16x3" else 0)
-        _conv_launch(x, _pack(weight, cin0, cin, False, std_eps), None if bias is None else bias.detach(),
+        flags = (CONV_IN_RELU if cfg.get("in_relu") else 0) | (CONV_F16X3 if SWITCHES.forward == "f16x3" else 0)
+        _conv_launch(x, CACHE.pack(weight, cin0, cin, False, std_eps), None if bias is None else bias.detach(),
                      None if res1 is None else _f32c(res1, "res1"), None if res2 is None else _f32c(res2, "res2"),
                      out, kh, kw, stride, pt, pl, flags, cfg.get("in_scale", 1.0), cfg.get("in_shift", 0.0), act)
         ctx.cfg = dict(cfg, pt=pt, pl=pl, kh=kh, kw=kw, cin0=cin0, cin=cin)
@@ -722,7 +258,7 @@ class _Conv(torch.autograd.Function):
         _, H, W, Cx = x.shape
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         want_b = ctx.has[0] and need_b
-        gp = g if cout % 4 == 0 else _pad_channels(g, _ceil4(cout))
+        gp = g if cout % 4 == 0 else _pad_channels(g, ceil4(cout))
         dw = db = None
         if want_b and not need_w:
             db = column_sum(g.view(-1, cout))
@@ -731,36 +267,26 @@ class _Conv(torch.autograd.Function):
             dw = torch.zeros_like(weight) if sub else torch.empty_like(weight)
             if want_b:          # the bias gradient rides on the weight-gradient kernel (it stages dY anyway)
                 db = torch.empty(cout, dtype=torch.float32, device=x.device)
-            dws = torch.empty_like(weight) if std_eps is not None else None
-            flags = (_CONV_IN_RELU if in_relu else 0) | (_CONV_F16X3 if wgrad_precision() == "f16x3" else 0)
-            # SIDE_WGRAD (the engine's backward passes): nothing in the backward pass waits for a weight gradient, so it goes to a
-            # side stream behind everything enqueued so far and the data-gradient chain continues at once - the weight-gradient
-            # launches fill the tails of the chain's launches (join_side_wgrads() before anyone reads a gradient)
-            side = _side_wgrad_stream(x.device) if SIDE_WGRAD[0] else None
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream(x.device))
-                _SIDE_KEEP.append((x, gp, weight, dw, db, dws))       # alive until the join: the side stream reads / writes them
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                ws = scratch(x.device, "wgrad_side" if side is not None else "wgrad",
-                             _ws_bytes("zs_conv2d_wgrad_workspace_bytes", B, Ho, Wo, Cx, cout, kh, kw))
-                with _lib.on(x.device):
-                    _lib.check(lib.zs_conv2d_wgrad(_lib.ptr(x), _lib.ptr(gp), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), B, H, W, Cx, Ho,
-                                                   Wo, cout, kh, kw, stride, pt, pl, flags, float(in_scale),
-                                                   float(in_shift), cin, cin0, weight.shape[1], 0, _stream(x)),
-                               "zs_conv2d_wgrad")
-                if std_eps is not None:
-                    with _lib.on(x.device):
-                        _lib.check(lib.zs_standardize_weight_bwd(_lib.ptr(weight.detach()), _lib.ptr(dw), _lib.ptr(dws),
-                                                                 weight.shape[0], weight[0].numel(), float(std_eps),
-                                                                 _stream(x)), "zs_standardize_weight_bwd")
+            flags = (CONV_IN_RELU if in_relu else 0) | (CONV_F16X3 if wgrad_precision() == "f16x3" else 0)
+            ws = scratch(x.device, "wgrad", _ws_bytes("zs_conv2d_wgrad_workspace_bytes", B, Ho, Wo, Cx, cout, kh, kw))
+            with _lib.on(x.device):
+                _lib.check(lib.zs_conv2d_wgrad(_lib.ptr(x), _lib.ptr(gp), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), B, H, W, Cx, Ho,
+                                               Wo, cout, kh, kw, stride, pt, pl, flags, float(in_scale),
+                                               float(in_shift), cin, cin0, weight.shape[1], 0, _stream(x)),
+                           "zs_conv2d_wgrad")
             if std_eps is not None:
+                dws = torch.empty_like(weight)
+                with _lib.on(x.device):
+                    _lib.check(lib.zs_standardize_weight_bwd(_lib.ptr(weight.detach()), _lib.ptr(dw), _lib.ptr(dws),
+                                                             weight.shape[0], weight[0].numel(), float(std_eps),
+                                                             _stream(x)), "zs_standardize_weight_bwd")
                 dw = dws
         dx = None
         if need_x:
             assert stride in (1, 2), "data gradient: stride 1 or 2"
             if cin <= 4 and cout % 4 == 0 and kh * kw * cout * 16 <= 160 * 1024:
                 # a network stem: direct gather kernel instead of a GEMM with 3 useful columns
-                w_used = standardize(weight, std_eps) if std_eps is not None else weight.detach()
+                w_used = CACHE.standardize(weight, std_eps) if std_eps is not None else weight.detach()
                 dx = torch.empty(B, H, W, Cx, dtype=torch.float32, device=x.device)
                 with _lib.on(x.device):
                     _lib.check(lib.zs_conv2d_dgrad_small_cin(_lib.ptr(g), _lib.ptr(w_used), _lib.ptr(dx), B, H, W, Cx, Ho, Wo,
@@ -768,9 +294,9 @@ class _Conv(torch.autograd.Function):
                                                              float(in_scale), _stream(x)), "zs_conv2d_dgrad_small_cin")
             else:
                 dx = torch.empty(B, H, W, cin, dtype=torch.float32, device=x.device)
-                flags = (_CONV_IN_DILATE2 if stride == 2 else 0) | (_CONV_F16X3 if BWD_DATA_PRECISION == "f16x3" else 0)
+                flags = (CONV_IN_DILATE2 if stride == 2 else 0) | (CONV_F16X3 if SWITCHES.backward == "f16x3" else 0)
                 fused = dpass is not None and cin == Cx and not in_relu     # the pass-through's gradient: the GEMM's residual
-                _conv_launch(gp, _pack(weight, cin0, cin, True, std_eps), None, dpass if fused else None, None, dx, kh, kw, 1,
+                _conv_launch(gp, CACHE.pack(weight, cin0, cin, True, std_eps), None, dpass if fused else None, None, dx, kh, kw, 1,
                              kh - 1 - pt, kw - 1 - pl, flags, in_scale, 0.0, ACT_NONE)
                 if fused:
                     dpass = None
@@ -897,7 +423,7 @@ class _Attention(torch.autograd.Function):
         out = torch.empty(B, L, C, dtype=torch.float32, device=qkv.device)
         # optim.amp: the split-fp16 forms, like the forward GEMMs around it (batch 4 = 48 (sample, head) pairs: the key-split
         # kernel, 25 -> 9 us per ViT block); the backward pass recomputes the probabilities in fp32 either way
-        split = FWD_CONV_PRECISION == "f16x3" and ATT_FWD_SPLIT
+        split = SWITCHES.forward == "f16x3" and ATT_FWD_SPLIT
         with _lib.on(qkv.device):
             _lib.check((lib.zs_attention_split if split else lib.zs_attention)(
                 _lib.ptr(qkv), _lib.ptr(out), B, L, heads, C // heads, _stream(qkv)),

@@ -13,9 +13,8 @@ class HipModule(nn.Module):
         self._packed_cache = None
 
     def _tensors_key(self):
-        from . import autograd
-        return (autograd.GENERATION[0],) + tuple((t.data_ptr(), t._version)
-                                                 for t in list(self.parameters()) + list(self.buffers()))
+        from .operands import weights_stamp
+        return weights_stamp(list(self.parameters()) + list(self.buffers()))
 
     def packed(self, device):
         key = (str(device),) + self._tensors_key()
