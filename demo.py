@@ -3,6 +3,7 @@
 
     python demo.py --yaml=options/shape.yaml --task=shape --datadir=examples --eval.vox_res=128 --ckpt=weights/shape.ckpt
     python demo.py --yaml=options/depth.yaml --task=depth --datadir=examples --ckpt=weights/depth.ckpt
+    python demo.py --yaml=options/shape.yaml --task=shape --datadir=examples --ckpt=weights/shape.ckpt --viz
 
 <datadir>/images/*.png|jpg with <datadir>/masks/<same name>.png -> <datadir>/preds/: the cropped
 input and mask, and for the shape task the reconstructed mesh (marching cubes at 0.5 of the
@@ -10,6 +11,12 @@ input and mask, and for the shape task the reconstructed mesh (marching cubes at
 reference (demo.py:27-70: mask binarised at 127, square crop 1.2x the mask's bounding box, resize to
 image_size, white background, intrinsics f = 1.3875 * W).  Everything after image loading runs on
 the GPU through the HIP library.
+
+--viz (opt-in, shape task) adds the two animations the reference's demo leaves: <name>_attn.gif, the
+attention of the decoder's points over the input image as the query sweeps the grid (the slice-loop
+path with vis_attn=True), and <name>_mesh_viz.gif, 180 frames of the mesh on the reference's camera
+path from the library's rasteriser (geometry and shading formula pinned by tests; pyrender's PBR
+pixels are not reproduced).  Without --viz the files written are exactly the four above.
 """
 import importlib
 import os
@@ -75,11 +82,13 @@ def prepare_data(opt):
 
 
 @torch.no_grad()
-def marching_cubes(opt, var, impl_network):
+def marching_cubes(opt, var, impl_network, vis_attn=False):
     points_3D = get_dense_3D_grid(opt, var)                                # [B,G,G,G,3] (tagged: fused grid query)
-    level_vox, _ = compute_level_grid(opt, impl_network, var.latent_depth, var.latent_semantic, points_3D,
-                                      var.rgb_input_map, False)
+    level_vox, attn_vis = compute_level_grid(opt, impl_network, var.latent_depth, var.latent_semantic, points_3D,
+                                             var.rgb_input_map, vis_attn)
     var.eval_vox = level_vox
+    if attn_vis:
+        var.attn_vis = attn_vis
     var.mesh_pred = convert_to_explicit(opt, list(level_vox), isoval=0.5, to_pointcloud=False)
     return var
 
@@ -104,6 +113,7 @@ def main():
         shutil.rmtree(save_folder)
     os.makedirs(save_folder)
     opt.output_path = opt.datadir
+    viz = bool(opt.get("viz", False))
     for var, name in zip(data_list, name_list):
         with torch.no_grad():
             var = graph.forward(opt, var, training=False, get_loss=False)
@@ -111,8 +121,11 @@ def main():
             util_vis.dump_images(opt, [name], "mask_input", var.mask_input_map, folder='preds')
             util_vis.dump_depths(opt, [name], "depth_est", var.depth_pred, var.mask_input_map, rescale=True, folder='preds')
             if opt.task == 'shape':
-                var = marching_cubes(opt, var, graph.impl_network)
+                var = marching_cubes(opt, var, graph.impl_network, vis_attn=viz)
                 util_vis.dump_meshes(opt, [name], "mesh", var.mesh_pred, folder='preds')
+                if viz:
+                    util_vis.dump_attentions(opt, [name], "attn", var.attn_vis, folder='preds')
+                    util_vis.dump_meshes_viz(opt, [name], "mesh_viz", var.mesh_pred, save_frames=False, folder='preds')
         print("{}: done".format(name))
 
 

@@ -24,6 +24,8 @@
  *   zs_fscore            <- compute_fscore, utils/eval_3D.py:215-231
  *   zs_mc_*, zs_mesh_*   <- convert_to_explicit, utils/eval_3D.py:233-263 (PyMCubes
  *                           marching_cubes + trimesh.sample on the host)
+ *   zs_mesh_stats, zs_render_frames <- dump_meshes_viz, scale_to_unit_cube, visualize_mesh,
+ *                           utils/util_vis.py:112-127, 310-405 (trimesh + pyrender on OpenGL)
  *   zs_seen_surface, zs_unproj_depth, zs_valid_norm_fac, zs_masked_resample,
  *   zs_intr_param2mtx    <- the seen-surface geometry of Graph.forward,
  *                           model/compute_graph/graph_shape.py:89-113,131-144, with
@@ -48,7 +50,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 38
+#define ZS_ABI_VERSION 39
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -335,6 +337,49 @@ int zs_mc_emit(const float *vol, int G, float iso, const int8_t *tri_table, int 
                float *tris, int n_tris, void *stream);
 int zs_mesh_sample(const float *tris, int n_tris, int n_samples, uint64_t seed, double *cum_area,
                    float *points, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Mesh turntable renderer (replaces dump_meshes_viz / scale_to_unit_cube / visualize_mesh,
+ * utils/util_vis.py:112-127, 310-405: trimesh + pyrender on OpenGL).  A z-buffer rasteriser
+ * over the triangle soup tris[n_tris][3][3] that zs_mc_emit writes; all frames of a camera
+ * path in one call.  pyrender's PBR pixels are not reproduced (parity unpinned: no GL here);
+ * the geometry and the shading formula below are what the tests pin.
+ * ------------------------------------------------------------------------- */
+
+/* Bounding box and signed volume of the soup: out[7] (device) = min xyz, max xyz,
+ * sum(v0 . (v1 x v2)) / 6 (accumulated in fp64).  Per-block partials in `scratch`
+ * (zs_mesh_stats_scratch_bytes(n_tris) bytes, 8-byte aligned) are summed by one block in a
+ * fixed order: no float atomics, bit-reproducible.  n_tris == 0 writes seven zeros (tris and
+ * scratch may then be NULL). */
+size_t zs_mesh_stats_scratch_bytes(int n_tris);
+int zs_mesh_stats(const float *tris, int n_tris, float *out, void *scratch, void *stream);
+
+/* Renders `frames` views of the soup into rgb[frames][H][W][3] uint8 and, when not NULL,
+ * depth[frames][H][W] fp32 (camera-space distance along the view axis, +inf where nothing is
+ * hit) and tri[frames][H][W] int32 (index of the visible triangle, -1 where nothing is hit).
+ *   xform [host][8]  : flip xyz, centre xyz, scale, winding - every vertex becomes
+ *                      (flip * v - centre) * scale on the fly (never written back), and v1 / v2
+ *                      of every triangle are exchanged when winding < 0
+ *   cams [frames][12]: camera position (3) + camera-to-world rotation (3x3, row-major); the
+ *                      camera looks along -z of its own frame, +y is up (pyrender's convention)
+ *   yfov, znear      : vertical field of view in radians (aspect = W / H), near plane
+ *   base_rgb [host][3]: material colour; c = base * (0.3 + 0.7 |n . l|) per face, n = unit face
+ *                      normal, l = unit vector from the hit point to the camera; stored
+ *                      floor(255 c + 0.5); the background is white
+ *   zbuffer          : zs_render_zbuffer_bytes(frames, H, W) bytes of scratch, 8-byte aligned
+ * With zv = -z_c: x_pix = (x_c / (zv tan(yfov/2) aspect) + 1) W/2 and
+ * y_pix = (1 - y_c / (zv tan(yfov/2))) H/2; the centre of pixel (row i, col j) is
+ * (j + 0.5, i + 0.5); a pixel is covered when its three barycentrics are >= 0 (inclusive on
+ * every edge).  Depth is perspective correct; the nearest depth wins and at exactly equal
+ * (fp32) depth the smaller triangle index: one 64-bit atomic maximum per covered pixel, so the
+ * result does not depend on the order of execution.  Zero-area triangles and triangles with a
+ * vertex at zv <= znear are skipped whole.  n_tris == 0 gives white frames (tris may be NULL);
+ * frames == 0 does nothing.  Limits: frames <= 65535, H and W <= 16384 (the size function
+ * returns 0 beyond them). */
+size_t zs_render_zbuffer_bytes(int frames, int H, int W);
+int zs_render_frames(const float *tris, int n_tris, const float *xform, const float *cams,
+                     int frames, int H, int W, float yfov, float znear, const float *base_rgb,
+                     uint8_t *rgb, float *depth, int *tri, void *zbuffer, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Seen-surface geometry front-end (model/compute_graph/graph_shape.py:131-144).

@@ -97,6 +97,11 @@ SIGNATURES = {
     "zs_mc_emit": (_c_int, [_c_void_p, _c_int, ctypes.c_float, _c_void_p, _c_int, _c_void_p, _c_void_p,
                             ctypes.c_float, ctypes.c_float, _c_void_p, _c_int, _c_void_p]),
     "zs_mesh_sample": (_c_int, [_c_void_p, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_stats_scratch_bytes": (_c_size_t, [_c_int]),
+    "zs_mesh_stats": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_render_zbuffer_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+    "zs_render_frames": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_float), _c_void_p, _c_int, _c_int, _c_int, _c_float,
+                                  _c_float, ctypes.POINTER(_c_float), _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_intr_param2mtx": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "zs_unproj_depth": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "zs_valid_norm_fac": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
@@ -206,7 +211,7 @@ SIGNATURES = {
     "zs_readout_concat_bwd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
 }
 
-ABI_VERSION = 38
+ABI_VERSION = 39
 _lib = None
 
 

@@ -35,6 +35,8 @@ EXTRA = {
     "sdf_decoder_split.hip": ["-fno-slp-vectorize", "-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form"],
     # vertices / sampled points reproducible op for op by oracle/mc_ref.py
     "marching_cubes.hip": ["-ffp-contract=off"],
+    # coverage and depth reproducible op for op by the float64 rasteriser in tests/test_gpu_render.py
+    "render.hip": ["-ffp-contract=off"],
 }
 
 

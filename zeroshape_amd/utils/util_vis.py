@@ -1,6 +1,9 @@
-"""Minimal result dumps for demo.py (the reference's utils/util_vis.py renders with pyrender / cv2 /
-trimesh, which this image does not have and the hot path does not need): input image and mask as
-PNG, depth maps as 16-bit PNG, meshes as Wavefront OBJ with welded vertices, attention maps as .npy.
+"""Result dumps for demo.py.  The reference's utils/util_vis.py renders with pyrender / cv2 / trimesh, which this image
+does not have (and pyrender needs OpenGL, which a headless compute node does not have either).  Here: input image and
+mask as PNG, depth maps as 16-bit PNG, meshes as Wavefront OBJ with welded vertices, attention maps as .npy or - given the
+frames of ``compute_level_grid(vis_attn=True)`` - as GIF, and the rotating mesh render of ``dump_meshes_viz`` /
+``visualize_mesh`` from the library's own rasteriser (csrc/render.hip: all frames in one call, one copy back to the host).
+Its geometry and shading formula are pinned by tests; pyrender's PBR pixels are not reproduced (parity unpinned).
 File names follow the reference's `<output_path>/<folder>/<idx>_<name>.<ext>` pattern."""
 import os
 
@@ -11,6 +14,21 @@ def _path(opt, folder, idx, name, ext):
     d = os.path.join(opt.output_path, folder)
     os.makedirs(d, exist_ok=True)
     return os.path.join(d, "{}_{}.{}".format(idx, name, ext))
+
+
+def _write_gif(path, images, duration):
+    """PIL images -> looping GIF at ``duration`` ms a frame, one GIF frame per image, each whole and with its own colour
+    table.  ``Image.save(save_all=True)`` folds an image that equals the one before it into that one's duration; the
+    turntable's camera path repeats a pose where two of its segments meet, so it would write 177 frames for 180."""
+    from PIL import GifImagePlugin, Image
+    frames = [im if im.mode == "P" else im.convert("P", palette=Image.Palette.ADAPTIVE) for im in images]
+    with open(path, "wb") as fp:
+        for block in GifImagePlugin.getheader(frames[0], info=dict(loop=0, duration=duration))[0]:
+            fp.write(block)
+        for frame in frames:
+            for block in GifImagePlugin.getdata(frame, duration=duration, include_color_table=True):
+                fp.write(block)
+        fp.write(b";")
 
 
 def dump_images(opt, idx, name, images, masks=None, from_range=(0, 1), folder="dump", **_):
@@ -57,9 +75,177 @@ def dump_meshes(opt, idx, name, meshes, folder="dump", **_):
 
 
 def dump_attentions(opt, idx, name, attn, folder="dump", **_):
-    """The reference colour-maps attention over the image with cv2; here the raw maps are stored."""
+    """Per-sample frame lists (what ``compute_level_grid(vis_attn=True)`` returns: [H,W,3] arrays in [0,1]) -> GIF at 50 ms a
+    frame like the reference (utils/util_vis.py:93-97).  A tensor (or a list of tensors) of raw maps -> .npy per sample: the
+    reference colour-maps those over the image with cv2, here they are stored as they are."""
     if attn is None:
         return
     for b, i in enumerate(idx):
-        a = attn[b] if not isinstance(attn, (list, tuple)) else attn[b]
+        a = attn[b]
+        if isinstance(a, (list, tuple)):
+            from PIL import Image
+            frames = [Image.fromarray((np.asarray(f) * 255).astype(np.uint8)).convert("RGB") for f in a]
+            if frames:
+                _write_gif(_path(opt, folder, i, name, "gif"), frames, 50)
+            continue
         np.save(_path(opt, folder, i, name, "npy"), np.asarray(a.detach().cpu() if hasattr(a, "detach") else a))
+
+
+# ---- mesh turntable (utils/util_vis.py:112-127, 295-405) ----
+
+YFOV = np.pi / 3.0                  # pyrender.PerspectiveCamera(yfov=np.pi / 3.0, aspectRatio=1.0)
+ZNEAR = 0.05                        # pyrender's default near plane
+BASE_RGB = (0.5, 0.5, 0.8)          # baseColorFactor of the reference's material
+
+
+def look_at(camera_position, camera_target, up_vector):
+    """utils/util_vis.py:295-308: the camera's axes as the columns of the upper 3x3 (right, up, backward - the camera looks
+    along -z), and the translation of the inverse in the last row."""
+    back = camera_position - camera_target
+    back = back / np.linalg.norm(back)
+    right = np.cross(up_vector, back)
+    right = right / np.linalg.norm(right)
+    up = np.cross(back, right)
+    return np.array([
+        [right[0], up[0], back[0], 0.0],
+        [right[1], up[1], back[1], 0.0],
+        [right[2], up[2], back[2], 0.0],
+        [-np.dot(right, camera_position), -np.dot(up, camera_position), np.dot(back, camera_position), 1.0]])
+
+
+def get_positions_and_rotations(n_frames=180, r=1.5):
+    """utils/util_vis.py:320-346: the four-segment camera path around the origin at radius ``r`` in the horizontal plane - a
+    full circle descending from height 1 to -1, half a circle at -1, a full circle climbing back, half a circle at 1."""
+    n_full, n_half = n_frames // 3, n_frames // 6
+    ring = lambda theta, elev: np.array([r * np.cos(theta), elev, r * np.sin(theta)])      # noqa: E731
+    pos = [ring(t, e) for t, e in zip(np.linspace(0.5 * np.pi, 2.5 * np.pi, n_full), np.linspace(1, -1, n_full))]
+    pos += [ring(t, -1) for t in np.linspace(2.5 * np.pi, 3.5 * np.pi, n_half)]
+    pos += [ring(t, e) for t, e in zip(np.linspace(3.5 * np.pi, 5.5 * np.pi, n_full), np.linspace(-1, 1, n_full))]
+    pos += [ring(t, 1) for t in np.linspace(3.5 * np.pi, 4.5 * np.pi, n_half)]
+    target, up = np.array([0.0, 0.0, 0.0]), np.array([0.0, 1.0, 0.0])
+    return pos, [look_at(x, target, up) for x in pos]
+
+
+IDENTITY_XFORM = np.array([1, 1, 1, 0, 0, 0, 1, 1], np.float32)
+
+
+def pretransform_params(stats):
+    """``stats`` = (bounding-box min xyz, max xyz, signed volume) of a triangle soup, what zs_mesh_stats writes -> the eight
+    numbers zs_render_frames applies on the fly, (flip xyz, centre xyz, scale, winding): dump_meshes_viz's two 180-degree
+    rotations about z and then y, (x, y, z) -> (x, -y, -z); scale_to_unit_cube's centring on the bounding box of the rotated
+    mesh and scaling by 1 / its largest extent; trimesh.repair.fix_inversion's v1 <-> v2 exchange when the volume is negative
+    (the rotations are proper, they leave its sign alone)."""
+    stats = np.asarray(stats, np.float64)
+    flip = np.array([1.0, -1.0, -1.0])
+    a, b = stats[0:3] * flip, stats[3:6] * flip
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    extent = float(np.max(hi - lo))
+    if not extent > 0:
+        raise ValueError("mesh has no extent")
+    winding = -1.0 if stats[6] < 0 else 1.0
+    return np.concatenate([flip, (lo + hi) / 2, [1.0 / extent, winding]]).astype(np.float32)
+
+
+def camera_rows(positions, rotations):
+    """[F][12] fp32 rows for zs_render_frames: position, then the camera-to-world rotation (the upper 3x3 of what look_at
+    returns, as visualize_mesh puts it into the pose, utils/util_vis.py:384-386)."""
+    pos = np.asarray(positions, np.float64).reshape(-1, 3)
+    rot = np.asarray(rotations, np.float64)[:, :3, :3].reshape(-1, 9)
+    assert len(pos) == len(rot)
+    return np.ascontiguousarray(np.concatenate([pos, rot], axis=1), np.float32)
+
+
+def mesh_stats(triangles):
+    """zs_mesh_stats of a GPU soup [n,3,3] fp32 -> 7 floats on the host (a 28-byte copy)."""
+    import torch
+    from .. import _lib
+    lib = _lib.load()
+    n = triangles.shape[0]
+    out = torch.empty(7, dtype=torch.float32, device=triangles.device)
+    scratch = torch.empty(max(lib.zs_mesh_stats_scratch_bytes(n) // 8, 1), dtype=torch.float64, device=triangles.device)
+    with _lib.on(triangles.device):
+        _lib.check(lib.zs_mesh_stats(_lib.ptr(triangles), n, _lib.ptr(out), _lib.ptr(scratch),
+                                     _lib.current_stream_ptr(triangles.device)), "zs_mesh_stats")
+    return out.cpu().numpy()
+
+
+def render_into(triangles, xform, cams, H, W, rgb, depth=None, tri=None, zbuffer=None):
+    """zs_render_frames into caller-owned GPU buffers: ``triangles`` [n,3,3] fp32, ``xform`` 8 host floats, ``cams`` [F,12]
+    fp32 on the device, ``rgb`` uint8 [F,H,W,3], ``depth`` fp32 / ``tri`` int32 [F,H,W] or None."""
+    import ctypes
+    import torch
+    from .. import _lib
+    lib = _lib.load()
+    dev = triangles.device
+    F = cams.shape[0]
+    assert triangles.is_cuda and triangles.dtype == torch.float32 and triangles.is_contiguous() and triangles.shape[1:] == (3, 3)
+    assert cams.device == dev and cams.dtype == torch.float32 and cams.is_contiguous() and cams.shape == (F, 12)
+    assert rgb.device == dev and rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.shape == (F, H, W, 3)
+    assert depth is None or (depth.device == dev and depth.dtype == torch.float32 and depth.is_contiguous()
+                             and depth.shape == (F, H, W))
+    assert tri is None or (tri.device == dev and tri.dtype == torch.int32 and tri.is_contiguous() and tri.shape == (F, H, W))
+    if zbuffer is None:
+        zbuffer = torch.empty(max(lib.zs_render_zbuffer_bytes(F, H, W) // 8, 1), dtype=torch.int64, device=dev)
+    assert zbuffer.device == dev and zbuffer.numel() * zbuffer.element_size() >= lib.zs_render_zbuffer_bytes(F, H, W)
+    xf = (ctypes.c_float * 8)(*[float(v) for v in xform])
+    base = (ctypes.c_float * 3)(*BASE_RGB)
+    with _lib.on(dev):
+        _lib.check(lib.zs_render_frames(_lib.ptr(triangles), triangles.shape[0], xf, _lib.ptr(cams), F, H, W, float(YFOV),
+                                        float(ZNEAR), base, _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(tri), _lib.ptr(zbuffer),
+                                        _lib.current_stream_ptr(dev)), "zs_render_frames")
+
+
+def render_mesh_frames(triangles, positions, rotations, resolution, return_depth=False, return_tri=False,
+                       pose_normalize=False):
+    """All frames of a camera path in one call.  ``triangles``: GPU tensor [n,3,3] fp32; ``positions`` / ``rotations``: what
+    get_positions_and_rotations returns; ``resolution`` = (width, height) like pyrender.OffscreenRenderer's.  Returns the
+    GPU tensor rgb uint8 [F,H,W,3], or the tuple (rgb[, depth fp32 [F,H,W]][, tri int32 [F,H,W]]).  With ``pose_normalize`` the
+    mesh is turned, centred and scaled on the fly as dump_meshes_viz does (pretransform_params of its zs_mesh_stats)."""
+    import torch
+    W, H = int(resolution[0]), int(resolution[1])
+    dev = triangles.device
+    triangles = triangles.detach().contiguous()
+    cams = torch.from_numpy(camera_rows(positions, rotations)).to(dev)
+    F = cams.shape[0]
+    xform = pretransform_params(mesh_stats(triangles)) if pose_normalize and triangles.shape[0] else IDENTITY_XFORM
+    rgb = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    depth = torch.empty(F, H, W, dtype=torch.float32, device=dev) if return_depth else None
+    tri = torch.empty(F, H, W, dtype=torch.int32, device=dev) if return_tri else None
+    render_into(triangles, xform, cams, H, W, rgb, depth, tri)
+    out = (rgb,) + ((depth,) if return_depth else ()) + ((tri,) if return_tri else ())
+    return out[0] if len(out) == 1 else out
+
+
+def visualize_mesh(mesh, output_path, resolution=(200, 200), write_gif=True, write_frames=True, time_per_frame=80,
+                   n_frames=180, pose_normalize=False, device="cuda"):
+    """utils/util_vis.py:348-405.  ``mesh``: an eval_3D.SimpleMesh, or a triangle soup [n,3,3] as tensor or array (a host
+    soup is uploaded once).  Renders the ``n_frames`` of get_positions_and_rotations in one call, copies them to the host
+    once, writes ``<output_path>.gif`` (80 ms a frame, endless loop - the reference ignores ``time_per_frame`` too) and, with
+    ``write_frames``, ``<output_path>/0000.jpg ...``.  Returns the frames, uint8 [n_frames,H,W,3]."""
+    import torch
+    from PIL import Image
+    soup = getattr(mesh, "triangles", mesh)
+    if not isinstance(soup, torch.Tensor):
+        soup = torch.from_numpy(np.ascontiguousarray(soup, np.float32)).to(device)
+    soup = soup.to(torch.float32).reshape(-1, 3, 3)
+    positions, rotations = get_positions_and_rotations(n_frames=n_frames)
+    frames = render_mesh_frames(soup, positions, rotations, resolution, pose_normalize=pose_normalize).cpu().numpy()
+    images = [Image.fromarray(f, mode="RGB") for f in frames]
+    if write_gif:
+        _write_gif("{}.gif".format(output_path), images, 80)
+    if write_frames:
+        os.makedirs(output_path, exist_ok=True)
+        for i, img in enumerate(images):
+            img.save(os.path.join(output_path, "{:04d}.jpg".format(i)))
+    return frames
+
+
+def dump_meshes_viz(opt, idx, name, meshes, save_frames=True, folder="dump"):
+    """utils/util_vis.py:112-127: ``<idx>_<name>.gif`` (and ``<idx>_<name>/0000.jpg ...`` with ``save_frames``) of every mesh,
+    turned, centred and scaled to the unit cube.  An empty mesh writes nothing and raises nothing (the reference's
+    ``try/except`` around scale_to_unit_cube)."""
+    for i, mesh in zip(idx, meshes):
+        if len(getattr(mesh, "triangles", mesh)) == 0:
+            continue
+        fname = _path(opt, folder, i, name, "gif")[:-4]
+        visualize_mesh(mesh, fname, write_frames=save_frames, pose_normalize=True, device=getattr(opt, "device", "cuda"))
