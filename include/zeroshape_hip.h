@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 39
+#define ZS_ABI_VERSION 40
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -169,6 +169,41 @@ int zs_sdf_query_grid(const void *programs, size_t program_stride_bytes, int bat
                       const float *axis, int G, int slice_begin, int slice_end,
                       int apply_sigmoid, float *out, const int *tile_mask, void *workspace,
                       void *stream);
+
+/* z-mean attention of grid columns (the heat-map GIF of compute_level_grid(vis_attn=True), utils/eval_3D.py:47-80, which
+ * averages the attention map over z and draws only the columns at multiples of 8): for every column (ix, iy) of
+ * columns[n_cols][2] (int32, device; 0 <= ix, iy < G)
+ *   zmean[batch][n_cols][197] = mean over iz < G of the attn row zs_sdf_query_points gives for (axis[ix], axis[iy], axis[iz])
+ * on EXACT fp32 programs, without that [points][197] tensor: per chunk of columns the entry writes the points (the bits
+ * zs_sdf_query_grid reads from `axis`), runs the attention variant of the exact kernel on them (logits discarded) and
+ * reduces its raw probability tiles straight to the column means - fixed summation order, no atomics, bit-identical
+ * from run to run and for every chunking.  A column is padded to whole 32-point wave tiles.
+ *   workspace : zs_sdf_workspace_bytes(), as for the other queries
+ *   scratch   : scratch_bytes >= zs_sdf_grid_attn_zmean_scratch_bytes(batch, n_cols, G, cap_bytes), 16-byte aligned; the
+ *               entry uses scratch_bytes as its cap
+ * cap_bytes (0 = 256 MiB) bounds the scratch whatever batch, n_cols and G are: the columns are split into chunks of
+ * *cols_per_chunk columns of *imgs_per_chunk images (zs_sdf_grid_attn_zmean_chunk; every image, or - when one column of
+ * every image exceeds the cap - one column of as many images as fit), enqueued in stream order on the same scratch.  A cap
+ * below one column of one image (ceil(G / 32) wave tiles rounded up to a 128-point tile, ~1.9 MiB each) is an error:
+ * _scratch_bytes returns 0, the others 0 with a message.  batch == 0 or n_cols == 0: 1, nothing launched. */
+size_t zs_sdf_grid_attn_zmean_scratch_bytes(int batch, int n_cols, int G, size_t cap_bytes);
+int zs_sdf_grid_attn_zmean_chunk(int batch, int n_cols, int G, size_t cap_bytes, int *imgs_per_chunk /* [host] */,
+                                 int *cols_per_chunk /* [host] */);
+int zs_sdf_grid_attn_zmean(const void *programs, size_t program_stride_bytes, int batch,
+                           const float *axis, int G, const int *columns, int n_cols, float *zmean,
+                           void *workspace, void *scratch, size_t scratch_bytes, void *stream);
+
+/* Heat-map frames of the attention GIF (utils/eval_3D.py:62-79 + show_att_on_image, utils/util_vis.py:267-293) composed on
+ * the device, one workgroup per frame:
+ *   a[R][R]  = zmean[b][frame_col[f]][0] + zmean[b][frame_col[f]][1 + ..]          (zmean: [batch][n_cols][1 + R*R])
+ *   v[H][W]  = bilinear upsample of a, align_corners = false, fp32 (scale = (float)R / H, src = scale (d + 0.5) - 0.5
+ *              clamped at 0, i1 = i0 + (i0 < R - 1), v = l0h (l0w a00 + l1w a01) + l1h (l0w a10 + l1w a11))
+ *   level    = (uint8)(255 (v / max v));  heat = lut[level] / 255;  merged = heat + image;  frame = merged / max merged
+ * images: [batch][3][H][W] fp32 in [0, 1]; lut: [256][3] uint8 (RGB); frames: [batch][n_frames][H][W][3] fp32.  The two
+ * maxima are exact in any order, so frames are bit-reproducible.  1 <= R <= 64; frame_col entries outside [0, n_cols) are
+ * clamped. */
+int zs_attn_frames(const float *zmean, int batch, int n_cols, const int *frame_col, int n_frames,
+                   const float *images, int H, int W, const uint8_t *lut, int R, float *frames, void *stream);
 
 /* Split-fp16 ("f16x3") decoder: the same network with every contraction on the 16-bit matrix
  * pipe, both operands split into two fp16 halves (A B ~= Ah Bh + Ah Bl + Al Bh, fp32

@@ -50,6 +50,13 @@ SIGNATURES = {
                                      _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_sdf_query_grid": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int, _c_int,
                                    _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_sdf_grid_attn_zmean_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_size_t]),
+    "zs_sdf_grid_attn_zmean_chunk": (_c_int, [_c_int, _c_int, _c_int, _c_size_t, ctypes.POINTER(_c_int),
+                                              ctypes.POINTER(_c_int)]),
+    "zs_sdf_grid_attn_zmean": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
+                                        _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "zs_attn_frames": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_int,
+                                _c_void_p, _c_void_p]),
     "zs_sdf_split_programs": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "zs_sdf_query_points_split": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int,
                                            _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
@@ -211,7 +218,7 @@ SIGNATURES = {
     "zs_readout_concat_bwd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
 }
 
-ABI_VERSION = 39
+ABI_VERSION = 40
 _lib = None
 
 

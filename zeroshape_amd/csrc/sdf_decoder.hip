@@ -757,7 +757,198 @@ int decode_grid_size(int batch, int m) {
     return (int)(tiles < MAX_WGS ? tiles : MAX_WGS);
 }
 
+// ---- z-mean attention of grid columns (the demo's heat-map GIF, utils/eval_3D.py:47-80) ---------- //
+// A column (ix, iy) of the G^3 grid is its G points along z, padded to `zt` = ceil(G / 32) wave tiles so that
+// a wave tile belongs to one column (iz clamped to G - 1: the padding recomputes the last point and is never
+// summed).  The points of a chunk of columns, in the layout zs_sdf_query_points reads: [img][col][zt * 32][3].
+__global__ __launch_bounds__(256) void column_points_kernel(const float *__restrict__ axis, int G,
+                                                            const int *__restrict__ columns, int cols, int zt,
+                                                            int imgs, float *__restrict__ points) {
+    const int m = cols * zt * PTS_PER_WAVE;
+    const long long total = (long long)imgs * m;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int p = (int)(e % m);
+        const int c = p / (zt * PTS_PER_WAVE);
+        const int z = p - c * (zt * PTS_PER_WAVE);
+        int ix = columns[2 * c], iy = columns[2 * c + 1];
+        ix = ix < 0 ? 0 : ix < G ? ix : G - 1;  // (the Python surface rejects such columns; never read past axis)
+        iy = iy < 0 ? 0 : iy < G ? iy : G - 1;
+        const int iz = z < G ? z : G - 1;
+        points[e * 3 + 0] = axis[ix];
+        points[e * 3 + 1] = axis[iy];
+        points[e * 3 + 2] = axis[iz];
+    }
+}
+
+// zmean[img][col][l] = 1/G sum_iz 1/16 sum_(block, head) softmax probability of latent l, straight from the raw
+// dumps of sdf_decode_kernel<false, true> - no per-point rows are written.  One workgroup per (img, col, latent
+// tile): wave w takes (block, head) pairs 4w .. 4w + 3 and walks the column's wave tiles in z order; every load
+// is the lane-contiguous 16 bytes (P tiles) or 4 bytes (statistics) per lane the decoder stored, so a lane
+// accumulates the 16 latent rows it owns (row = c + 8 j + 4 hi of component c of float4 j) for its point slot.
+// Then, through LDS and in a fixed order: 16 terms per thread, 8 threads per latent row combined by xor
+// shuffles.  No atomics; bit-identical from run to run and for any split of the columns into chunks.
+__global__ __launch_bounds__(256) void attn_zmean_kernel(const f32x4 *__restrict__ raw, float *__restrict__ zmean,
+                                                         int cols, int n_cols, int tiles_per_img, int zt, int G) {
+    __shared__ float part[WAVES * 16 * 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lt = blockIdx.x % LT;
+    const int ic = blockIdx.x / LT;
+    const int col = ic % cols, img = ic / cols;
+    const f32x4 *w = raw + ((size_t)img * tiles_per_img * WAVES + (size_t)col * zt) * ATTN_WT_F4;
+    float acc[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.f;
+    for (int k = 0; k < zt; k++, w += ATTN_WT_F4) {
+        const float *st = reinterpret_cast<const float *>(w + ATTN_P_F4);
+        const bool live = k * PTS_PER_WAVE + (lane & 31) < G;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int bh = wv * 4 + b;
+            const float *sb = st + bh * 9 * 64 + lane;
+            const float wgt = live ? __builtin_amdgcn_exp2f(sb[lt * 64] - sb[7 * 64]) * sb[8 * 64] : 0.f;
+            const f32x4 *pt = w + ((bh * LT + lt) * 4) * 64 + lane;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const f32x4 pv = pt[j * 64];
+                acc[4 * j + 0] = fmaf(pv.x, wgt, acc[4 * j + 0]);
+                acc[4 * j + 1] = fmaf(pv.y, wgt, acc[4 * j + 1]);
+                acc[4 * j + 2] = fmaf(pv.z, wgt, acc[4 * j + 2]);
+                acc[4 * j + 3] = fmaf(pv.w, wgt, acc[4 * j + 3]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r++) part[(wv * 16 + r) * 64 + lane] = acc[r];
+    __syncthreads();
+    // thread -> (latent row of the tile, one of 8 runs of 16 terms): run = (wave, half of the 32 point slots)
+    const int row = threadIdx.x >> 3, run = threadIdx.x & 7;
+    const int r = (row & 3) + 4 * (row >> 3), hi = (row >> 2) & 1;
+    const float *src = part + ((run >> 1) * 16 + r) * 64 + hi * 32 + (run & 1) * 16;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; i++) s += src[i];
+    s += __shfl_xor(s, 1);
+    s += __shfl_xor(s, 2);
+    s += __shfl_xor(s, 4);
+    const int l = lt * 32 + row;
+    if (run == 0 && l < L)
+        zmean[((size_t)img * n_cols + col) * L + l] = s * (1.0f / (BLOCKS * HEADS)) / (float)G;
+}
+
+constexpr size_t ZMEAN_DEFAULT_CAP = (size_t)256 << 20;
+constexpr size_t ZMEAN_MAX_CAP = (size_t)1 << 40;      // keeps every tile / point count of a chunk inside an int
+
+struct ZmeanPlan {
+    int zt;        // wave tiles per column
+    int imgs;      // images per chunk
+    int cols;      // columns per chunk
+    size_t bytes;  // scratch of one chunk
+};
+
+// scratch of one chunk: the raw tiles of every 128-point tile the decoder launches, then points (xyz) and logits
+size_t zmean_chunk_bytes(int imgs, int cols, int zt) {
+    const size_t m = (size_t)cols * zt * PTS_PER_WAVE;
+    const size_t tiles = (m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK;
+    return (size_t)imgs * (tiles * WAVES * ATTN_WT_F4 * sizeof(f32x4) + m * 4 * sizeof(float));
+}
+
+// Every image with as many columns as fit under the cap; when one column of every image does not fit, one
+// column of as many images as do.  Planning again with cap = plan.bytes gives the same plan.
+bool zmean_plan(const char *who, int batch, int n_cols, int G, size_t cap, ZmeanPlan &p) {
+    if (batch < 0 || n_cols < 0 || G <= 0) {
+        zs::set_err("%s: bad size (batch=%d n_cols=%d G=%d)", who, batch, n_cols, G);
+        return false;
+    }
+    if (cap == 0) cap = ZMEAN_DEFAULT_CAP;
+    if (cap > ZMEAN_MAX_CAP) cap = ZMEAN_MAX_CAP;
+    p.zt = (G + PTS_PER_WAVE - 1) / PTS_PER_WAVE;
+    p.imgs = p.cols = 0;
+    p.bytes = 0;
+    if (batch == 0 || n_cols == 0) return true;
+    const size_t one = zmean_chunk_bytes(1, 1, p.zt);
+    if (one > cap) {
+        zs::set_err("%s: a scratch cap of %zu bytes is below one column of one image (%zu bytes at G=%d)", who, cap,
+                    one, G);
+        return false;
+    }
+    if ((size_t)batch * one > cap) {
+        p.imgs = (int)(cap / one);
+        p.cols = 1;
+    } else {
+        p.imgs = batch;
+        int lo = 1, hi = n_cols;      // largest column count that fits: the bytes grow strictly with it
+        while (lo < hi) {
+            const int mid = lo + (hi - lo + 1) / 2;
+            if (zmean_chunk_bytes(batch, mid, p.zt) <= cap) lo = mid; else hi = mid - 1;
+        }
+        p.cols = lo;
+    }
+    p.bytes = zmean_chunk_bytes(p.imgs, p.cols, p.zt);
+    return true;
+}
+
 }  // namespace
+
+extern "C" size_t zs_sdf_grid_attn_zmean_scratch_bytes(int batch, int n_cols, int G, size_t cap_bytes) {
+    ZmeanPlan p;
+    return zmean_plan("zs_sdf_grid_attn_zmean_scratch_bytes", batch, n_cols, G, cap_bytes, p) ? p.bytes : 0;
+}
+
+extern "C" int zs_sdf_grid_attn_zmean_chunk(int batch, int n_cols, int G, size_t cap_bytes, int *imgs_per_chunk,
+                                            int *cols_per_chunk) {
+    ZmeanPlan p;
+    if (!zmean_plan("zs_sdf_grid_attn_zmean_chunk", batch, n_cols, G, cap_bytes, p)) return 0;
+    if (imgs_per_chunk) *imgs_per_chunk = p.imgs;
+    if (cols_per_chunk) *cols_per_chunk = p.cols;
+    return 1;
+}
+
+extern "C" int zs_sdf_grid_attn_zmean(const void *programs, size_t program_stride_bytes, int batch,
+                                      const float *axis, int G, const int *columns, int n_cols, float *zmean,
+                                      void *workspace, void *scratch, size_t scratch_bytes, void *stream) {
+    ZmeanPlan p;
+    if (batch > 0 && n_cols > 0 && scratch_bytes == 0) {
+        zs::set_err("zs_sdf_grid_attn_zmean: no scratch");
+        return 0;
+    }
+    if (!zmean_plan("zs_sdf_grid_attn_zmean", batch, n_cols, G, scratch_bytes, p)) return 0;
+    if (batch == 0 || n_cols == 0) return 1;
+    if (!programs || !axis || !columns || !zmean || !workspace || !scratch) {
+        zs::set_err("zs_sdf_grid_attn_zmean: null pointer");
+        return 0;
+    }
+    if (program_stride_bytes % 16 != 0 || program_stride_bytes < zs_sdf_program_bytes()) {
+        zs::set_err("zs_sdf_grid_attn_zmean: bad program stride %zu", program_stride_bytes);
+        return 0;
+    }
+    if (reinterpret_cast<uintptr_t>(scratch) % 16 != 0) {
+        zs::set_err("zs_sdf_grid_attn_zmean: scratch must be 16-byte aligned");
+        return 0;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // chunks reuse the scratch: they are enqueued on one stream and run in order
+    for (int img0 = 0; img0 < batch; img0 += p.imgs) {
+        const int imgs = batch - img0 < p.imgs ? batch - img0 : p.imgs;
+        const float *prog = static_cast<const float *>(programs) + (size_t)img0 * (program_stride_bytes / sizeof(float));
+        for (int col0 = 0; col0 < n_cols; col0 += p.cols) {
+            const int cols = n_cols - col0 < p.cols ? n_cols - col0 : p.cols;
+            const int m = cols * p.zt * PTS_PER_WAVE;
+            const int tiles_per_img = (m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK;
+            f32x4 *raw = static_cast<f32x4 *>(scratch);
+            float *points = reinterpret_cast<float *>(raw + (size_t)imgs * tiles_per_img * WAVES * ATTN_WT_F4);
+            float *logits = points + (size_t)imgs * m * 3;
+            const long long n_pts = (long long)imgs * m;
+            hipLaunchKernelGGL(column_points_kernel, dim3((int)((n_pts + 255) / 256 < 1024 ? (n_pts + 255) / 256 : 1024)),
+                               dim3(256), 0, st, axis, G, columns + 2 * (size_t)col0, cols, p.zt, imgs, points);
+            hipLaunchKernelGGL((sdf_decode_kernel<false, true>), dim3(decode_grid_size(imgs, m)), dim3(WAVES * 64), 0,
+                               st, prog, program_stride_bytes / sizeof(float), imgs, points, nullptr, 0, 0LL, m, logits,
+                               0, static_cast<f32x4 *>(workspace), raw, nullptr);
+            hipLaunchKernelGGL(attn_zmean_kernel, dim3(imgs * cols * LT), dim3(256), 0, st, raw,
+                               zmean + ((size_t)img0 * n_cols + col0) * L, cols, n_cols, tiles_per_img, p.zt, G);
+        }
+    }
+    return zs::check_launch("zs_sdf_grid_attn_zmean") ? 1 : 0;
+}
 
 extern "C" size_t zs_sdf_program_bytes(void) { return (size_t)PROGRAM_FLOATS * sizeof(float); }
 extern "C" size_t zs_sdf_workspace_bytes(void) { return WORKSPACE_BYTES; }

@@ -24,6 +24,7 @@ inference too (`fused` is False: forward(), with the attention map from zs_point
 slice loop; prepare / query_* raise).  Head dimensions other than 32 and more than 256 latent rows raise.
 """
 import contextlib
+import ctypes
 import os
 from functools import partial
 
@@ -641,6 +642,58 @@ class Implicit(nn.Module):
                                                  _lib.ptr(axis), G, point_begin, point_end, sig, _lib.ptr(out),
                                                  None, ws, st)
         _lib.check(rc, "zs_sdf_query_grid_range")
+        return out
+
+    @staticmethod
+    def grid_attention_chunks(batch, n_cols, G, scratch_cap_bytes=None):
+        """How query_grid_attention splits its work under a scratch cap (None: the library's 256 MiB):
+        (images per chunk, columns per chunk, number of chunks).  Raises when the cap is below one column of one image."""
+        lib = _lib.load()
+        imgs, cols = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(lib.zs_sdf_grid_attn_zmean_chunk(batch, n_cols, G, int(scratch_cap_bytes or 0), ctypes.byref(imgs),
+                                                    ctypes.byref(cols)), "zs_sdf_grid_attn_zmean_chunk")
+        if batch == 0 or n_cols == 0:
+            return 0, 0, 0
+        return imgs.value, cols.value, -(-batch // imgs.value) * -(-n_cols // cols.value)
+
+    @torch.no_grad()
+    def query_grid_attention(self, latent_depth, axis, columns, state=None, scratch_cap_bytes=None):
+        """The attention map of forward(need_attn=True) averaged over z for the grid columns ``columns`` [n_cols, 2] =
+        (ix, iy) of the dense grid over ``axis`` (utils/eval_3D.py:47-52 keeps nothing else of the map): [B, n_cols, 197]
+        fp32, reduced on the device from the exact kernel's raw tiles - no [points, 197] tensor.  Always the exact-fp32
+        programs (``state.exact`` of an f16x3 state), like the map of forward().  The scratch is bounded by
+        ``scratch_cap_bytes`` (None: 256 MiB) whatever the grid; see grid_attention_chunks."""
+        if self.semantic:
+            raise ValueError("query_grid_attention serves Implicit(semantic=False); this decoder takes semantic codes")
+        self._check_supported()                 # (raises for configurations that run layer by layer)
+        lib = _lib.load()
+        if state is None:
+            state = self.prepare(latent_depth)
+        programs = state.exact if state.precision == "f16x3" else state.programs
+        axis = axis.detach().to(torch.float32).contiguous()
+        dev = programs.device
+        if axis.device != dev:
+            raise ValueError("axis and latent_depth live on different devices")
+        G = axis.numel()
+        cols = np.ascontiguousarray(np.asarray(columns.cpu() if isinstance(columns, torch.Tensor) else columns,
+                                               dtype=np.int32).reshape(-1, 2))
+        if cols.size and (cols.min() < 0 or cols.max() >= G):
+            raise IndexError("grid column outside [0, %d)" % G)
+        n_cols = cols.shape[0]
+        out = torch.empty(state.batch, n_cols, P.L, dtype=torch.float32, device=dev)
+        if state.batch == 0 or n_cols == 0:
+            return out
+        cap = int(scratch_cap_bytes or 0)
+        need = lib.zs_sdf_grid_attn_zmean_scratch_bytes(state.batch, n_cols, G, cap)
+        if need == 0:       # the cap is below one column of one image: the chunk query carries the message
+            self.grid_attention_chunks(state.batch, n_cols, G, cap)
+        cols_dev = torch.from_numpy(cols).to(dev)
+        scratch = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        with _lib.on(dev):
+            rc = lib.zs_sdf_grid_attn_zmean(_lib.ptr(programs), programs.stride(0) * 4, state.batch, _lib.ptr(axis), G,
+                                            _lib.ptr(cols_dev), n_cols, _lib.ptr(out), _lib.ptr(self.workspace(dev)),
+                                            _lib.ptr(scratch), need, _lib.current_stream_ptr(dev))
+        _lib.check(rc, "zs_sdf_grid_attn_zmean")
         return out
 
     def forward(self, latent_depth, latent_semantic, points_3D, need_attn=True):

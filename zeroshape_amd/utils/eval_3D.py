@@ -2,7 +2,8 @@
 argument meaning and return values, running on the hand-written HIP kernels.
 
   get_dense_3D_grid   utils/eval_3D.py:11-20
-  compute_level_grid  utils/eval_3D.py:22-81   (vis_attn branch: host-side, see below)
+  compute_level_grid  utils/eval_3D.py:22-81   (vis_attn branch: z-mean attention of the drawn grid columns + frame
+                                               composer on the device, csrc/attn_vis.hip; the slice loop otherwise)
   standardize_pc      utils/eval_3D.py:83-91
   normalize_pc        utils/eval_3D.py:93-102
   brute_force_search  utils/eval_3D.py:140-170
@@ -75,7 +76,10 @@ def compute_level_grid(opt, impl_network, latent_depth, latent_semantic, points_
     Fast path: ``impl_network`` is the HIP decoder and ``points_3D`` came from
     get_dense_3D_grid -> one fused launch per image batch over the whole grid
     (no per-slice loop, no points tensor read, no attention materialisation).
-    Otherwise: the reference's slice loop through ``impl_network(...)``."""
+    With ``vis_attn`` the same occupancies, plus the heat-map frames from the attention of the grid columns
+    they draw (query_grid_attention: 1.7 % of the points at vox 128, reduced to the z-mean on the device) and
+    one composer launch (attention_frames); one device-to-host copy of all frames.
+    Otherwise (also with image sharding and vis_attn): the reference's slice loop through ``impl_network(...)``."""
     latent_depth = latent_depth.to(torch.float32) if latent_depth is not None else None
     latent_semantic = latent_semantic.to(torch.float32) if latent_semantic is not None else None
     batch_size = points_3D.shape[0]
@@ -86,8 +90,16 @@ def compute_level_grid(opt, impl_network, latent_depth, latent_semantic, points_
     info = getattr(points_3D, "_zs_grid", None)
     if info is not None and (info.version != points_3D._version or info.G != N):
         info = None            # modified in place since get_dense_3D_grid made it: read the points
-    if info is not None and hasattr(impl_network, "query_grid") and getattr(impl_network, "fused", True) and not vis_attn \
-            and latent_semantic is None:
+    fast = info is not None and hasattr(impl_network, "query_grid") and getattr(impl_network, "fused", True) \
+        and latent_semantic is None
+    if fast and vis_attn and image_sharding(opt) is None:
+        columns, frame_col = attention_frame_columns(N)
+        state = impl_network.prepare(latent_depth)
+        occ = impl_network.query_grid(latent_depth, info.axis, apply_sigmoid=True, state=state)
+        zmean = impl_network.query_grid_attention(latent_depth, info.axis, columns, state=state)
+        frames = attention_frames(opt, zmean, frame_col, images).cpu().numpy()       # the one device-to-host copy
+        return occ, [[frames[b, f] for f in range(frames.shape[1])] for b in range(batch_size)]
+    if fast and not vis_attn:
         if image_sharding(opt) is not None:
             # every rank holds the same images (and ran the same prologue); rank r evaluates its tile-aligned
             # point range of every image and ONE all_gather_into_tensor rebuilds the grids everywhere
@@ -137,8 +149,62 @@ def show_att_on_image(img, mask):
     return merged / np.max(merged)
 
 
+def attention_frame_columns(G):
+    """The frames of utils/eval_3D.py:62-79 as host-side index lists: ``columns`` int32 [n_cols, 2] = the distinct grid
+    columns (ix, iy) the loop draws, in ascending order, and ``frame_col`` int32 [F] = the column of every frame in the
+    loop's order - rows (iy) 0, 8, ..., columns (ix) 0, 8, ..., G // 8 * 8 ascending on rows that are multiples of 16 and
+    descending on the others.  A G that is a multiple of 8 makes the loop index column G: IndexError, here too."""
+    last = G // 8 * 8
+    if last >= G:
+        raise IndexError("index %d is out of bounds for dimension 1 with size %d" % (last, G))
+    frames = []
+    for row in range(0, G, 8):
+        cols = range(0, last + 1, 8) if row % 16 == 0 else range(last, -1, -8)
+        frames += [(col, row) for col in cols]
+    distinct = sorted(set(frames))
+    where = {c: i for i, c in enumerate(distinct)}
+    return (np.asarray(distinct, np.int32).reshape(-1, 2), np.asarray([where[c] for c in frames], np.int32))
+
+
+_JET_LUT_DEV = {}
+
+
+@torch.no_grad()
+def attention_frames(opt, zmean, frame_col, images):
+    """utils/eval_3D.py:62-79 + show_att_on_image for every frame in ONE launch (zs_attn_frames, csrc/attn_vis.hip):
+    ``zmean`` [B, n_cols, 1 + R*R] (Implicit.query_grid_attention), ``frame_col`` [F] indices into n_cols, ``images``
+    [B, 3, H, W] in [0, 1] -> GPU tensor [B, F, H, W, 3] fp32.  show_att_on_image's assertion on the image is kept (one
+    check per call; the mask is v / max v <= 1 by construction)."""
+    from .. import _lib
+    lib = _lib.load()
+    dev = zmean.device
+    H, W = int(opt.H), int(opt.W)
+    R = H // opt.arch.win_size
+    B, n_cols = zmean.shape[0], zmean.shape[1]
+    zmean = _gpu_f32(zmean, "zmean")
+    images = _gpu_f32(images, "images")
+    if zmean.shape[2] != 1 + R * R:
+        raise ValueError("zmean must be [B, n_cols, %d] for %d x %d patches, got %s" % (1 + R * R, R, R, tuple(zmean.shape)))
+    if tuple(images.shape) != (B, 3, H, W):
+        raise ValueError("images must be [%d, 3, %d, %d], got %s" % (B, H, W, tuple(images.shape)))
+    fc = np.ascontiguousarray(np.asarray(frame_col, np.int32).reshape(-1))
+    if fc.size and (fc.min() < 0 or fc.max() >= n_cols):
+        raise IndexError("frame column outside [0, %d)" % n_cols)
+    assert B == 0 or float(images.max()) <= 1
+    key = str(dev)
+    if key not in _JET_LUT_DEV:
+        _JET_LUT_DEV[key] = torch.from_numpy(_jet_lut()).to(dev).contiguous()
+    frames = torch.empty(B, fc.size, H, W, 3, dtype=torch.float32, device=dev)
+    fc_dev = torch.from_numpy(fc).to(dev)
+    with torch.cuda.device(dev):
+        rc = lib.zs_attn_frames(_lib.ptr(zmean), B, n_cols, _lib.ptr(fc_dev), fc.size, _lib.ptr(images), H, W,
+                                _lib.ptr(_JET_LUT_DEV[key]), R, _lib.ptr(frames), _lib.current_stream_ptr(dev))
+    _lib.check(rc, "zs_attn_frames")
+    return frames
+
+
 def _attention_frames(opt, attn, images, batch_size, N):
-    """utils/eval_3D.py:47-80: host-side heat-map frames for the demo GIF (not part of the hot path)."""
+    """utils/eval_3D.py:47-80: host-side heat-map frames of the slice loop (the fused path: attention_frames)."""
     N_global = 1
     feat_res = opt.H // opt.arch.win_size
     attn = torch.stack(attn, dim=1).view(batch_size, N, N, N, N_global + feat_res ** 2)
