@@ -48,6 +48,24 @@ def test_versions_and_sizes(lib):
     assert lib.zs_last_error() in (b"", None) or isinstance(lib.zs_last_error(), bytes)
 
 
+def test_python_constants_equal_the_header():
+    """Every #define ZS_ACT_* / ZS_CONV_* has a Python constant of the same value in nn/ops.py (the one place in nn/ that
+    writes them), and the names nn/autograd.py and nn/operands.py hand on are those objects' values."""
+    from zeroshape_amd.nn import autograd as A, operands, ops
+    hdr = open(os.path.join(ROOT, "include", "zeroshape_hip.h")).read()
+    defines = {name: int(value, 0) for name, value in re.findall(r"^#define ZS_((?:ACT|CONV)_\w+)[ \t]+(\w+)", hdr, flags=re.M)}
+    assert sum(n.startswith("ACT_") for n in defines) >= 5 and sum(n.startswith("CONV_") for n in defines) >= 13
+    for name, value in defines.items():
+        assert getattr(ops, name) == value, name
+    python = {n for n in vars(ops) if re.fullmatch(r"(ACT|CONV)_[A-Z0-9_]+", n) and isinstance(getattr(ops, n), int)}
+    assert python == set(defines)
+    for mod in (A, operands):
+        for name in defines:
+            if hasattr(mod, name):
+                assert getattr(mod, name) == defines[name], (mod.__name__, name)
+    assert all(hasattr(A, n) for n in defines if n.startswith("ACT_"))
+
+
 def test_argument_errors_are_reported_without_touching_the_gpu(lib):
     # negative sizes / null pointers are rejected before any HIP call: 0 + message
     assert lib.zs_chamfer_forward(None, None, 1, -1, 3, None, None, None, None, None) == 0

@@ -350,6 +350,32 @@ def test_inference_attention_lds_staged(B, L, heads, d, mult, monkeypatch):
     close(got, want, rtol=FWD, what="ops.attention")
 
 
+def test_training_attention_follows_the_training_precision(monkeypatch):
+    """A.attention picks its kernel from the TRAINING forward precision (fp32 unless optim.amp), never from the inference
+    switch ops.CONV_PRECISION: bit-equal to the fp32 kernel by default and to the split-fp16 one after
+    set_forward_precision("f16x3").  33 keys: more than one 32-key tile and a ragged tail."""
+    from zeroshape_amd.nn import autograd as A, ops
+    from zeroshape_amd.nn.operands import SWITCHES
+    heads = 2
+    qkv = torch.randn(2, 33, 3 * 64, generator=torch.Generator().manual_seed(33)).cuda()
+    with torch.no_grad():
+        with monkeypatch.context() as m:
+            m.setattr(ops, "CONV_PRECISION", "f32")
+            r32 = ops.attention(qkv, heads)
+            m.setattr(ops, "CONV_PRECISION", "f16x3")
+            r16 = ops.attention(qkv, heads)
+    assert not torch.equal(r32, r16), "precondition: the two arithmetics must differ on this input (choose another seed)"
+    monkeypatch.setattr(A, "ATT_FWD_SPLIT", True)
+    before = SWITCHES.forward
+    try:
+        A.set_forward_precision("f32")
+        assert torch.equal(A.attention(qkv, heads), r32)
+        A.set_forward_precision("f16x3")
+        assert torch.equal(A.attention(qkv, heads), r16)
+    finally:
+        A.set_forward_precision(before)
+
+
 PA_HEADS, PA_D = 8, 32
 PA_CASES = [(1, 33, 256), (2, 70, 64), (1, 40, 65), (1, 5, 1), (1, 513, 197)]
 PA_NUMERIC_CASE = (2, 300, 197)

@@ -81,7 +81,7 @@ def test_conv_forward_dgrad_wgrad(cfg):
 def test_conv_weight_column_ranges_and_padded_input():
     """The decoder's skip layers: one [256, 515] weight applied as three column-range products
     (x | xyz | feat) / sqrt(2); xyz has 3 channels padded to 4."""
-    from zeroshape_amd.nn import autograd as A
+    from zeroshape_amd.nn import autograd as A, ops
     g = torch.Generator().manual_seed(5)
     n, C = 333, 256
     xs, pts, feat = torch.randn(1, n, C, generator=g), torch.randn(1, n, 3, generator=g), torch.randn(1, n, C, generator=g)
@@ -92,7 +92,7 @@ def test_conv_weight_column_ranges_and_padded_input():
     gy = torch.randn(y.shape, generator=g)
     y.backward(gy)
     xg, fg, wg, bg = [t.cuda().requires_grad_(True) for t in (xs, feat, w, b)]
-    p4 = A._pad_channels(pts.cuda(), 4)
+    p4 = ops.pad_channels(pts.cuda(), 4)
     yg = A.linear(p4, wg, None, in_scale=r2, cin0=C, cin=3)
     yg = A.linear(fg, wg, None, in_scale=r2, res1=yg, cin0=C + 3, cin=C)
     yg = A.linear(xg, wg, bg, in_scale=r2, res1=yg, cin0=0, cin=C)

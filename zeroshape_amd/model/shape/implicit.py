@@ -35,6 +35,7 @@ import torch.nn as nn
 from ... import _lib
 from ... import program as P
 from ...nn import autograd as A
+from ...nn import ops
 from ...nn.operands import weights_stamp
 from ...utils.pos_embed import get_2d_sincos_pos_embed
 
@@ -749,7 +750,7 @@ class Implicit(nn.Module):
         if tuple(lat.shape[1:]) != (Ll, self.latent_proj.in_features):
             raise ValueError("latent codes must be [B,%d,%d], got %s" % (Ll, self.latent_proj.in_features, tuple(lat.shape)))
         attn = torch.empty(B, M, Ll, dtype=torch.float32, device=pts.device) if want_attn else None
-        pts4 = A._pad_channels(pts, 4)
+        pts4 = ops.pad_channels(pts, 4)
         xp = A.linear(pts4, self.point_proj.proj.weight, self.point_proj.proj.bias, cin=3)            # :253
         pos = self.pos_embed.detach().expand(B, -1, -1).contiguous()
         cl = lat.shape[-1]

@@ -14,12 +14,16 @@ import os
 import torch
 
 from .. import _lib
+from . import ops
+# The header's ZS_ACT_* / ZS_CONV_* values have one owner, nn/ops.py; ACT_* are here for this module's callers (A.ACT_RELU ...).
+from .ops import ACT_GELU, ACT_NONE, ACT_RELU, ACT_RELU_CLAMP1, ACT_SOFTPLUS  # noqa: F401
+from .ops import CONV_F16X3, CONV_IN_DILATE2, CONV_IN_RELU
+from .pack import out_size
 # The packed / standardised / split forms of the weights and the switches that choose among them have one owner, nn/operands.py;
 # the second line of names is here for the callers outside nn/ (engines, optimiser, checkpoint loading, tools).
-from .operands import CACHE, CONV_F16X3, CONV_IN_DILATE2, CONV_IN_RELU, SWITCHES, ceil4
+from .operands import CACHE, SWITCHES, ceil4
 from .operands import GENERATION, bump_generation, refresh_packs, set_backward_precision, set_forward_precision  # noqa: F401
 
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_CLAMP1, ACT_SOFTPLUS = 0, 1, 2, 3, 4
 # Arithmetic of the weight-gradient GEMMs (zs_conv2d_wgrad with ZS_CONV_F16X3: wgrad_split_kernel, round 3).  Follows the
 # data-gradient setting (optim.amp) unless ZS_TRAIN_WGRAD_PRECISION pins it (A/B measurements).  It stays beside its one reader,
 # _Conv.backward: a weight gradient reads activations and gradients, no cached operand, so no operand's stamp depends on it.
@@ -71,13 +75,6 @@ def scratch(device, name, nbytes):
     return buf
 
 
-def _out_size(n, k, stride, padding):
-    if padding == "same":
-        out = -(-n // stride)
-        return out, max((out - 1) * stride + k - n, 0) // 2
-    return (n + 2 * padding - k) // stride + 1, padding
-
-
 def _conv_launch(x, rec, shift, res1, res2, out, kh, kw, stride, pt, pl, flags, in_scale, in_shift, act):
     lib = _lib.load()
     B, H, W, C = x.shape
@@ -108,16 +105,6 @@ def _act_backward(dy, ref, act, beta=0.0):
         _lib.check(lib.zs_act_backward(_lib.ptr(dy), _lib.ptr(ref), _lib.ptr(dx), dy.numel(), act, float(beta),
                                        _stream(dy)), "zs_act_backward")
     return dx
-
-
-def _pad_channels(x, cpad):
-    lib = _lib.load()
-    C = x.shape[-1]
-    rows = x.numel() // C
-    y = torch.empty(*x.shape[:-1], cpad, dtype=torch.float32, device=x.device)
-    with _lib.on(x.device):
-        _lib.check(lib.zs_nchw_to_nhwc(_lib.ptr(x), None, _lib.ptr(y), rows, C, 1, cpad, _stream(x)), "zs_nchw_to_nhwc")
-    return y
 
 
 # Segmented backward (the captured training step on more than one GPU, model/shape_engine.py).  One hipGraph of forward +
@@ -202,7 +189,7 @@ class _PadChannels(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cpad):
         ctx.C = x.shape[-1]
-        return _pad_channels(_f32c(x, "pad input"), cpad)
+        return ops.pad_channels(_f32c(x, "pad input"), cpad)
 
     @staticmethod
     def backward(ctx, dy):
@@ -228,8 +215,8 @@ class _Conv(torch.autograd.Function):
         cin = cfg.get("cin") or weight.shape[1]
         assert Cx == ceil4(cin), "input has %d channels, layer expects %d (padded to 4)" % (Cx, cin)
         std_eps = cfg.get("std_eps")
-        Ho, pt = _out_size(H, kh, stride, padding)
-        Wo, pl = _out_size(W, kw, stride, padding)
+        Ho, pt = out_size(H, kh, stride, padding)
+        Wo, pl = out_size(W, kw, stride, padding)
         out = torch.empty(B, Ho, Wo, cout, dtype=torch.float32, device=x.device)
         flags = (CONV_IN_RELU if cfg.get("in_relu") else 0) | (CONV_F16X3 if SWITCHES.forward == "f16x3" else 0)
         _conv_launch(x, CACHE.pack(weight, cin0, cin, False, std_eps), None if bias is None else bias.detach(),
@@ -258,7 +245,7 @@ class _Conv(torch.autograd.Function):
         _, H, W, Cx = x.shape
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         want_b = ctx.has[0] and need_b
-        gp = g if cout % 4 == 0 else _pad_channels(g, ceil4(cout))
+        gp = g if cout % 4 == 0 else ops.pad_channels(g, ceil4(cout))
         dw = db = None
         if want_b and not need_w:
             db = column_sum(g.view(-1, cout))
@@ -301,7 +288,7 @@ class _Conv(torch.autograd.Function):
                 if fused:
                     dpass = None
                 if cin != Cx:                       # the input carried zero padding channels
-                    dx = _pad_channels(dx, Cx)
+                    dx = ops.pad_channels(dx, Cx)
             if in_relu:
                 dx = _act_backward(dx, x, ACT_RELU)
         if dpass is not None:
@@ -371,13 +358,8 @@ FUSE_FORKS = os.environ.get("ZS_TRAIN_FUSE_FORKS", "1") != "0"      # A/B switch
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, fork):
-        lib = _lib.load()
         x = _f32c(x, "layer_norm input")
-        C = x.shape[-1]
-        y = torch.empty_like(x)
-        with _lib.on(x.device):
-            _lib.check(lib.zs_layer_norm(_lib.ptr(x), _lib.ptr(gamma.detach()), _lib.ptr(beta.detach()), _lib.ptr(y),
-                                         x.numel() // C, C, float(eps), _stream(x)), "zs_layer_norm")
+        y = ops.layer_norm(x, gamma.detach(), beta.detach(), eps)
         ctx.eps = eps
         ctx.save_for_backward(x, gamma)
         return (y, x.view_as(x)) if fork else y
@@ -416,18 +398,11 @@ ATT_FWD_SPLIT = os.environ.get("ZS_TRAIN_ATT_SPLIT", "1") != "0"      # A/B swit
 class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, heads):
-        lib = _lib.load()
         qkv = _f32c(qkv, "attention input")
-        B, L, C3 = qkv.shape
-        C = C3 // 3
-        out = torch.empty(B, L, C, dtype=torch.float32, device=qkv.device)
         # optim.amp: the split-fp16 forms, like the forward GEMMs around it (batch 4 = 48 (sample, head) pairs: the key-split
-        # kernel, 25 -> 9 us per ViT block); the backward pass recomputes the probabilities in fp32 either way
-        split = SWITCHES.forward == "f16x3" and ATT_FWD_SPLIT
-        with _lib.on(qkv.device):
-            _lib.check((lib.zs_attention_split if split else lib.zs_attention)(
-                _lib.ptr(qkv), _lib.ptr(out), B, L, heads, C // heads, _stream(qkv)),
-                "zs_attention_split" if split else "zs_attention")
+        # kernel, 25 -> 9 us per ViT block); the backward pass recomputes the probabilities in fp32 either way.  The choice is
+        # this path's own (passed explicitly): it never follows the inference switch ops.CONV_PRECISION
+        out = ops.attention(qkv, heads, split=SWITCHES.forward == "f16x3" and ATT_FWD_SPLIT)
         ctx.heads = heads
         ctx.save_for_backward(qkv)
         return out
@@ -694,18 +669,12 @@ def group_norm(x, gamma, beta, groups=32, eps=1e-5, relu=False, residual=None):
 class _MaxPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k, stride, padding):
-        lib = _lib.load()
         x = _f32c(x, "max_pool input")
-        B, H, W, C = x.shape
-        Ho, pt = _out_size(H, k, stride, padding)
-        Wo, pl = _out_size(W, k, stride, padding)
-        y = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
-        with _lib.on(x.device):
-            _lib.check(lib.zs_max_pool_nhwc(_lib.ptr(x), _lib.ptr(y), B, H, W, C, Ho, Wo, k, stride, pt, pl,
-                                            _stream(x)), "zs_max_pool_nhwc")
+        Ho, pt = out_size(x.shape[1], k, stride, padding)
+        Wo, pl = out_size(x.shape[2], k, stride, padding)
         ctx.cfg = (k, stride, pt, pl, Ho, Wo)
         ctx.save_for_backward(x)
-        return y
+        return ops.max_pool(x, k, stride, padding)
 
     @staticmethod
     def backward(ctx, dy):
@@ -728,15 +697,9 @@ def max_pool(x, k=3, stride=2, padding=1):
 class _GlobalMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        lib = _lib.load()
         x = _f32c(x, "global_mean input")
-        B, H, W, C = x.shape
-        y = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        with _lib.on(x.device):
-            _lib.check(lib.zs_global_mean_nhwc(_lib.ptr(x), _lib.ptr(y), B, H * W, C, _stream(x)),
-                       "zs_global_mean_nhwc")
-        ctx.shape = (B, H, W, C)
-        return y
+        ctx.shape = tuple(x.shape)
+        return ops.global_mean(x)
 
     @staticmethod
     def backward(ctx, dy):
@@ -757,14 +720,9 @@ def global_mean(x):
 class _Upsample2x(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        lib = _lib.load()
         x = _f32c(x, "upsample2x input")
-        B, H, W, C = x.shape
-        y = torch.empty(B, 2 * H, 2 * W, C, dtype=torch.float32, device=x.device)
-        with _lib.on(x.device):
-            _lib.check(lib.zs_upsample2x_nhwc(_lib.ptr(x), _lib.ptr(y), B, H, W, C, _stream(x)), "zs_upsample2x_nhwc")
-        ctx.shape = (B, H, W, C)
-        return y
+        ctx.shape = tuple(x.shape)
+        return ops.upsample2x(x)
 
     @staticmethod
     def backward(ctx, dy):
@@ -787,17 +745,12 @@ class _ToNHWC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, mask, cpad):
-        lib = _lib.load()
         x = _f32c(x, "to_nhwc input")
-        B, C, H, W = x.shape
+        # the fp32 mask is converted here, once: the backward saves it, ops.to_nhwc finds nothing left to convert
         m = None if mask is None else _f32c(mask.float(), "to_nhwc mask")
-        y = torch.empty(B, H, W, cpad, dtype=torch.float32, device=x.device)
-        with _lib.on(x.device):
-            _lib.check(lib.zs_nchw_to_nhwc(_lib.ptr(x), _lib.ptr(m), _lib.ptr(y), B, C, H * W, cpad, _stream(x)),
-                       "zs_nchw_to_nhwc")
-        ctx.shape = (B, C, H, W, cpad)
+        ctx.shape = tuple(x.shape) + (cpad,)
         ctx.save_for_backward(m)
-        return y
+        return ops.to_nhwc(x, cpad, m)
 
     @staticmethod
     def backward(ctx, dy):
@@ -819,24 +772,11 @@ def to_nhwc(x, cpad=None, mask=None):
 class _ToNCHW(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        lib = _lib.load()
-        x = _f32c(x, "to_nchw input")
-        B, H, W, C = x.shape
-        y = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
-        with _lib.on(x.device):
-            _lib.check(lib.zs_nhwc_to_nchw(_lib.ptr(x), _lib.ptr(y), B, C, H * W, _stream(x)), "zs_nhwc_to_nchw")
-        return y
+        return ops.to_nchw(_f32c(x, "to_nchw input"))
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        dy = _f32c(dy, "to_nchw grad")
-        B, C, H, W = dy.shape
-        dx = torch.empty(B, H, W, C, dtype=torch.float32, device=dy.device)
-        with _lib.on(dy.device):
-            _lib.check(lib.zs_nchw_to_nhwc(_lib.ptr(dy), None, _lib.ptr(dx), B, C, H * W, C, _stream(dy)),
-                       "zs_nchw_to_nhwc")
-        return dx
+        return ops.to_nhwc(_f32c(dy, "to_nchw grad"))
 
 
 def to_nchw(x):
@@ -845,46 +785,59 @@ def to_nchw(x):
 
 class _SeenSurface(torch.autograd.Function):
     """graph_shape.py:131-144 in one launch each way: (depth [B,1,H,W], intr [B,3,3], mask) ->
-    (seen_points [B,HW,3], seen_3D_dsp [B,3,H,W], mask_dsp [B,1,H,W]); same-size resample only."""
+    (seen_points [B,HW,3], seen_3D_dsp [B,3,H/dsp,W/dsp], mask_dsp [B,1,H/dsp,W/dsp]).  dsp = 1: same-size resample;
+    dsp = 2 (arch.depth.dsp = 2, the transformer coordinate encoder): the coordinate map and its mask resampled to half
+    the size (interpolate_coordmap, utils/util.py:336-345)."""
 
     @staticmethod
-    def forward(ctx, depth, intr, mask):
+    def forward(ctx, depth, intr, mask, dsp):
         lib = _lib.load()
         depth, intr = _f32c(depth, "depth"), _f32c(intr, "intr")
         m = _f32c(mask.float(), "mask")
         B, _, H, W = depth.shape
+        Ho, Wo = H // dsp, W // dsp
         dev = depth.device
         seen = torch.empty(B, H * W, 3, dtype=torch.float32, device=dev)
         mean = torch.empty(B, 3, dtype=torch.float32, device=dev)
         scale = torch.empty(B, dtype=torch.float32, device=dev)
-        coord = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
-        mask_dsp = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+        coord = torch.empty(B, 3, Ho, Wo, dtype=torch.float32, device=dev)
+        mask_dsp = torch.empty(B, 1, Ho, Wo, dtype=torch.float32, device=dev)
         with _lib.on(dev):
-            _lib.check(lib.zs_seen_surface(_lib.ptr(depth), _lib.ptr(intr), _lib.ptr(m), B, H, W, H, W, _lib.ptr(seen),
+            _lib.check(lib.zs_seen_surface(_lib.ptr(depth), _lib.ptr(intr), _lib.ptr(m), B, H, W, Ho, Wo, _lib.ptr(seen),
                                            _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(coord), _lib.ptr(mask_dsp),
                                            _stream(depth)), "zs_seen_surface")
-        ctx.save_for_backward(depth, intr, m, mean, scale)
+        ctx.dsp = dsp
+        ctx.save_for_backward(depth, intr, m, mean, scale, mask_dsp if dsp == 2 else None)
         ctx.mark_non_differentiable(mask_dsp)
         return seen, coord, mask_dsp
 
     @staticmethod
     def backward(ctx, d_seen, d_coord, _d_mask):
         lib = _lib.load()
-        depth, intr, m, mean, scale = ctx.saved_tensors
+        depth, intr, m, mean, scale, mask_dsp = ctx.saved_tensors
         B, _, H, W = depth.shape
         d_seen = None if d_seen is None else _f32c(d_seen, "seen grad")
         d_coord = None if d_coord is None else _f32c(d_coord, "coord grad")
-        dd = torch.empty_like(depth)
-        dk = torch.empty_like(intr)
         with _lib.on(depth.device):
+            if ctx.dsp == 2 and d_coord is not None:      # the half-size map's gradient back at full size first
+                d_full = torch.empty(B, 3, H, W, dtype=torch.float32, device=depth.device)
+                _lib.check(lib.zs_coord_dsp2_bwd(_lib.ptr(d_coord), _lib.ptr(m), _lib.ptr(mask_dsp), _lib.ptr(d_full),
+                                                 B, H, W, _stream(depth)), "zs_coord_dsp2_bwd")
+                d_coord = d_full
+            dd = torch.empty_like(depth)
+            dk = torch.empty_like(intr)
             _lib.check(lib.zs_seen_surface_bwd(_lib.ptr(depth), _lib.ptr(intr), _lib.ptr(m), _lib.ptr(mean),
                                                _lib.ptr(scale), _lib.ptr(d_seen), _lib.ptr(d_coord), B, H, W,
                                                _lib.ptr(dd), _lib.ptr(dk), _stream(depth)), "zs_seen_surface_bwd")
-        return dd, dk, None
+        return dd, dk, None, None
 
 
 def seen_surface(depth, intr, mask):
-    return _SeenSurface.apply(depth, intr, mask)
+    return _SeenSurface.apply(depth, intr, mask, 1)
+
+
+def seen_surface_dsp2(depth, intr, mask):
+    return _SeenSurface.apply(depth, intr, mask, 2)
 
 
 class _IntrParam2Mtx(torch.autograd.Function):
@@ -954,14 +907,7 @@ class _AssembleTokens(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, cls, pos):
-        lib = _lib.load()
-        feat, cls, pos = _f32c(feat, "tokens"), _f32c(cls, "cls"), _f32c(pos, "pos")
-        B, n, C = feat.shape
-        y = torch.empty(B, n + 1, C, dtype=torch.float32, device=feat.device)
-        with _lib.on(feat.device):
-            _lib.check(lib.zs_assemble_tokens(_lib.ptr(feat), _lib.ptr(cls), _lib.ptr(pos), _lib.ptr(y), B, n, C,
-                                              _stream(feat)), "zs_assemble_tokens")
-        return y
+        return ops.assemble_tokens(_f32c(feat, "tokens"), _f32c(cls, "cls"), _f32c(pos, "pos"))
 
     @staticmethod
     def backward(ctx, dy):
@@ -981,18 +927,12 @@ class _WindowTokens(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, emb, mask, invalid_token, cls, pos, win):
-        lib = _lib.load()
         emb, invalid_token = _f32c(emb, "window_tokens input"), _f32c(invalid_token, "invalid_coord_token")
         cls, pos = _f32c(cls, "cls_token"), _f32c(pos, "two_d_pos_embed")
-        B, H, W, C = emb.shape
-        m = mask.to(torch.uint8).contiguous()
-        out = torch.empty(B * (H // win) * (W // win), win * win + 1, C, dtype=torch.float32, device=emb.device)
-        with _lib.on(emb.device):
-            _lib.check(lib.zs_window_tokens(_lib.ptr(emb), _lib.ptr(m), _lib.ptr(invalid_token), _lib.ptr(cls), _lib.ptr(pos),
-                                            _lib.ptr(out), B, H, W, C, win, _stream(emb)), "zs_window_tokens")
+        m = mask.to(torch.uint8).contiguous()      # converted here, once: the backward saves it, ops.window_tokens takes it as is
         ctx.save_for_backward(m)
-        ctx.geom = (B, H, W, C, win)
-        return out
+        ctx.geom = tuple(emb.shape) + (win,)
+        return ops.window_tokens(emb, m, invalid_token, cls, pos, win)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1013,66 +953,10 @@ def window_tokens(emb, mask, invalid_token, cls, pos, win):
     return _WindowTokens.apply(emb, mask, invalid_token, cls, pos, win)
 
 
-class _SeenSurfaceDsp2(torch.autograd.Function):
-    """graph_shape.py:131-144 with arch.depth.dsp = 2 (the transformer coordinate encoder): as _SeenSurface, the
-    coordinate map and its mask resampled to half the size (interpolate_coordmap, utils/util.py:336-345)."""
-
-    @staticmethod
-    def forward(ctx, depth, intr, mask):
-        lib = _lib.load()
-        depth, intr = _f32c(depth, "depth"), _f32c(intr, "intr")
-        m = _f32c(mask.float(), "mask")
-        B, _, H, W = depth.shape
-        Ho, Wo = H // 2, W // 2
-        dev = depth.device
-        seen = torch.empty(B, H * W, 3, dtype=torch.float32, device=dev)
-        mean = torch.empty(B, 3, dtype=torch.float32, device=dev)
-        scale = torch.empty(B, dtype=torch.float32, device=dev)
-        coord = torch.empty(B, 3, Ho, Wo, dtype=torch.float32, device=dev)
-        mask_dsp = torch.empty(B, 1, Ho, Wo, dtype=torch.float32, device=dev)
-        with _lib.on(dev):
-            _lib.check(lib.zs_seen_surface(_lib.ptr(depth), _lib.ptr(intr), _lib.ptr(m), B, H, W, Ho, Wo, _lib.ptr(seen),
-                                           _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(coord), _lib.ptr(mask_dsp),
-                                           _stream(depth)), "zs_seen_surface")
-        ctx.save_for_backward(depth, intr, m, mean, scale, mask_dsp)
-        ctx.mark_non_differentiable(mask_dsp)
-        return seen, coord, mask_dsp
-
-    @staticmethod
-    def backward(ctx, d_seen, d_coord, _d_mask):
-        lib = _lib.load()
-        depth, intr, m, mean, scale, mask_dsp = ctx.saved_tensors
-        B, _, H, W = depth.shape
-        d_seen = None if d_seen is None else _f32c(d_seen, "seen grad")
-        d_full = None
-        with _lib.on(depth.device):
-            if d_coord is not None:
-                d_full = torch.empty(B, 3, H, W, dtype=torch.float32, device=depth.device)
-                _lib.check(lib.zs_coord_dsp2_bwd(_lib.ptr(_f32c(d_coord, "coord grad")), _lib.ptr(m), _lib.ptr(mask_dsp),
-                                                 _lib.ptr(d_full), B, H, W, _stream(depth)), "zs_coord_dsp2_bwd")
-            dd = torch.empty_like(depth)
-            dk = torch.empty_like(intr)
-            _lib.check(lib.zs_seen_surface_bwd(_lib.ptr(depth), _lib.ptr(intr), _lib.ptr(m), _lib.ptr(mean),
-                                               _lib.ptr(scale), _lib.ptr(d_seen), _lib.ptr(d_full), B, H, W,
-                                               _lib.ptr(dd), _lib.ptr(dk), _stream(depth)), "zs_seen_surface_bwd")
-        return dd, dk, None
-
-
-def seen_surface_dsp2(depth, intr, mask):
-    return _SeenSurfaceDsp2.apply(depth, intr, mask)
-
-
 class _ReadoutConcat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tokens):
-        lib = _lib.load()
-        tokens = _f32c(tokens, "readout input")
-        B, n1, C = tokens.shape
-        y = torch.empty(B, n1 - 1, 2 * C, dtype=torch.float32, device=tokens.device)
-        with _lib.on(tokens.device):
-            _lib.check(lib.zs_readout_concat(_lib.ptr(tokens), _lib.ptr(y), B, n1 - 1, C, _stream(tokens)),
-                       "zs_readout_concat")
-        return y
+        return ops.readout_concat(_f32c(tokens, "readout input"))
 
     @staticmethod
     def backward(ctx, dy):

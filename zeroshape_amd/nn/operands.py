@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .ops import CONV_F16X3, CONV_IN_DILATE2, CONV_W_PRESPLIT      # ZS_CONV_* flags of zs_conv2d_nhwc
 
-CONV_IN_RELU, CONV_IN_DILATE2, CONV_F16X3, CONV_W_PRESPLIT = 1, 8, 16, 128      # ZS_CONV_* flags of zs_conv2d_nhwc
 # Bumped whenever parameters are updated through raw pointers (the fused optimiser): tensor
 # ._version does not see those writes, so every pack cache also keys on this counter.
 GENERATION = [0]

@@ -6,8 +6,15 @@ import os
 import torch
 
 from .. import _lib
+from .pack import out_size
 
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_CLAMP1 = 0, 1, 2, 3
+# The ZS_ACT_* / ZS_CONV_* values of include/zeroshape_hip.h, written here and nowhere else in nn/ (nn/operands.py and
+# nn/autograd.py import them; tests/test_c_abi.py holds every one against the header).  ACT_SOFTPLUS: zs_act_forward /
+# zs_act_backward only.
+ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_CLAMP1, ACT_SOFTPLUS = 0, 1, 2, 3, 4
+CONV_IN_RELU, CONV_FORCE_LARGE, CONV_FORCE_SMALL, CONV_IN_DILATE2, CONV_F16X3 = 1, 2, 4, 8, 16
+CONV_SPLIT_SMALL, CONV_STREAM_K, CONV_W_PRESPLIT, CONV_STREAM_K_ALWAYS = 32, 64, 128, 256
+CONV_IN_UPSAMPLE2, CONV_FORCE_TILE256, CONV_OUT_K16, CONV_IN_K16 = 512, 1024, 2048, 4096
 
 
 def _chk(t, what):
@@ -20,7 +27,7 @@ def _stream(t):
     return _lib.current_stream_ptr(t.device)
 
 
-_TILING = {None: 0, "large": 2, "small": 4, "tile256": 1024}
+_TILING = {None: 0, "large": CONV_FORCE_LARGE, "small": CONV_FORCE_SMALL, "tile256": CONV_FORCE_TILE256}
 
 # Arithmetic of the inference convolutions / linear layers (zs_conv2d_nhwc): "f32" = exact fp32 MFMA,
 # "f16x3" = split-fp16 on the 16-bit matrix pipe (ZS_CONV_F16X3; operands as two fp16 halves, ~2^-21
@@ -40,7 +47,6 @@ SPLIT_K = os.environ.get("ZS_CONV_SPLIT_K", "0") != "0"
 # of convolution time with it everywhere).  ZS_CONV_STREAM_K=1 enables the kernel's own shape rule,
 # "always" (tests) forces it wherever supported.
 STREAM_K = {"0": False, "1": True, "always": "always"}[os.environ.get("ZS_CONV_STREAM_K", "0")]
-_CONV_SPLIT_SMALL, _CONV_STREAM_K, _CONV_W_PRESPLIT, _CONV_STREAM_K_ALWAYS = 32, 64, 128, 256
 # f16x3: the weights' fp16 halves are computed once per layer (zs_conv2d_presplit_weight) instead of in every
 # workgroup of every launch.  ZS_CONV_PRESPLIT=0: split at run time (A/B measurements).
 PRESPLIT = os.environ.get("ZS_CONV_PRESPLIT", "1") != "0"
@@ -78,8 +84,8 @@ def splitk_workspace(device):
 
 
 def conv_flags():
-    return (16 if CONV_PRECISION == "f16x3" else 0) | (_CONV_SPLIT_SMALL if SPLIT_K else 0) | \
-        (_CONV_STREAM_K if STREAM_K else 0) | (_CONV_STREAM_K_ALWAYS if STREAM_K == "always" else 0)
+    return (CONV_F16X3 if CONV_PRECISION == "f16x3" else 0) | (CONV_SPLIT_SMALL if SPLIT_K else 0) | \
+        (CONV_STREAM_K if STREAM_K else 0) | (CONV_STREAM_K_ALWAYS if STREAM_K == "always" else 0)
 
 
 class Stats:
@@ -100,15 +106,12 @@ def fused_ok(x, pc=None):
 FUSE_NORM = os.environ.get("ZS_CONV_FUSE_NORM", "1") != "0"
 
 
-_CONV_OUT_K16, _CONV_IN_K16 = 2048, 4096       # include/zeroshape_hip.h
-
-
 def k16_ok(rows, cin, cout, in_k16=False, out_k16=False, ln_tiles=0, row_stats=False, has_res=False):
     """Would the library take this pointwise layer with K16-major operands (zs_conv2d_k16_ok)?  Asked before a tensor's layout is
     chosen: only the streaming GEMM kernel of the batch-1 engine reads / writes [C / 16][rows][16]."""
     if not (CONV_PRECISION == "f16x3" and PRESPLIT and K16_HIDDEN):
         return False
-    flags = (_CONV_IN_K16 if in_k16 else 0) | (_CONV_OUT_K16 if out_k16 else 0)
+    flags = (CONV_IN_K16 if in_k16 else 0) | (CONV_OUT_K16 if out_k16 else 0)
     return bool(_lib.load().zs_conv2d_k16_ok(int(rows), int(cin), int(cout), flags, int(ln_tiles), 1 if row_stats else 0,
                                              1 if has_res else 0))
 
@@ -133,10 +136,10 @@ def conv2d(x, pc, res1=None, res2=None, act=ACT_NONE, in_relu=False, in_scale=1.
         if r is not None:
             _chk(r, "conv2d residual")
             assert r.shape == out.shape
-    flags = (1 if in_relu else 0) | _TILING[tiling] | conv_flags()
+    flags = (CONV_IN_RELU if in_relu else 0) | _TILING[tiling] | conv_flags()
     # K16-major operands (pointwise layers of few rows; the caller has asked k16_ok): x / the result keep their logical shape,
     # the bytes are [C / 16][rows][16]
-    flags |= (_CONV_IN_K16 if in_k16 else 0) | (_CONV_OUT_K16 if out_k16 else 0)
+    flags |= (CONV_IN_K16 if in_k16 else 0) | (CONV_OUT_K16 if out_k16 else 0)
     w = pc.w
     if PRESPLIT and CONV_PRECISION == "f16x3":
         if pc.w16 is None:
@@ -144,7 +147,7 @@ def conv2d(x, pc, res1=None, res2=None, act=ACT_NONE, in_relu=False, in_scale=1.
             with _lib.on(x.device):
                 _lib.check(lib.zs_conv2d_presplit_weight(_lib.ptr(pc.w), _lib.ptr(pc.w16), C, pc.cout, pc.kh, pc.kw,
                                                          _stream(x)), "zs_conv2d_presplit_weight")
-        w, flags = pc.w16, flags | _CONV_W_PRESPLIT
+        w, flags = pc.w16, flags | CONV_W_PRESPLIT
     fused = gn_in is not None or ln_in is not None or stats_out is not None
     if not fused:
         with _lib.on(x.device):
@@ -182,7 +185,7 @@ def conv2d(x, pc, res1=None, res2=None, act=ACT_NONE, in_relu=False, in_scale=1.
     with _lib.on(x.device):
         _lib.check(lib.zs_conv2d_nhwc_fused(_lib.ptr(x), _lib.ptr(w), _lib.ptr(pc.scale), _lib.ptr(pc.shift),
                                             _lib.ptr(res1), _lib.ptr(res2), _lib.ptr(out), B, H, W, C, Ho, Wo, pc.cout,
-                                            pc.kh, pc.kw, pc.stride, pt, pl, flags & ~_CONV_SPLIT_SMALL, float(in_scale),
+                                            pc.kh, pc.kw, pc.stride, pt, pl, flags & ~CONV_SPLIT_SMALL, float(in_scale),
                                             float(in_shift), act, ctypes.addressof(fz),
                                             _lib.ptr(splitk_workspace(x.device)), _stream(x)),
                    "zs_conv2d_nhwc_fused")
@@ -230,7 +233,7 @@ def conv2d_tail(x, pc, pc_tail, act=ACT_NONE, tail_act=ACT_NONE, in_relu=False, 
             wv = wv * pc_tail.scale[0]
         pc_tail.tail_vec = wv.contiguous()
     out = torch.empty(B, H, W, 1, dtype=torch.float32, device=x.device)
-    flags = (1 if in_relu else 0) | 16 | _CONV_W_PRESPLIT | (512 if up_fused else 0)
+    flags = (CONV_IN_RELU if in_relu else 0) | CONV_F16X3 | CONV_W_PRESPLIT | (CONV_IN_UPSAMPLE2 if up_fused else 0)
     with _lib.on(x.device):
         _lib.check(lib.zs_conv3x3_tail_nhwc(_lib.ptr(x), _lib.ptr(pc.w16), _lib.ptr(pc.scale), _lib.ptr(pc.shift), _lib.ptr(out),
                                             B, H, W, C, pc.cout, flags, act, _lib.ptr(pc_tail.tail_vec),
@@ -312,16 +315,20 @@ def layer_norm(x, gamma, beta, eps=1e-6):
     return y
 
 
-def attention(qkv, heads):
-    """qkv [B,L,3*C] -> [B,L,C]."""
+def attention(qkv, heads, split=None):
+    """qkv [B,L,3*C] -> [B,L,C].  split: the split-fp16 kernel (zs_attention_split) or the fp32 one; None = follow
+    CONV_PRECISION like the convolutions around it (the training path passes its own choice, nn/autograd.py)."""
     lib = _lib.load()
     _chk(qkv, "attention input")
     B, L, C3 = qkv.shape
     C = C3 // 3
     out = torch.empty(B, L, C, dtype=torch.float32, device=qkv.device)
+    if split is None:
+        split = CONV_PRECISION == "f16x3"
     with _lib.on(qkv.device):
-        fn = lib.zs_attention_split if CONV_PRECISION == "f16x3" else lib.zs_attention
-        _lib.check(fn(_lib.ptr(qkv), _lib.ptr(out), B, L, heads, C // heads, _stream(qkv)), "zs_attention")
+        fn = lib.zs_attention_split if split else lib.zs_attention
+        _lib.check(fn(_lib.ptr(qkv), _lib.ptr(out), B, L, heads, C // heads, _stream(qkv)),
+                   "zs_attention_split" if split else "zs_attention")
     return out
 
 
@@ -330,14 +337,8 @@ def max_pool(x, k=3, stride=2, padding=1):
     lib = _lib.load()
     _chk(x, "max_pool input")
     B, H, W, C = x.shape
-
-    def size(n):
-        if padding == "same":
-            out = -(-n // stride)
-            return out, max((out - 1) * stride + k - n, 0) // 2
-        return (n + 2 * padding - k) // stride + 1, padding
-    Ho, pt = size(H)
-    Wo, pl = size(W)
+    Ho, pt = out_size(H, k, stride, padding)
+    Wo, pl = out_size(W, k, stride, padding)
     y = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
     with _lib.on(x.device):
         _lib.check(lib.zs_max_pool_nhwc(_lib.ptr(x), _lib.ptr(y), B, H, W, C, Ho, Wo, k, stride, pt, pl, _stream(x)),
@@ -351,14 +352,8 @@ def gn_relu_max_pool(x, st, gamma, beta, k=3, stride=2, padding=1, eps=1e-5):
     lib = _lib.load()
     _chk(x, "gn_relu_max_pool input")
     B, H, W, C = x.shape
-
-    def size(n):
-        if padding == "same":
-            out = -(-n // stride)
-            return out, max((out - 1) * stride + k - n, 0) // 2
-        return (n + 2 * padding - k) // stride + 1, padding
-    Ho, pt = size(H)
-    Wo, pl = size(W)
+    Ho, pt = out_size(H, k, stride, padding)
+    Wo, pl = out_size(W, k, stride, padding)
     y = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
     table = torch.empty(B, C, 2, dtype=torch.float32, device=x.device)
     with _lib.on(x.device):

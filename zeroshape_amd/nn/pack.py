@@ -11,6 +11,15 @@ import torch
 BK, BN = 16, 128
 
 
+def out_size(n, k, stride, padding):
+    """(output length, leading pad) along one axis of input length n and kernel k; padding: int (torch symmetric zero
+    padding) or "same" (timm / TF)."""
+    if padding == "same":
+        out = -(-n // stride)
+        return out, max((out - 1) * stride + k - n, 0) // 2
+    return (n + 2 * padding - k) // stride + 1, padding
+
+
 class PackedConv:
     """Geometry + packed parameters of one convolution / linear layer."""
 
@@ -21,12 +30,7 @@ class PackedConv:
         self.padding = padding              # int (torch symmetric zero padding) or "same" (timm / TF)
 
     def out_size(self, n, k):
-        """(output length, leading pad) along one axis of input length n and kernel k."""
-        if self.padding == "same":
-            out = -(-n // self.stride)
-            total = max((out - 1) * self.stride + k - n, 0)
-            return out, total // 2
-        return (n + 2 * self.padding - k) // self.stride + 1, self.padding
+        return out_size(n, k, self.stride, self.padding)
 
     def to(self, device):
         self.w = self.w.to(device)
