@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 40
+#define ZS_ABI_VERSION 41
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -232,6 +232,17 @@ int zs_sdf_query_grid_split(const void *split_programs, size_t program_stride_by
                             const float *axis, int G, int slice_begin, int slice_end,
                             int apply_sigmoid, float *out, int *tile_flags, void *workspace,
                             void *stream);
+
+/* Block 0's point-side q/k/v as a rank-4 table (ABI 41).  Block 0's point row is point_proj(xyz), affine in (x, y, z, 1), so
+ * after LN1 all 768 q/k/v rows are rstd * (T (x, y, z, 1)) + c with T [768][4] and c [768] functions of the weights alone.
+ * Every split launch writes the tables of its images to the head of `workspace` (16 KiB per image, inside the region of the
+ * exact-fp32 kernel's slabs) with one small kernel in front of the decode kernel, which then evaluates block 0's q/k/v from
+ * them and steps over the 8 x 48 q/k/v K-blocks of block 0 in the weight stream (384 of 4,928 per wave tile).
+ * ZS_SPLIT_BLOCK0_GEMM=1 in the environment (read per launch), or a batch whose tables exceed that region (> 6,144
+ * images), selects the GEMM path for block 0 as well.
+ *   zs_sdf_block0_tables      that kernel alone: tables[batch][4096] floats = [b_proj 256][c 768][T 3,072] of each split
+ *                             program, in the kernel's register order (zeroshape_amd/program.py: block0_window) */
+int zs_sdf_block0_tables(const void *split_programs, size_t program_stride_bytes, int batch, float *tables, void *stream);
 
 /* As zs_sdf_query_grid / zs_sdf_query_grid_split, for the points [point_begin, point_end) of
  * the grid in its memory order (x slowest, z fastest): out[batch][point_end - point_begin].

@@ -5,9 +5,14 @@ The kernel's LDS-DMA statements write M0 without saving it and count their own v
   * M0 may only be touched inside ;;#ASMSTART/;;#ASMEND (hipcc must have no use of its own);
   * no scratch traffic / no private segment (a spill would also upset the counted waits);
   * every MFMA is a v_mfma_f32_32x32x16_f16 accumulating in place (the VGPR form where the
-    registers allow, -mllvm -amdgpu-mfma-vgpr-form); the dynamic count (14,784 per wave tile) is
-    in the instruction counters of profiles/;
-  * each decode kernel carries LDS-DMAs and raw barriers, and allocates all 160 KiB of LDS.
+    registers allow, -mllvm -amdgpu-mfma-vgpr-form); the dynamic count (13,632 per wave tile = 4,544
+    K-blocks since block 0's q/k/v come from a table; 14,784 = 4,928 with ZS_SPLIT_BLOCK0_GEMM=1 and in
+    the instruction counters of profiles/ up to round 6);
+  * each decode kernel carries LDS-DMAs and raw barriers, and allocates all 160 KiB of LDS;
+  * hipcc does not see the MFMAs inside the asm K-blocks, so it pads no wait states behind them: no VALU instruction (in
+    or outside asm) may read a register whose last writer is such an MFMA fewer than 12 issue slots behind it (8-pass
+    MFMA; `s_nop n` counts n + 1, every other instruction 1 - the intervening MFMA's own issue stall is not counted on).
+    The source keeps that distance structurally or with mfma_settle().
 
     python tools/check_split_isa.py            (compiles with the flags of zeroshape_amd/build.py)
 """
@@ -32,15 +37,66 @@ def compile_to_asm():
     return out
 
 
+MFMA_READ_SLOTS = 12
+
+
+def _regs(tok):
+    tok = tok.strip().rstrip(",")
+    m = re.match(r"^\|?-?([va])\[(\d+):(\d+)\]", tok)
+    if m:
+        return {(m.group(1), i) for i in range(int(m.group(2)), int(m.group(3)) + 1)}
+    m = re.match(r"^\|?-?([va])(\d+)\|?$", tok)
+    return {(m.group(1), int(m.group(2)))} if m else set()
+
+
+class _AsmMfmaReads(object):
+    """Issue-slot distance between an MFMA inside an asm statement and the next VALU read of its result."""
+
+    def __init__(self):
+        self.slot, self.last = 0, {}
+
+    def feed(self, no, l, in_asm, errors):
+        l = l.split(";")[0].strip()
+        if not l or l.endswith(":"):
+            return
+        p = l.split(None, 1)
+        op, ops = p[0], ([o.strip() for o in p[1].split(",")] if len(p) > 1 else [])
+        if op == "s_nop":
+            self.slot += int(ops[0], 0) + 1
+            return
+        self.slot += 1
+        if op.startswith("v_mfma"):
+            for r in _regs(ops[0]):
+                if in_asm:
+                    self.last[r] = self.slot
+                else:
+                    self.last.pop(r, None)      # hipcc pads behind the MFMAs it sees
+            return
+        if not op.startswith("v_"):
+            return
+        rd = set()
+        for o in ops[1:]:
+            rd |= _regs(o)
+        if op.startswith("v_fmac") and ops:
+            rd |= _regs(ops[0])
+        short = [self.slot - self.last[r] for r in rd if r in self.last and self.slot - self.last[r] < MFMA_READ_SLOTS]
+        if short:
+            errors.append("%d: VALU read %d slots behind an MFMA inside asm: %s" % (no, min(short), l))
+        for r in (_regs(ops[0]) if ops else ()):
+            self.last.pop(r, None)
+
+
 def check(path):
     errors, stats = [], {}
     kern, in_asm = None, False
+    reads = None
     for no, raw in enumerate(open(path).read().split("\n"), 1):
         l = raw.strip()
         m = re.match(r"^(_Z\w+):\s*(;.*)?$", l)
         if m and "sdf_decode_split_kernel" in m.group(1):
             kern = m.group(1)
             stats[kern] = dict(mfma=0, dma=0, barrier=0, lds=None, private=None)
+            reads = _AsmMfmaReads()
             continue
         m = re.match(r"^\.amdhsa_(group_segment_fixed_size|private_segment_fixed_size)\s+(\d+)", l)
         if m and stats:
@@ -59,6 +115,7 @@ def check(path):
         if not l or l.startswith(";") or l.startswith("."):
             continue
         st = stats[kern]
+        reads.feed(no, l, in_asm, errors)
         if re.search(r"\bm0\b", l) and not in_asm:
             errors.append("%d: compiler instruction touches m0: %s" % (no, l))
         if l.startswith("scratch_") or "buffer_store" in l and "offen" in l:

@@ -23,8 +23,8 @@ ws = net.workspace(dev)
 tail = ws[-1024:].view(torch.int64).cpu().numpy()[:16]
 names = ["init", "point_proj", "b0 LN1", "b0 heads", "b0 LN2", "b0 MLP", "b1 LN1", "b1 heads", "b1 LN2", "b1 MLP",
          "final LN", "impl L0", "impl Z", "impl L1", "impl pairs", "drain"]
-kb = {3: 8 * 92, 5: 1024, 7: 8 * 92, 9: 1024, 11: 128, 12: 384, 13: 128, 14: 768}   # K-blocks (x 96 cycles)
+kb = {3: 8 * 44, 5: 1024, 7: 8 * 92, 9: 1024, 11: 128, 12: 384, 13: 128, 14: 768}   # K-blocks (x 96 cycles); block 0's heads: 44 each, q/k/v come from the table
 for i in range(1, 16):
     d = int(tail[i] - tail[i - 1])
     print("%-12s %9d ticks   MFMA cycles %s" % (names[i], d, kb[i] * 96 if i in kb else ""))
-print("total", int(tail[15] - tail[0]), " MFMA", 4928 * 96)
+print("total", int(tail[15] - tail[0]), " MFMA", 4544 * 96)   # 13,632 MFMAs per wave tile (4,928 K-blocks with ZS_SPLIT_BLOCK0_GEMM=1)

@@ -58,6 +58,7 @@ SIGNATURES = {
     "zs_attn_frames": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_int,
                                 _c_void_p, _c_void_p]),
     "zs_sdf_split_programs": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_void_p]),
+    "zs_sdf_block0_tables": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p]),
     "zs_sdf_query_points_split": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int,
                                            _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_sdf_query_grid_split": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int, _c_int,
@@ -218,7 +219,7 @@ SIGNATURES = {
     "zs_readout_concat_bwd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
 }
 
-ABI_VERSION = 40
+ABI_VERSION = 41
 _lib = None
 
 

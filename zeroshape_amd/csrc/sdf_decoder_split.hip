@@ -175,8 +175,8 @@ struct AStream {
     u32x4 hi, lo;             // A operand of the next K-block (read in flight)
     const char *gsrc;         // this lane's source of this wave's K-blocks of the next chunk to stage
 
-    DEV void init(const char *prog, u32x4 *stage, unsigned stage_addr, int wave, int lane) {
-        const char *g = prog + wave * (KPW * KB_U4 * 16) + lane * 16;
+    DEV void init(const char *prog, u32x4 *stage, unsigned stage_addr, int wave, int lane, int first_byte = 0) {
+        const char *g = prog + first_byte + wave * (KPW * KB_U4 * 16) + lane * 16;
         // the previous tile's reads and DMAs are retired in every wave before the buffers are reused
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
@@ -221,6 +221,22 @@ struct AStream {
 #endif
         }
     }
+    // Step over `bytes` of the program: this wave's NEXT staged chunk comes from that much further on.  Only gsrc moves -
+    // nothing is in flight to it - so the buffers, the barriers and the counted waits are untouched.  Used by block 0 when
+    // its q/k/v come from the table (BLOCK 0 TABLE below) to pass the 48 q/k/v K-blocks = 6 whole chunks in front of every
+    // head; the stream starts 6 chunks in (init) and a head then consumes 44 K-blocks, so heads still alternate between
+    // chunk positions 0 and 4.  The pos-7 step of chunk n stages chunk n + 2, which fixes where head hd (hd < 7) bumps:
+    //  * P = 4 heads: the proj K-blocks fill two whole chunks and the next head starts on a chunk boundary.  Every wave
+    //    bumps BEFORE the proj loop: behind the attention's last pos-7 step, in front of the pos-7 step of proj tile 3, which
+    //    stages the next head's first chunk.
+    //  * P = 0 heads: proj takes pos 4-7 of one chunk, a whole chunk and pos 0-3 of a third, whose pos 4-7 are the next
+    //    head's first K-blocks (a MIXED chunk, staged by the pos-7 step of proj tile 1).  Waves 2 and 3 stage pos 4-7: they
+    //    bump BEFORE the proj loop.  Waves 0 and 1 stage pos 0-3: they bump in front of proj tile 2 - the mixed chunk is
+    //    staged, the next one (pos-7 step of proj tile 5) not yet.
+    //  * head 7 bumps nothing: block 0's MLP section follows it directly.
+    // Block 0 so consumes program K-blocks 92 h + 48 .. 92 h + 91 for h = 0..7, then 736 on (program.split_consumed_kblocks;
+    // tests/test_block0_tables.py replays this schedule wave by wave).
+    DEV void skip(int bytes) { gsrc += bytes; }
     DEV void drain() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 };
 
@@ -402,6 +418,16 @@ DEV float kblock_softplus(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const
                  : [alo] "v"(alo), [ahi] "v"(ahi), [bh] "v"(bhi), [bl] "v"(blo), [x] "v"(x), [c0] "s"(c0));
     return m;
 }
+
+// The asm K-blocks hide their MFMAs from hipcc, which therefore pads no wait states between the last of them and a VALU
+// read of the accumulator (the result of an 8-pass MFMA may be read 12 wait states after its issue; hipcc placed such a
+// read 4 behind it).  Called in front of every VALU read of a tile that follows the asm GEMM that produced it by fewer
+// instructions than that: the plain-C++ activation of the last output tile of each impl_mlp layer, and in the skip layers
+// every hand-over of tile nt to the activation carried by tile nt + 1's first K-block (only three LDS reads, a wait and one
+// independent MFMA lie between).  Everywhere else the distance is structural: the hand-overs of the plain layers and of
+// layer 0 have the previous K-block's own tail (7+ VALU instructions behind its last MFMA, inside the same asm statement)
+// plus the next step's reads in front of the read; the MLP's GELU hand-over has 16 K-blocks of fc2 in between.
+DEV void mfma_settle(f32x16 &acc) { asm volatile("s_nop 7\n\ts_nop 3" : "+v"(acc)); }
 
 // acc += W_tile X, X = KT packed tiles in registers; starts at a chunk boundary.
 // SIDE: side(kb, g) runs behind the g-th MFMA of K-block kb
@@ -610,6 +636,25 @@ DEV f32x16 rp16(const float *prm, int off, int tile, int hi) {
     for (int r = 0; r < 16; r++) v[r] = t[r];
     return v;
 }
+// BLOCK 0 TABLE.  Block 0's point row is pf = point_proj(xyz) = A p~ with p~ = (x, y, z, 1), so
+//     LN1(pf) = rstd g (A - 1 m) p~ + b          (m: column mean of A; rstd: the point's scalar from ln_stats)
+//     qkv     = rstd (T p~) + c,   T = Wqkv diag(g) (A - 1 m)  [768 x 4],   c = Wqkv b + bqkv
+// for all 768 q/k/v rows of block 0.  T and c depend on the weights only (block0_window_kernel writes them in front of every
+// launch), so block 0 needs neither its LN1 -> pack -> slab pass nor its 8 x 48 q/k/v K-blocks (384 of 4,928 per wave tile).
+// Window layout (floats; one load_params): [b_proj 256][c 768, row-param order][T 3,072, [tile][hi][r][4]], tile = 3 head + {q, k, v}.
+constexpr int B0_BPROJ = 0, B0_C = 256, B0_T = 1024;
+static_assert(B0_T + HEADS * 3 * 128 == PRM_WINDOW, "the block-0 table is exactly one params window");
+// xr, yr, zr = (x, y, z) * rstd
+DEV f32x16 block0_qkv(const float *prm, int tile, int hi, float xr, float yr, float zr, float rstd) {
+    f32x16 v = rp16(prm, B0_C, tile, hi);
+    const f32x4 *q = reinterpret_cast<const f32x4 *>(prm + B0_T + tile * 128 + hi * 64);
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const f32x4 w = q[r];
+        v[r] = fmaf(w.z, zr, fmaf(w.y, yr, fmaf(w.x, xr, fmaf(w.w, rstd, v[r]))));
+    }
+    return v;
+}
 // w.w + w.x*x + w.y*y + w.z*z for the 16 registers of (tile, hi): [tile][hi][r][4] table
 DEV f32x16 xyz_affine(const float *prm, int off, int tile, int hi, float x, float y, float z) {
     const f32x4 *q = reinterpret_cast<const f32x4 *>(prm + off + tile * 128 + hi * 64);
@@ -750,13 +795,16 @@ DEV void attn_tile(AStream &s, const PT &q, f32x16 &o, float &m_run, float &z_ru
 #define ZS_STAMP(i) do { } while (0)
 #endif
 // One wave: 32 points (lane & 31; both lane halves carry the same point).
+// tbl: this image's block-0 table (BLOCK 0 TABLE above; wave-uniform), or null: block 0 runs its q/k/v GEMMs like block 1
 DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage_addr, u32x4 *slab,
-                      f32x4 *zs, float px, float py, float pz, int wave, int lane, float &guard,
+                      const float *tbl, float px, float py, float pz, int wave, int lane, float &guard,
                       unsigned long long *dbg) {
     const int hi = lane >> 5;
     const float *prog_params = reinterpret_cast<const float *>(prog) + REC_FLOATS;
+    constexpr int QKV_BYTES = 3 * NT * 2 / CK * CHUNK_BYTES;   // q/k/v K-blocks of a head: 6 whole chunks
+    static_assert(3 * NT * 2 % CK == 0, "AStream::skip passes whole chunks");
     AStream s;
-    s.init(prog, stage, stage_addr, wave, lane);
+    s.init(prog, stage, stage_addr, wave, lane, tbl ? QKV_BYTES : 0);   // head 0's q/k/v are the first six chunks
     Slab sl;
     sl.fl = slab;
     ZS_STAMP(0);
@@ -773,23 +821,42 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
 
 #pragma unroll 1
     for (int blk = 0; blk < BLOCKS; blk++) {
-        load_params(prm, prog_params, W_BLK + blk * P_BLK_STRIDE, P_BLK_STRIDE);
-        layer_norm_lds(y, sl, prm, PB_LN1G, PB_LN1B, hi);
+        const bool tab = blk == 0 && tbl != nullptr;   // wave-uniform
+        float rstd0 = 0.f, xr = 0.f, yr = 0.f, zr = 0.f;
+        if (tab) {
+            // the table window instead of the block window (which returns behind the heads): LN1's output is not needed
+            load_params(prm, tbl, 0, PRM_WINDOW);
+            float mean;
+            ln_stats(y, mean, rstd0);
+            xr = px * rstd0;
+            yr = py * rstd0;
+            zr = pz * rstd0;
+        } else {
+            load_params(prm, prog_params, W_BLK + blk * P_BLK_STRIDE, P_BLK_STRIDE);
+            layer_norm_lds(y, sl, prm, PB_LN1G, PB_LN1B, hi);
+        }
         ZS_STAMP(2 + blk * 4);
         // y = x + proj_bias + sum_heads Wproj_h o_h
 #pragma unroll
-        for (int nt = 0; nt < NT; nt++) y[nt] += rp16(prm, PB_BPROJ, nt, hi);
+        for (int nt = 0; nt < NT; nt++) y[nt] += rp16(prm, tab ? B0_BPROJ : PB_BPROJ, nt, hi);
 
         // one head: 48 (q, k, v) + 28 (7 latent tiles) + 16 (proj) = 92 K-blocks = 11.5 chunks, so
         // heads alternate between chunk positions 0 and 4 (P); all positions are compile-time
         auto head = [&](int hd, auto Ptag) {
             constexpr int P = decltype(Ptag)::value;
-            f32x16 q = rp16(prm, PB_BQKV, hd * 3 + 0, hi);
-            gemm_lds(s, sl, q, P);
-            f32x16 k = rp16(prm, PB_BQKV, hd * 3 + 1, hi);
-            gemm_lds(s, sl, k, P);
-            f32x16 v = rp16(prm, PB_BQKV, hd * 3 + 2, hi);
-            gemm_lds(s, sl, v, P);
+            f32x16 q, k, v;
+            if (tab) {
+                q = block0_qkv(prm, hd * 3 + 0, hi, xr, yr, zr, rstd0);
+                k = block0_qkv(prm, hd * 3 + 1, hi, xr, yr, zr, rstd0);
+                v = block0_qkv(prm, hd * 3 + 2, hi, xr, yr, zr, rstd0);
+            } else {
+                q = rp16(prm, PB_BQKV, hd * 3 + 0, hi);
+                gemm_lds(s, sl, q, P);
+                k = rp16(prm, PB_BQKV, hd * 3 + 1, hi);
+                gemm_lds(s, sl, k, P);
+                v = rp16(prm, PB_BQKV, hd * 3 + 2, hi);
+                gemm_lds(s, sl, v, P);
+            }
 
             // logits are kept in the log2 domain: c = d^-1/2 * log2(e), softmax = 2^(c s - m)
             const float c = scale * 1.44269504088896340736f;
@@ -827,8 +894,14 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
             }
             // y += Wproj[:, head] o_h
             const PT op = pack_tile(o);
+            // the next head's q/k/v K-blocks are not consumed: AStream::skip has the bump points
+            const bool bump = tab && hd + 1 < HEADS;   // wave-uniform
+            if (bump && (P == 4 || wave >= 2)) s.skip(QKV_BYTES);
 #pragma unroll
-            for (int nt = 0; nt < NT; nt++) gemm_one(s, op, y[nt], (P + 4 + 2 * nt) & (CK - 1));
+            for (int nt = 0; nt < NT; nt++) {
+                if (P == 0 && nt == 2 && bump && wave < 2) s.skip(QKV_BYTES);
+                gemm_one(s, op, y[nt], (P + 4 + 2 * nt) & (CK - 1));
+            }
         };
         static_assert((LT - 1) % 2 == 0 && (3 * NT * 2 + LT * 4 + NT * 2) % CK == 4, "head = 11.5 chunks");
 #pragma unroll 1
@@ -838,6 +911,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
         }
 
         ZS_STAMP(3 + blk * 4);
+        if (tab) load_params(prm, prog_params, W_BLK, P_BLK_STRIDE);   // block 0's own window, for LN2 and the MLP
         // MLP (timm Mlp): y += b2 + W2 gelu(W1 LN2(y) + b1), one hidden tile at a time
         layer_norm_lds(y, sl, prm, PB_LN2G, PB_LN2B, hi);
 #pragma unroll
@@ -912,6 +986,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                 if (nt > 0) sl.store(nt - 1, e.p);
                 prev = acc;
             } else {
+                mfma_settle(prev);
 #pragma unroll
                 for (int kb = 0; kb < 16; kb++) e.feed(kb, softplus100(prev[kb]));
                 sl.store(nt - 1, e.p);
@@ -955,6 +1030,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                 if (nt > 0) hp[nt - 1] = e.p;
                 prev = acc;
             } else {
+                mfma_settle(prev);
 #pragma unroll
                 for (int kb = 0; kb < 16; kb++) e.feed(kb, softplus100(prev[kb]) * rsqrt2);
                 hp[nt - 1] = e.p;
@@ -975,6 +1051,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
 #pragma unroll
             for (int nt = 0; nt <= NT; nt++) {
                 TilePacker e;
+                if (nt > 0) mfma_settle(prev);   // prev's last MFMA (gemm_areg) is a few instructions back
                 if (nt < NT) {
                     f32x16 acc = ini.v;
                     if (nt + 1 < NT) ini.start(prm, pp, nt + 1, hi);
@@ -1032,6 +1109,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                     if (nt > 0) hp[nt - 1] = e.p;
                     prev = acc;
                 } else {
+                    mfma_settle(prev);
 #pragma unroll
                     for (int kb = 0; kb < 16; kb++) finish(kb, softplus100(prev[kb]));
                     hp[nt - 1] = e.p;
@@ -1055,7 +1133,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
     int m,                             // points per image handled by this launch
     float *__restrict__ out, int apply_sigmoid, f32x4 *__restrict__ workspace,
     int *__restrict__ tile_flags,    // [tiles] zeroed by the caller, or null
-    int static_order) {              // 1: tile += gridDim.x, no counter (ZS_SPLIT_STATIC_TILES=1: the A/B arm of tools/ab_tile_order.py)
+    int static_order,                // 1: tile += gridDim.x, no counter (ZS_SPLIT_STATIC_TILES=1: the A/B arm of tools/ab_tile_order.py)
+    const float *__restrict__ block0_tables) {   // [batch][PRM_WINDOW] (block0_window_kernel), or null: block 0 runs its q/k/v GEMMs
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     float *prm = lds;
     const int lane = threadIdx.x & 63;
@@ -1064,7 +1143,6 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
     const unsigned stage_addr = __builtin_amdgcn_readfirstlane(
         (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)(lds + PRM_WINDOW));
     u32x4 *fl = reinterpret_cast<u32x4 *>(lds + PRM_WINDOW + STAGE_FLOATS) + wave * SLAB_U4 + lane;
-    f32x4 *zslab = workspace + ((size_t)blockIdx.x * WAVES + wave) * ZSLAB_F4 + lane;
 
     const int tiles_per_img = (m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK;
     const int total = tiles_per_img * batch;
@@ -1115,7 +1193,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
         unsigned long long *dbg = nullptr;
 #endif
         float guard = 0.f;
-        float logit = decode_tile(prog, prm, stage, stage_addr, fl, zslab, px, py, pz, wave, lane, guard, dbg);
+        const float *tbl = block0_tables ? block0_tables + (size_t)img * PRM_WINDOW : nullptr;
+        float logit = decode_tile(prog, prm, stage, stage_addr, fl, tbl, px, py, pz, wave, lane, guard, dbg);
         if (apply_sigmoid) logit = 1.0f / (1.0f + expf(-logit));
         // ENVELOPE (zeroshape_amd/program.py, S_GUARD): outside it the tile is flagged for the
         // exact-fp32 kernel, and a program with non-finite / out-of-range operands yields NaN like
@@ -1254,6 +1333,94 @@ __global__ __launch_bounds__(256) void k_bound_kernel(const float *__restrict__ 
         reinterpret_cast<float *>(dst + (size_t)img * dst_stride_u4)[REC_FLOATS + P_KMAX + bh] = sqrtf(red[0]);
 }
 
+// BLOCK 0 TABLE of every image, from its SPLIT program (the launchers hold nothing else): weights are hi + lo of block 0's
+// q/k/v K-blocks, g / b / A / the biases come from the params section; sums in double, rounded once.  One workgroup of four
+// waves per (image, tile = 3 head + {q, k, v}): wave w takes K-blocks 4 w .. 4 w + 3 of the tile's 16, lane l of it owns
+// output row l & 31 and the 8 input features per K-block its lane half holds in the records (K-block 2 kt + j, element e:
+// feature 32 kt + row(8 j + e, l >> 5), which is position 32 kt + 16 (l >> 5) + 8 j + e of a row-param vector); the eight
+// partial sums of a row meet through LDS in a fixed order.  Non-finite operands just propagate (P_FLAG turns such an image
+// into NaN anyway).
+constexpr int B0_THREADS = 256;
+__global__ __launch_bounds__(B0_THREADS) void block0_window_kernel(const char *__restrict__ programs,
+                                                                   size_t program_stride_bytes, float *__restrict__ tables) {
+    __shared__ double red[B0_THREADS][5];
+    __shared__ double msum[64][4];
+    const int tile = blockIdx.x, img = blockIdx.y, t = threadIdx.x, wave = t >> 6, lane = t & 63, hl = lane >> 5;
+    const char *prog = programs + (size_t)img * program_stride_bytes;
+    const float *par = reinterpret_cast<const float *>(prog) + REC_FLOATS;
+    float *out = tables + (size_t)img * PRM_WINDOW;
+    // m = column mean of A (point_proj: one (w0, w1, w2, b) quad per feature): 64 partial sums of 4 features, then all of them
+    if (t < 64) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            double a = 0.0;
+#pragma unroll
+            for (int f = 0; f < 4; f++) a += (double)par[P_PP + (4 * t + f) * 4 + d];
+            msum[t][d] = a;
+        }
+    }
+    __syncthreads();
+    double m[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < 64; i++)
+#pragma unroll
+        for (int d = 0; d < 4; d++) m[d] += msum[i][d];
+#pragma unroll
+    for (int d = 0; d < 4; d++) m[d] *= 1.0 / C;
+    const int head = tile / 3, part = tile - head * 3;
+    const u32x4 *kb0 = reinterpret_cast<const u32x4 *>(prog) + (size_t)(head * (G_HEAD / 2) + part * 2 * NT) * KB_U4;
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // T[.][0..3], W b
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int kb = 4 * wave + k;
+        const u32x4 h4 = kb0[kb * KB_U4 + lane], l4 = kb0[kb * KB_U4 + 64 + lane];
+        const int f0 = (kb >> 1) * 32 + hl * 16 + (kb & 1) * 8;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            const unsigned hw = h4[e >> 1] >> (16 * (e & 1)), lw = l4[e >> 1] >> (16 * (e & 1));
+            const double w = (double)(float)__builtin_bit_cast(_Float16, (unsigned short)hw) +
+                             (double)(float)__builtin_bit_cast(_Float16, (unsigned short)lw);
+            const double wg = w * (double)par[P_BLK0 + PB_LN1G + f0 + e];
+#pragma unroll
+            for (int d = 0; d < 4; d++) acc[d] += wg * ((double)par[P_PP + (f0 + e) * 4 + d] - m[d]);
+            acc[4] += w * (double)par[P_BLK0 + PB_LN1B + f0 + e];
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 5; d++) red[t][d] = acc[d];
+    __syncthreads();
+    if (t < 32) {
+        // output row t of the tile sits in register r of lane half hh with row(r, hh) = t
+        const int hh = (t >> 2) & 1, r = (t & 3) + 4 * (t >> 3), o = tile * 32 + hh * 16 + r;
+        double sum[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int w = 0; w < B0_THREADS / 64; w++)
+#pragma unroll
+            for (int d = 0; d < 5; d++) sum[d] += red[w * 64 + t][d] + red[w * 64 + 32 + t][d];
+#pragma unroll
+        for (int d = 0; d < 4; d++) out[B0_T + o * 4 + d] = (float)sum[d];
+        out[B0_C + o] = (float)(sum[4] + (double)par[P_BLK0 + PB_BQKV + o]);
+    }
+    if (tile < C / 32 && t < 32) out[B0_BPROJ + tile * 32 + t] = par[P_BLK0 + PB_BPROJ + tile * 32 + t];
+}
+
+// in front of every split launch: the block-0 tables of the launch's images -> the head of `workspace`, img * 16 KiB.  That
+// region (96 MiB) is the exact-fp32 kernel's per-wave slabs, which the split kernel never touches; the fp32 re-evaluation
+// that may follow on the stream overwrites it, and the next split launch writes it again.  The tables depend on the weights
+// only and could be computed once per weight version, but the program's bytes are pinned (tests compare them with the host
+// mirror word for word) and the entry points keep their signatures, so there is nowhere to keep them: 24 small workgroups per image
+// per launch (microseconds) against ~8 % of the decode launch.  A plain kernel launch: capturable.
+// -> the kernel's block0_tables argument; null (block 0 runs its q/k/v GEMMs) when the tables do not fit the slab region or
+// ZS_SPLIT_BLOCK0_GEMM=1 (read per launch: the A/B arm of tools/ab_block0_tables.py)
+const float *launch_block0_tables(const void *split_programs, size_t program_stride_bytes, int batch, void *workspace,
+                                  hipStream_t st) {
+    const char *e = getenv("ZS_SPLIT_BLOCK0_GEMM");
+    if (e && atoi(e) != 0) return nullptr;
+    if ((size_t)batch * PRM_WINDOW * sizeof(float) > (size_t)MAX_WGS * WAVES * ZSLAB_F4 * sizeof(f32x4)) return nullptr;
+    float *tables = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(block0_window_kernel, dim3(HEADS * 3, batch), dim3(B0_THREADS), 0, st,
+                       static_cast<const char *>(split_programs), program_stride_bytes, tables);
+    return tables;
+}
+
 int decode_grid_size(int batch, int m) {
     const long long tiles = (long long)batch * ((m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK);
     return (int)(tiles < MAX_WGS ? tiles : MAX_WGS);
@@ -1300,6 +1467,23 @@ extern "C" int zs_sdf_split_programs(const void *programs, size_t program_stride
     return zs::check_launch("zs_sdf_split_programs") ? 1 : 0;
 }
 
+extern "C" int zs_sdf_block0_tables(const void *split_programs, size_t program_stride_bytes, int batch, float *tables,
+                                    void *stream) {
+    if (batch < 0 || batch > 65535) {
+        zs::set_err("zs_sdf_block0_tables: bad batch %d", batch);
+        return 0;
+    }
+    if (batch == 0) return 1;
+    if (!tables) {
+        zs::set_err("zs_sdf_block0_tables: null pointer");
+        return 0;
+    }
+    if (!check_programs("zs_sdf_block0_tables", split_programs, program_stride_bytes)) return 0;
+    hipLaunchKernelGGL(block0_window_kernel, dim3(HEADS * 3, batch), dim3(B0_THREADS), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const char *>(split_programs), program_stride_bytes, tables);
+    return zs::check_launch("zs_sdf_block0_tables") ? 1 : 0;
+}
+
 // in front of every split launch: the dynamic tile order's counter (1 KiB into the workspace tail) starts at zero whatever
 // the caller's workspace held (a memset node when the stream is being captured); -> static_order of the launch
 static int launch_counter_reset(void *workspace, hipStream_t st) {
@@ -1328,10 +1512,11 @@ extern "C" int zs_sdf_query_points_split(const void *split_programs, size_t prog
         return 0;
     }
     const int static_order = launch_counter_reset(workspace, static_cast<hipStream_t>(stream));
+    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL((sdf_decode_split_kernel<false>), dim3(decode_grid_size(batch, m)),
                        dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char *>(split_programs), program_stride_bytes, batch, points,
-                       nullptr, 0, 0LL, m, logits, 0, static_cast<f32x4 *>(workspace), tile_flags, static_order);
+                       nullptr, 0, 0LL, m, logits, 0, static_cast<f32x4 *>(workspace), tile_flags, static_order, b0_tables);
     return zs::check_launch("zs_sdf_query_points_split") ? 1 : 0;
 }
 
@@ -1358,10 +1543,11 @@ extern "C" int zs_sdf_query_grid_range_split(const void *split_programs, size_t 
     if (!check_programs("zs_sdf_query_grid_range_split", split_programs, program_stride_bytes)) return 0;
     const int m = (int)mm;
     const int static_order = launch_counter_reset(workspace, static_cast<hipStream_t>(stream));
+    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL((sdf_decode_split_kernel<true>), dim3(decode_grid_size(batch, m)),
                        dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char *>(split_programs), program_stride_bytes, batch, nullptr,
-                       axis, G, point_begin, m, out, apply_sigmoid, static_cast<f32x4 *>(workspace), tile_flags, static_order);
+                       axis, G, point_begin, m, out, apply_sigmoid, static_cast<f32x4 *>(workspace), tile_flags, static_order, b0_tables);
     return zs::check_launch("zs_sdf_query_grid_range_split") ? 1 : 0;
 }
 
@@ -1387,10 +1573,11 @@ extern "C" int zs_sdf_query_grid_split(const void *split_programs, size_t progra
     if (!check_programs("zs_sdf_query_grid_split", split_programs, program_stride_bytes)) return 0;
     const int m = (int)mm;
     const int static_order = launch_counter_reset(workspace, static_cast<hipStream_t>(stream));
+    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL((sdf_decode_split_kernel<true>), dim3(decode_grid_size(batch, m)),
                        dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char *>(split_programs), program_stride_bytes, batch, nullptr,
                        axis, G, (long long)slice_begin * G * G, m, out, apply_sigmoid,
-                       static_cast<f32x4 *>(workspace), tile_flags, static_order);
+                       static_cast<f32x4 *>(workspace), tile_flags, static_order, b0_tables);
     return zs::check_launch("zs_sdf_query_grid_split") ? 1 : 0;
 }

@@ -473,3 +473,89 @@ def latent_k_bounds(prog):
             row = sq[:, :32] + sq[:, 32:]                                              # lanes l, l + 32: the two halves
             out[blk, h] = np.sqrt(row.max())
     return out
+
+
+# ----------------------------------------------------------------------------- #
+# block 0's point-side q/k/v as a rank-4 table (csrc/sdf_decoder_split.hip: block0_window_kernel)
+# ----------------------------------------------------------------------------- #
+# Block 0's point row is pf = point_proj(xyz) = A p~, p~ = (x, y, z, 1), so LN1(pf) = rstd * g (A - 1 m) p~ + b with m the
+# column mean of A and rstd the per-point scalar, and for the 768 rows of block 0's qkv
+#     qkv = rstd * (T p~) + c,    T = Wqkv diag(g) (A - 1 m)  [768 x 4],    c = Wqkv b + bqkv.
+# The split kernel reads T and c from a 4,096-float window instead of running the three 256 -> 256 GEMMs per head, and
+# steps over their 48 K-blocks per head in the weight stream (which keep their place in the program).
+B0_WINDOW_FLOATS = 4096
+B0_BPROJ, B0_C, B0_T = 0, C, C + HEADS * 96      # [b_proj 256][c 768: row-param order][T 3072: [tile][hi][r][4]]
+KB_HEAD = G_HEAD // 2                            # 92 K-blocks per head: 48 q/k/v, 28 latent K/V, 16 proj
+KB_QKV_HEAD = G_QKV_HEAD // 2                    # 48
+
+
+def _kblock_values(words, kb):
+    """K-block `kb` of a split program (uint32 words) as float64 [lane][8]: hi + lo."""
+    h = np.ascontiguousarray(words[kb * KB_WORDS:(kb + 1) * KB_WORDS]).view(np.float16).reshape(2, 64, 8)
+    return h[0].astype(np.float64) + h[1].astype(np.float64)
+
+
+def block0_qkv_weights(split_prog):
+    """Block 0's qkv weight [768, 256] (rows in the order of attn.qkv.weight) as the split program holds it: hi + lo, float64."""
+    W = np.zeros((3 * C, C), np.float64)
+    for h in range(HEADS):
+        for part in range(3):
+            for kt in range(NT):
+                for j in range(2):
+                    v = _kblock_values(split_prog, h * KB_HEAD + part * 2 * NT + kt * 2 + j)       # [lane][e]: record 8 j + e
+                    rows = part * C + h * HD + LANE_I                                              # [64]
+                    cols = 32 * kt + ROW_TABLE[LANE_HI][:, 8 * j:8 * j + 8]                        # [64, 8]
+                    W[rows[:, None], cols] = v
+    return W
+
+
+def _from_rowparam(v):
+    """Inverse of rowparam: [T][hi][r] order -> feature order."""
+    v = np.asarray(v)
+    T = v.shape[0] // 32
+    idx = ((32 * np.arange(T))[:, None, None] + ROW_TABLE[None, :, :]).reshape(-1)
+    out = np.empty_like(v)
+    out[idx] = v
+    return out
+
+
+def block0_window(split_prog):
+    """The 4,096 floats the split kernel reads for block 0 in place of its LN1 / q, k, v GEMMs, from one SPLIT program
+    (uint32 words, split_program()): [b_proj | c | T] as laid out above, computed in float64 and rounded once to float32 -
+    host mirror of zs_sdf_block0_tables."""
+    words = np.ascontiguousarray(split_prog).view(np.uint32)
+    params = words[REC_FLOATS:].view(np.float32).astype(np.float64)
+    d = PARAMS.blk[0]
+    A = np.stack([_from_rowparam(params[PARAMS.PP + i:PARAMS.PP + 4 * C:4]) for i in range(4)], axis=1)   # [256, 4]: w0 w1 w2 b
+    g = _from_rowparam(params[d["ln1_g"]:d["ln1_g"] + C])
+    b = _from_rowparam(params[d["ln1_b"]:d["ln1_b"] + C])
+    W = block0_qkv_weights(words)
+    T = W @ (g[:, None] * (A - A.mean(axis=0, keepdims=True)))                                       # [768, 4]
+    c = W @ b                                                                                         # + bqkv below (row-param)
+    out = np.zeros(B0_WINDOW_FLOATS, np.float64)
+    out[B0_BPROJ:B0_BPROJ + C] = params[d["bproj"]:d["bproj"] + C]
+    for h in range(HEADS):
+        for part in range(3):
+            tile = 3 * h + part
+            rows = slice(part * C + h * HD, part * C + (h + 1) * HD)
+            out[B0_C + tile * 32:B0_C + (tile + 1) * 32] = \
+                _rowparam64(c[rows]) + params[d["bqkv"] + tile * 32:d["bqkv"] + (tile + 1) * 32]
+            out[B0_T + tile * 128:B0_T + (tile + 1) * 128] = \
+                np.stack([_rowparam64(T[rows, i]) for i in range(4)], axis=-1).reshape(-1)
+    return out.astype(np.float32)
+
+
+def _rowparam64(v):
+    """rowparam without the float32 rounding."""
+    v = np.asarray(v, np.float64)
+    T = v.shape[0] // 32
+    idx = (32 * np.arange(T))[:, None, None] + ROW_TABLE[None, :, :]
+    return v[idx].reshape(-1)
+
+
+def split_consumed_kblocks():
+    """K-blocks of the SPLIT program (its own stream order: the positions the weight stream's DMAs read from) in the order
+    the split kernel consumes them when block 0's q/k/v come from the table: everything but the 48 q/k/v K-blocks in front of
+    each of block 0's eight heads - head h keeps 92 h + 48 .. 92 h + 91, the MLP section follows from 736 on (4,544 in all)."""
+    keep = [kb for kb in range(KB_TOTAL) if not (kb < HEADS * KB_HEAD and kb % KB_HEAD < KB_QKV_HEAD)]
+    return np.array(keep)
