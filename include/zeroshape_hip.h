@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 41
+#define ZS_ABI_VERSION 42
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -529,11 +529,10 @@ int zs_depth_metrics(const float *prediction, const float *target, const float *
                                K = 16 MFMAs per eight fp32 ones; inference */
 #define ZS_CONV_SPLIT_SMALL 32 /* with a workspace: small-tile layers that would leave most CUs idle split K across
                                * workgroups (partial sums in the workspace, fixed-order reduction kernel) */
-#define ZS_CONV_STREAM_K 64   /* with a workspace: 128x128-tile layers run as a fixed number of workgroups that share the
-                               * (tile, k-step) iteration space evenly; shared tiles are summed in k order by the
-                               * workgroup that arrives last (deterministic) */
-#define ZS_CONV_STREAM_K_ALWAYS 256 /* tests / tuning: with ZS_CONV_STREAM_K, stream-K wherever the kernels support it (by
-                                     * default only where it was measured to pay: see csrc/nn_conv.hip) */
+/* Bits 64 and 256 are RETIRED (they selected the stream-K kernels, removed in ABI 42: DESIGN.md section 9.1).  Do not reuse
+ * them: zs_conv2d_nhwc, zs_conv2d_nhwc_ws and zs_conv2d_nhwc_fused refuse a call that sets either (return 0, zs_last_error). */
+#define ZS_CONV_RETIRED_64 64
+#define ZS_CONV_RETIRED_256 256
 #define ZS_CONV_W_PRESPLIT 128 /* with ZS_CONV_F16X3: packed_w is the output of zs_conv2d_presplit_weight (the weights'
                                * fp16 halves, same size and indexing as the fp32 packing) - no operand split of the
                                * weights at run time */
@@ -565,14 +564,15 @@ int zs_conv2d_nhwc(const float *in, const float *packed_w, const float *scale, c
                    int Hout, int Wout, int Cout, int kh, int kw, int stride, int pad_t, int pad_l, int flags,
                    float in_scale, float in_shift, int act, void *stream);
 /* As zs_conv2d_nhwc, with a workspace of zs_conv2d_splitk_workspace_bytes() bytes (16-byte aligned, ZEROED ONCE by
- * the caller when allocated - its first 1 MiB are arrival counters the kernels leave at zero - and used by one
- * stream at a time; NULL = zs_conv2d_nhwc).  What uses it is chosen by the flags: ZS_CONV_SPLIT_SMALL (problems
- * that would launch fewer than 256 small-tile workgroups - 14x14 feature maps, 197-token matrices at small
- * batch - split K across workgroups; a second kernel sums the partial tiles in split order and applies the
- * fused epilogue) and ZS_CONV_STREAM_K (128x128-tile problems; see above).  Independently of those flags, with
- * ZS_CONV_F16X3 | ZS_CONV_W_PRESPLIT a workspace lets two more paths split the contraction across workgroups the same
- * way (partial tiles, summed in order): 3x3 stride-1 layers of 64..191 input-patch workgroups (nn_conv_patch.h) and
- * layers of 40..191 tiles with >= 96 k-steps on the LDS-DMA kernel.  All of it is deterministic. */
+ * the caller when allocated - its first 1 MiB are the streaming kernel's tickets, which the kernels leave at zero - and
+ * used by one stream at a time; NULL = zs_conv2d_nhwc).  It holds the partial results of a contraction split across
+ * workgroups, which a second kernel (or the last workgroup of a tile) sums in range order before the fused epilogue.  One
+ * flag asks for such a split: ZS_CONV_SPLIT_SMALL (problems that would launch fewer than 256 small-tile workgroups - 14x14
+ * feature maps, 197-token matrices at small batch).  Independently of it a workspace lets these paths split by the layer's
+ * shape: small-tile layers with K >= 2048 on <= 64 workgroups; and, with ZS_CONV_F16X3 | ZS_CONV_W_PRESPLIT, 3x3 stride-1
+ * layers of 32..191 input-patch workgroups (nn_conv_patch.h), layers of 40..191 tiles with >= 96 k-steps on the LDS-DMA
+ * kernel, the last partial round of the 256 x 256 tiles (nn_conv_pp256.h) and pointwise layers of few rows (the streaming
+ * kernel).  With a workspace the large-tile kernels also start at 96 instead of 192 tiles.  All of it is deterministic. */
 size_t zs_conv2d_splitk_workspace_bytes(void);
 int zs_conv2d_nhwc_ws(const float *in, const float *packed_w, const float *scale, const float *shift,
                    const float *res1, const float *res2, float *out, int batch, int Hin, int Win, int Cin,

@@ -67,6 +67,14 @@ def test_python_constants_equal_the_header():
 
 
 def test_argument_errors_are_reported_without_touching_the_gpu(lib):
+    from zeroshape_amd import _lib
+    # the retired convolution flag bits (64, 256: the removed stream-K kernels) fail loudly at all three entry points
+    conv = [None] * 7 + [1, 8, 8, 16, 8, 8, 16, 1, 1, 1, 0, 0]
+    for bit in (64, 256):
+        assert lib.zs_conv2d_nhwc(*conv, 16 | bit, 1.0, 0.0, 0, None) == 0 and b"retired" in lib.zs_last_error()
+        assert lib.zs_conv2d_nhwc_ws(*conv, 16 | bit, 1.0, 0.0, 0, None, None) == 0 and b"retired" in lib.zs_last_error()
+        assert lib.zs_conv2d_nhwc_fused(*conv, 16 | 128 | bit, 1.0, 0.0, 0, ctypes.byref(_lib.ConvFuse()), None, None) == 0
+        assert b"retired" in lib.zs_last_error()
     # negative sizes / null pointers are rejected before any HIP call: 0 + message
     assert lib.zs_chamfer_forward(None, None, 1, -1, 3, None, None, None, None, None) == 0
     assert b"negative" in lib.zs_last_error()

@@ -310,12 +310,10 @@ def test_conv2d_split_k_across_workgroups(B, Cin, H, W, Cout, k, monkeypatch):
     (28, 768, 14, 14, 768, 1, 1, False), (6, 3072, 14, 14, 768, 1, 1, False), (3, 64, 56, 56, 256, 3, 1, False),
     (2, 32, 57, 41, 200, 3, 2, False), (5, 20, 31, 33, 130, 5, 1, False), (1, 256, 64, 64, 128, 1, 1, False),
     (8, 256, 28, 28, 320, 3, 1, True), (3, 128, 40, 36, 256, 3, 2, False), (28, 768, 14, 14, 2304, 1, 1, False)])
-def test_conv2d_stream_k(B, Cin, H, W, Cout, k, stride, in_relu, monkeypatch):
-    """ZS_CONV_STREAM_K: the large-tile kernels as a fixed number of workgroups sharing the (tile, k-step) space
-    (128 x 128 tiles over 768 workgroups; 256 x 256 tiles over 256 for layers with >= 192 output channels); tiles
-    cut across workgroups are summed in k order by whichever arrives last.  Same result as one workgroup per tile
-    up to the summation order, bit-reproducible over repeated launches (counters return to zero), every operand
-    path (pointwise, tap-major with / without input ReLU, generic taps; ragged M and Cout), fused epilogue."""
+def test_conv2d_large_tile_operand_paths(B, Cin, H, W, Cout, k, stride, in_relu):
+    """The large-tile kernels (tiling="large": LDS-DMA pipelined in split-fp16, register-staged otherwise) on every operand
+    path - pointwise, tap-major with / without input ReLU, generic taps - with ragged M and Cout and the fused residual +
+    ReLU epilogue: parity with torch, bit-reproducible over repeated launches, the shared workspace counters at rest."""
     from zeroshape_amd.nn import ops, pack
     g = torch.Generator().manual_seed(Cin + Cout + k)
     xc = torch.randn(B, Cin, H, W, generator=g)
@@ -331,14 +329,10 @@ def test_conv2d_stream_k(B, Cin, H, W, Cout, k, stride, in_relu, monkeypatch):
     try:
         for prec in ("f32", "f16x3"):
             ops.set_conv_precision(prec)
-            monkeypatch.setattr(ops, "STREAM_K", "always")
             runs = [ops.conv2d(x, pc, res1=res, act=ops.ACT_RELU, in_relu=in_relu, tiling="large") for _ in range(4)]
-            monkeypatch.setattr(ops, "STREAM_K", False)
-            single = ops.conv2d(x, pc, res1=res, act=ops.ACT_RELU, in_relu=in_relu, tiling="large")
             for r in runs[1:]:
                 assert torch.equal(runs[0], r)
             close(runs[0], want)
-            assert float((runs[0] - single).abs().max()) < 2e-5 * max(1.0, float(single.abs().max()))
         assert int(ops.splitk_workspace(x.device)[:1 << 18].view(torch.int32).abs().max()) == 0    # counters at rest
     finally:
         ops.set_conv_precision(prev)
@@ -346,7 +340,7 @@ def test_conv2d_stream_k(B, Cin, H, W, Cout, k, stride, in_relu, monkeypatch):
 
 def test_conv2d_random_shape_sweep():
     """tools/fuzz_conv.py: 80 random layer shapes (kernel 1 / 3 / 5, stride 1 / 2, ragged M and Cout, 4..320 input
-    channels, input ReLU, three activations, forced tilings, stream-K on every other case) - split-fp16 against the
+    channels, input ReLU, three activations, forced tilings) - split-fp16 against the
     exact-fp32 kernels at 2e-5 of the output scale, the fp32 kernels against torch CPU on every tenth case."""
     import subprocess
     import sys

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Random-shape sweep of the inference convolution engine: split-fp16 (whatever kernel the dispatcher picks: small
-tiles, register-staged, LDS-DMA pipelined; stream-K forced on every other case) against the exact-fp32 kernels of
+tiles, register-staged, LDS-DMA pipelined) against the exact-fp32 kernels of
 the same engine and against torch CPU on a subsample.   python tools/fuzz_conv.py [cases] [seed]"""
 import os
 import sys
@@ -33,7 +33,6 @@ for case in range(cases):
     b = torch.randn(cout, generator=g)
     pc = pack.pack_conv(w, b, stride=stride, padding=k // 2).to("cuda")
     xg = x.cuda()
-    ops.STREAM_K = "always" if case % 2 else False
     outs = {}
     res = None
     for prec in ("f32", "f16x3"):
@@ -52,7 +51,7 @@ for case in range(cases):
         e2 = float((ref - outs["f32"]).abs().max()) / scale
         ok = ok and e2 < 2e-5
     if not ok:
-        print("FAIL case %d: B=%d %dx%d cin=%d cout=%d k=%d s=%d in_relu=%s act=%d tiling=%s stream_k=%s err=%.3e"
-              % (case, B, H, W, cin, cout, k, stride, in_relu, act, tiling, ops.STREAM_K, err))
+        print("FAIL case %d: B=%d %dx%d cin=%d cout=%d k=%d s=%d in_relu=%s act=%d tiling=%s err=%.3e"
+              % (case, B, H, W, cin, cout, k, stride, in_relu, act, tiling, err))
         sys.exit(1)
 print("%d cases ok, worst |f16x3 - f32| / max = %.2e" % (cases, worst))

@@ -6,7 +6,6 @@ OUT=$ROOT/gpurun_out/prof
 TAG=${1:-conv}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export ZS_CONV_STREAM_K=${ZS_CONV_STREAM_K:-0}
 for shape in "pw --B 28 --H 14 --Cin 768 --Cout 3072 --k 1" "c3 --B 28 --H 56 --Cin 256 --Cout 256 --k 3"; do
   set -- $shape; name=$1; shift
   CMD="python3 $ROOT/tools/bench_conv.py $* --mode fwd --iters 20 --engine ops"

@@ -48,16 +48,14 @@ struct ConvArgs {
     float in_scale, in_shift;
     int dil;   // 1, or 2: the input is read as if zero-stuffed to (H-1)*2+1 rows / columns (the
                // data-gradient of a stride-2 convolution is a stride-1 convolution over that)
-    // split-K across workgroups (small-tile variant): blockIdx.z takes one of `splits` ranges of K and
+    // split-K across workgroups (small-tile, LDS-DMA and patch128 kernels): blockIdx.z takes one of `splits` ranges of K and
     // writes its raw partial tile to ws[split][M][Cout]; conv_splitk_reduce_kernel sums them in order
     float *ws;
     int splits;
-    // stream-K (large-tile variant): the (tile, k-step) iteration space is cut into gridDim.x equal contiguous
-    // ranges; sk_per = iterations per workgroup, ws = [tile arrival counters | partial tiles]
-    int sk_per;
+    int xcd_ntiles;   // conv3x3_patch128_kernel: > 0 = its column tiles, the launch is 1-D and dealt to the XCDs (nn_conv_patch.h)
+    int tail_tiles;   // conv_gemm_pp256_kernel: tiles of the last, partial round; each is cut into `splits` K ranges (nn_conv_pp256.h)
     int w_split;   // F16: the weights are already split (zs_conv2d_presplit_weight): quads 4s+q hold the hi halves and
                    // 4s+q+2 the lo halves of the K = 16 operand the lane half q contracts, q = 0, 1
-    int slab_major;   // LDS-DMA kernel, kh * kw > 1: walk K as (16-channel slab, tap) instead of (tap, channel) - see SlabWalk
     // conv3x3_patch32_kernel only: fused pointwise tail to one channel (zs_conv3x3_tail_nhwc); out is then [B][H][W]
     const float *tail_w, *tail_b;
     int tail_act;
@@ -66,11 +64,12 @@ struct ConvArgs {
     int fz_tiles_per_sample;      // input-statistics tiles per sample (in_mode 1 / 3), output tiles per sample (out_mode 1)
 };
 
-// workspace layout (floats): [SK_COUNTERS ints, zero between launches][partial tiles / split-K partial sums]
-constexpr size_t WS_COUNTER_FLOATS = (size_t)1 << 18;          // 1 MiB: up to 262,144 tiles
-constexpr int SK_MAX_WGS = 1024;
+// workspace layout (floats): [WS_COUNTER_FLOATS ints, zero between launches: the streaming kernel's tickets][partial tiles /
+// split-K partial sums].  Captured graphs bake in the workspace pointer and its size: the byte values stay as they are.
+constexpr size_t WS_COUNTER_FLOATS = (size_t)1 << 18;          // 1 MiB: up to 262,144 tickets
 constexpr size_t WS_SPLITK_BYTES = (size_t)16 << 20;           // small-tile split-K partial sums
-constexpr size_t WS_PARTS_BYTES = (size_t)SK_MAX_WGS * 2 * 128 * 128 * 4;     // the partial-tile region (stream-K shares, patch-kernel split-K)
+constexpr size_t WS_PARTS_BYTES = (size_t)128 << 20;           // the partial-tile region (split-K of the patch, LDS-DMA, pp256-tail and
+                                                               // streaming kernels): 2,048 tiles of 128 x 128 floats
 
 __device__ __forceinline__ float activate(float v, int act) {
     if (act == ZS_ACT_RELU) return fmaxf(v, 0.f);
@@ -146,6 +145,7 @@ struct TapWalk {
         kx = tap - ky * a.kw;
         set_tap(a, pix_ok, iy0, ix0);
     }
+    __device__ __forceinline__ int kquad(const ConvArgs &a) const { return (tap * a.Cin + cc) >> 2; }   // row quad of the weights
     __device__ __forceinline__ void advance(const ConvArgs &a, int step, bool pix_ok, int iy0, int ix0) {
         cc += step;
         if (cc >= a.Cin) {        // uniform
@@ -154,62 +154,6 @@ struct TapWalk {
             kx++;
             if (kx == a.kw) { kx = 0; ky++; }
             set_tap(a, pix_ok, iy0, ix0);
-        }
-    }
-};
-
-// Slab-major walk (round 3 experiment, LDS-DMA kernel, opt-in ZS_CONV_SLAB_MAJOR=1): the k steps of a kh x kw layer in
-// the order (16-channel slab outer, tap inner) instead of (tap outer, channels inner).  Hypothesis: the
-// tap-major order streams all channels of a tap - 131 KiB per 128-row tile at 56 x 56 x 256 - before the next tap touches
-// the same input pixels again, 32 concurrent tiles per XCD overflow its 4 MiB L2, so every tap re-reads its activations
-// from beyond L2; slab-major puts the nine reads of an input pixel's 64-byte slab back to back.  MEASURED (tools/
-// conv_shapes.py, batch 28, same box): SLOWER - the 3 x 3 256 -> 256 layer at 56 x 56 516 vs 432 us, the 128 -> 32 head
-// at 224 x 224 1,611 vs 1,370 us, 20.2 vs 19.3 ms of convolutions per forward.  Where the re-reads are served from does
-// not matter: the kernel is bound by the BYTES it moves into LDS (the same in both orders), and tap-major reads each
-// pixel's channels as one sequential run over consecutive steps.  Only staging fewer bytes helps (an input patch kept
-// in LDS across the nine taps) - not built.  Same products, summed in another order; weights addressed by (tap, slab).
-struct SlabWalk {
-    int tap, cc, ky, kx;          // uniform across the workgroup / wave
-    bool ok;
-    size_t base;
-    __device__ __forceinline__ void set_tap(const ConvArgs &a, bool pix_ok, int iy0, int ix0) {
-        const int vy = iy0 + ky, vx = ix0 + kx, sh = a.dil - 1;
-        const int iy = vy >> sh, ix = vx >> sh;
-        ok = pix_ok && ky < a.kh && vy >= 0 && iy < a.Hin && vx >= 0 && ix < a.Win && ((vy | vx) & sh) == 0;
-        base = ok ? ((size_t)iy * a.Win + ix) * a.Cin : 0;
-    }
-    __device__ __forceinline__ void init(const ConvArgs &a, int step, bool pix_ok, int iy0, int ix0) {
-        const int ntaps = a.kh * a.kw;
-        if (a.slab_major) {
-            const int slab = step / ntaps;
-            tap = step - slab * ntaps;
-            cc = slab * BK;
-        } else {
-            const int k = BK * step;
-            tap = k / a.Cin;
-            cc = k - tap * a.Cin;
-        }
-        ky = tap / a.kw;
-        kx = tap - ky * a.kw;
-        set_tap(a, pix_ok, iy0, ix0);
-    }
-    __device__ __forceinline__ int kquad(const ConvArgs &a) const { return (tap * a.Cin + cc) >> 2; }   // row quad of the weights
-    __device__ __forceinline__ void advance(const ConvArgs &a, bool pix_ok, int iy0, int ix0) {
-        if (a.slab_major) {       // uniform
-            tap++;
-            kx++;
-            if (kx == a.kw) { kx = 0; ky++; }
-            if (tap == a.kh * a.kw) { tap = 0; kx = 0; ky = 0; cc += BK; }
-            set_tap(a, pix_ok, iy0, ix0);
-        } else {
-            cc += BK;
-            if (cc >= a.Cin) {
-                cc -= a.Cin;
-                tap++;
-                kx++;
-                if (kx == a.kw) { kx = 0; ky++; }
-                set_tap(a, pix_ok, iy0, ix0);
-            }
         }
     }
 };
@@ -226,30 +170,21 @@ struct AQuad { f32x4 v; bool ok; };
 // exactly the eight k values the MFMA lane (row, half = kq_lo) contracts over - so it splits them
 // once into the hi / lo operand halves and stores those where the two fp32 quads went; the MFMA
 // loop then issues 3 K = 16 MFMAs per tile pair instead of 8 K = 2 ones at a quarter of the rate.
-template <bool PW, int MODE = 0, bool PLAIN = false, bool F16 = false, bool SK = false>
+template <bool PW, int MODE = 0, bool PLAIN = false, bool F16 = false>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
     constexpr bool TM = MODE == 2;
     __shared__ f32x4 lds_a[2][KQ][BM];
     __shared__ f32x4 lds_b[2][KQ][BN];
-    __shared__ int sk_last;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ksteps = (a.K + BK - 1) / BK;
-    const int ntiles = a.CoutPad / BN;
     const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64, l32 = lane & 31, half = lane >> 5;
     const int prow = tid & (BM - 1), kq_lo = tid >> 7;       // this thread stages row prow, k-quads kq_lo and kq_lo + 2
     const float relu_floor = a.in_relu ? 0.f : -INFINITY;
     const int adv_tap = BK / a.Cin, adv_c = BK % a.Cin;
     const f32x4 *wq = reinterpret_cast<const f32x4 *>(a.w);
 
-    // stream-K: this workgroup's contiguous range of the iteration space (tile-major, n fastest, then k-steps);
-    // otherwise one tile per workgroup, all of K
-    int it = SK ? (int)blockIdx.x * a.sk_per : ((int)blockIdx.x * ntiles + (int)blockIdx.y) * ksteps;
-    const int it_begin = it;
-    const int it_end = SK ? min(it + a.sk_per, (int)(((a.M + BM - 1) / BM) * ntiles) * ksteps) : it + ksteps;
-
-    while (it < it_end) {
-    const int tile = it / ksteps, kb = it - tile * ksteps, ke = min(ksteps, kb + (it_end - it));
-    const int m0 = (tile / ntiles) * BM, n0 = (tile % ntiles) * BN;
+    const int m0 = (int)blockIdx.x * BM, n0 = (int)blockIdx.y * BN;      // one tile per workgroup, all of K
+    const int kb = 0, ke = ksteps;
 
     // this thread's A pixel
     const int pix = m0 + prow;
@@ -433,69 +368,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
             }
         }
     };
-    if (!SK || (kb == 0 && ke == ksteps)) {
 #pragma unroll
-        for (int j = 0; j < 2; j++)
+    for (int j = 0; j < 2; j++)
 #pragma unroll
-            for (int i = 0; i < 2; i++) epilogue(i, j, acc[i][j]);
-    } else {
-        // A share of a tile: park the raw accumulators (slot 0 = this workgroup's first segment, slot 1 = its last),
-        // count arrivals; the workgroup that arrives last sums all shares in k order - the same sum whoever does
-        // it - and runs the epilogue.  No workgroup ever waits for another.  Shares move as agent-scope relaxed atomics
-        // (sc1: written through to / read from memory, the coherence point of the eight XCDs' L2s), drained by the store
-        // counter before the workgroup barrier; the arrival counter is an ACQ_REL read-modify-write by one thread per
-        // workgroup (release: the shares written before the barrier; acquire: the last arriver reads the others' shares) -
-        // the ordering no longer rests on what gfx950 and hipcc happen to do.  (A __threadfence() in every
-        // thread costs 3x the whole kernel here, measured.)  The sum is formed in fresh registers, tile by tile: the
-        // accumulators stay in the AGPR half and the kernel keeps three workgroups per CU.
-        float *parts = a.ws + WS_COUNTER_FLOATS;
-        int *counters = reinterpret_cast<int *>(a.ws);
-        float *mine = parts + ((size_t)blockIdx.x * 2 + (it == it_begin ? 0 : 1)) * (BM * BN) + tid;
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-#pragma unroll
-                for (int r = 0; r < 16; r++)
-                    __hip_atomic_store(&mine[((i * 2 + j) * 16 + r) * 256], acc[i][j][r], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("" ::: "memory");                 // one tile's registers at a time
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's shares have reached memory
-        __syncthreads();
-        const int w_first = (tile * ksteps) / a.sk_per, w_last = ((tile + 1) * ksteps - 1) / a.sk_per;
-        if (tid == 0) {
-            const int old = __hip_atomic_fetch_add(&counters[tile], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            sk_last = old == w_last - w_first;
-            if (sk_last)                                      // ready for the next launch
-                __hip_atomic_store(&counters[tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (sk_last) {
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    f32x16 d;
-#pragma unroll
-                    for (int r = 0; r < 16; r++) d[r] = 0.f;
-#pragma unroll 1
-                    for (int w = w_first; w <= w_last; w++) {
-                        const int w_tile0 = (w * a.sk_per) / ksteps;   // the tile of w's first iteration
-                        const float *p = parts + ((size_t)w * 2 + (w_tile0 == tile ? 0 : 1)) * (BM * BN) + tid;
-#pragma unroll
-                        for (int r = 0; r < 16; r++)
-                            d[r] += __hip_atomic_load(&p[((i * 2 + j) * 16 + r) * 256], __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    epilogue(i, j, d);
-                    asm volatile("" ::: "memory");
-                }
-        }
-        __syncthreads();          // sk_last is rewritten by the next segment
-    }
-    it += ke - kb;
-    }
+        for (int i = 0; i < 2; i++) epilogue(i, j, acc[i][j]);
 }
 
 
@@ -521,41 +397,32 @@ __device__ __forceinline__ void wait_vm_then_barrier() {       // all but the N 
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" : : "n"(N) : "memory");
 }
 
-// DMA_NS stages of 16 KiB: 3 -> three workgroups per CU, two steps of lead.  (9 stages, one workgroup per CU, eight
+// DMA_NS = 3 stages of 16 KiB: three workgroups per CU, two steps of lead.  (9 stages, one workgroup per CU, eight
 // steps of lead measured SLOWER - 632 vs 471 us on the 3x3 layer: the limit is the rate of the stream, not its latency.)
-// MI = 32-row MFMA tiles per wave along M: 2 -> 128 x 128 workgroup tile (three workgroups per CU), 4 -> 256 x 128 (two
-// per CU, 25 % fewer bytes through LDS per MFMA: 24 KiB instead of 2 x 16 per 256 x 128 outputs and k-step)
-template <bool PW, bool RELU, bool SK, int DMA_NS, int MI = 2>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DMA_NS == 2 ? 4 : 2, 8))) void conv_gemm_dma_kernel(ConvArgs a) {
-    constexpr int DMA_DEPTH = DMA_NS - 1;
+// MI = 32-row MFMA tiles per wave along M: 2 -> 128 x 128 workgroup tile (three workgroups per CU), 1 -> 64 x 128 (four)
+constexpr int DMA_NS = 3, DMA_DEPTH = DMA_NS - 1;
+template <bool PW, bool RELU, int MI = 2>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) void conv_gemm_dma_kernel(ConvArgs a) {
     constexpr int TMB = 64 * MI;                              // rows of the workgroup tile
     constexpr int NDMA = MI + 2;                              // DMAs per wave and step: A row blocks of 64, B columns x 2
     constexpr int STAGE_BYTES = (TMB + BN) * BK * 4;
     __shared__ f32x4 lds[DMA_NS][KQ * (TMB + BN)];            // [stage][A: [k-quad][row] | B: [k-quad][column]]
     __shared__ __attribute__((aligned(16))) float ep_lds[2][BN];   // the tile's per-channel scale | shift (epilogue reads them as
                                                                   // ds_read_b128: no vector-memory instructions for them)
-    __shared__ int sk_last;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) f32x4 *)&lds[0][0]);
     const int ksteps = (a.K + BK - 1) / BK;
-    const int ntiles = a.CoutPad / BN;
     const int wm = (wave & 1) * (32 * MI), wn = (wave >> 1) * 64, l32 = lane & 31, half = lane >> 5;
     const char *zero = reinterpret_cast<const char *>(zs_zero_page);
     const f32x4 *wq = reinterpret_cast<const f32x4 *>(a.w);
 
-    // plain split-K (a.splits > 1, not SK): blockIdx.z owns the k-steps [z, z + 1) * ksteps / splits of its tile and writes the
-    // raw partial tile to ws[z][M][Cout]; conv_splitk_reduce_kernel sums the ranges in order and applies the epilogue
-    const int split_lo = (!SK && a.splits > 1) ? (int)(((long long)blockIdx.z * ksteps) / a.splits) : 0;
-    const int split_n = (!SK && a.splits > 1) ? (int)(((long long)(blockIdx.z + 1) * ksteps) / a.splits) - split_lo : ksteps;
-    int it = SK ? (int)blockIdx.x * a.sk_per : ((int)blockIdx.x * ntiles + (int)blockIdx.y) * ksteps + split_lo;
-    const int it_begin = it;
-    const int it_end = SK ? min(it + a.sk_per, (int)(((a.M + TMB - 1) / TMB) * ntiles) * ksteps) : it + split_n;
-
-    while (it < it_end) {
-    const int tile = it / ksteps, kb = it - tile * ksteps, ke = min(ksteps, kb + (it_end - it));
-    const int m0 = (tile / ntiles) * TMB, n0 = (tile % ntiles) * BN;
-    {   // visible to the epilogue through the barriers of the k loop (the previous tile's epilogue is behind a barrier too)
+    // One tile per workgroup.  Split-K (a.splits > 1): blockIdx.z owns the k-steps [z, z + 1) * ksteps / splits of its tile and
+    // writes the raw partial tile to ws[z][M][Cout]; conv_splitk_reduce_kernel sums the ranges in order and applies the epilogue
+    const int kb = a.splits > 1 ? (int)(((long long)blockIdx.z * ksteps) / a.splits) : 0;
+    const int ke = a.splits > 1 ? (int)(((long long)(blockIdx.z + 1) * ksteps) / a.splits) : ksteps;
+    const int m0 = (int)blockIdx.x * TMB, n0 = (int)blockIdx.y * BN;
+    {   // visible to the epilogue through the barriers of the k loop
         const int which = tid >> 7, c = tid & (BN - 1), n = n0 + c;
         const float *src = which ? a.shift : a.scale;
         ep_lds[which][c] = (src && n < a.Cout) ? src[n] : (which ? 0.0f : 1.0f);
@@ -567,7 +434,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DMA_NS == 2
     // [row][4 slots], slot = quad ^ ((row >> 2) & 3): the MFMA fragment reads (32 rows, one quad) stay conflict-free.
     // This wave issues instructions wave * MI + h (rows 16 (wave MI + h) + lane / 4), B: k-quad `wave`, columns lane, + 64.
     const int a_slot = lane & 3;
-    SlabWalk tw[MI];
+    TapWalk tw[MI];
     const float *src[MI];                                     // PW: the pixel's row; TM: the image
     bool pok[MI];
     int iy0[MI], ix0[MI];
@@ -589,7 +456,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DMA_NS == 2
             iy0[h] = py * a.stride - a.pad_t;
             ix0[h] = px * a.stride - a.pad_l;
             src[h] = a.in + (size_t)pb * a.Hin * a.Win * a.Cin;
-            tw[h].init(a, kb, pok[h], iy0[h], ix0[h]);
+            tw[h].init(a, BK * kb, pok[h], iy0[h], ix0[h]);
         }
     }
     const f32x4 *wcol = wq + n0 + lane;
@@ -611,7 +478,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DMA_NS == 2
                 g = (live && pok[h] && k < a.K) ? reinterpret_cast<const char *>(src[h] + k) : zero;
             } else {
                 g = (live && tw[h].ok) ? reinterpret_cast<const char *>(src[h] + tw[h].base + tw[h].cc + 4 * a_quad) : zero;
-                if (live) tw[h].advance(a, pok[h], iy0[h], ix0[h]);
+                if (live) tw[h].advance(a, BK, pok[h], iy0[h], ix0[h]);
             }
 #if !defined(ZS_EXP_CONV_NO_DMA) && !defined(ZS_EXP_CONV_NO_DMA_A)
             dma16(g, dst + h * 1024);
@@ -635,8 +502,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DMA_NS == 2
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
-    // everybody is done with the stages (previous segment's reads) before they are refilled
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the pipeline starts with nothing in flight
 #pragma unroll
     for (int d = 0; d < DMA_DEPTH; d++) issue();
 
@@ -697,7 +563,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DMA_NS == 2
     auto epilogue = [&](int i, int j, const f32x16 &d) {
         const int m = m0 + wm + 32 * i + l32;
         if (m >= a.M) return;
-        float *part = (!SK && a.splits > 1) ? a.ws + WS_COUNTER_FLOATS + (size_t)blockIdx.z * a.M * a.Cout : nullptr;
+        float *part = a.splits > 1 ? a.ws + WS_COUNTER_FLOATS + (size_t)blockIdx.z * a.M * a.Cout : nullptr;
         const size_t row = (size_t)m * a.Cout;
         const bool vec = (a.Cout & 3) == 0;
 #pragma unroll
@@ -726,278 +592,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DMA_NS == 2
             }
         }
     };
-    if (!SK || (kb == 0 && ke == ksteps)) {
 #pragma unroll
-        for (int j = 0; j < 2; j++)
+    for (int j = 0; j < 2; j++)
 #pragma unroll
-            for (int i = 0; i < MI; i++) epilogue(i, j, acc[i][j]);
-    } else {   // a share of a tile: see conv_gemm_kernel
-        float *parts = a.ws + WS_COUNTER_FLOATS;
-        int *counters = reinterpret_cast<int *>(a.ws);
-        float *mine = parts + ((size_t)blockIdx.x * 2 + (it == it_begin ? 0 : 1)) * (TMB * BN) + tid;
-#pragma unroll
-        for (int i = 0; i < MI; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-#pragma unroll
-                for (int r = 0; r < 16; r++)
-                    __hip_atomic_store(&mine[((i * 2 + j) * 16 + r) * 256], acc[i][j][r], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("" ::: "memory");
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const int w_first = (tile * ksteps) / a.sk_per, w_last = ((tile + 1) * ksteps - 1) / a.sk_per;
-        if (tid == 0) {
-            const int old = __hip_atomic_fetch_add(&counters[tile], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            sk_last = old == w_last - w_first;
-            if (sk_last) __hip_atomic_store(&counters[tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (sk_last) {
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < MI; i++) {
-                    f32x16 d;
-#pragma unroll
-                    for (int r = 0; r < 16; r++) d[r] = 0.f;
-#pragma unroll 1
-                    for (int w = w_first; w <= w_last; w++) {
-                        const int w_tile0 = (w * a.sk_per) / ksteps;
-                        const float *p = parts + ((size_t)w * 2 + (w_tile0 == tile ? 0 : 1)) * (TMB * BN) + tid;
-#pragma unroll
-                        for (int r = 0; r < 16; r++)
-                            d[r] += __hip_atomic_load(&p[((i * 2 + j) * 16 + r) * 256], __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    epilogue(i, j, d);
-                    asm volatile("" ::: "memory");
-                }
-        }
-        __syncthreads();
-    }
-    it += ke - kb;
-    }
+        for (int i = 0; i < MI; i++) epilogue(i, j, acc[i][j]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the zero-page DMAs issued past the end
-}
-
-// ---- 256 x 256 tiles, eight waves, stream-K: the variant for large layers ------------------------------------ //
-// tools/conv_abl.sh: with the DMAs removed the 128 x 128 kernel above runs 2.6x faster (3x3 256 -> 256 at 56 x 56 x
-// 28: 186 vs 490 us) - it is bound by the bytes it moves from L2 into LDS (1 KiB per k for 128 x 128 outputs, ~9 TB/s
-// in aggregate), not by latency or the matrix pipe.  A 256 x 256 tile moves half the bytes per MFMA.  One workgroup
-// of eight waves per CU (wave tile 64 x 128, two waves per SIMD), four 32 KiB stages, three steps of lead, always
-// as stream-K over 256 persistent workgroups (with 256 slots every layer shape would otherwise round up badly).
-constexpr int TM2 = 256, TN2 = 256, NS2 = 4, DEPTH2 = NS2 - 1;
-constexpr int STAGE2_BYTES = (TM2 + TN2) * BK * 4;           // 32 KiB: A [4 quads][256 rows][16 B], then B the same
-
-template <bool PW, bool RELU>
-__global__ __launch_bounds__(512) void conv_gemm_dma256_kernel(ConvArgs a) {
-    __shared__ f32x4 lds[NS2][2][KQ][TM2];
-    __shared__ int sk_last;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) f32x4 *)&lds[0][0][0][0]);
-    const int ksteps = (a.K + BK - 1) / BK;
-    const int ntiles = (a.CoutPad + TN2 - 1) / TN2;
-    const int wm = (wave & 3) * 64, wn = (wave >> 2) * 128, l32 = lane & 31, half = lane >> 5;
-    const int kq_w = wave & 3, blk_w = wave >> 2;              // this wave stages k-quad kq_w of row / column block blk_w
-    const char *zero = reinterpret_cast<const char *>(zs_zero_page);
-    const f32x4 *wq = reinterpret_cast<const f32x4 *>(a.w);
-
-    // workgroups are dealt to the eight XCDs round-robin: give each XCD one contiguous eighth of the iteration space
-    // (neighbouring tiles share A rows / B columns through that XCD's own L2)
-#ifdef ZS_EXP_CONV_NO_XCD_MAP
-    const int wg = (int)blockIdx.x;
-#else
-    const int wg = (gridDim.x & 7) == 0 ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-#endif
-    int it = wg * a.sk_per;
-    const int it_begin = it;
-    const int it_end = min(it + a.sk_per, (int)(((a.M + TM2 - 1) / TM2) * ntiles) * ksteps);
-
-    while (it < it_end) {
-    const int tile = it / ksteps, kb = it - tile * ksteps, ke = min(ksteps, kb + (it_end - it));
-    const int m0 = (tile / ntiles) * TM2, n0 = (tile % ntiles) * TN2;
-
-    TapWalk tw[2];
-    const float *src[2];
-    bool pok[2], nok[2];
-    int iy0[2], ix0[2];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const int pix = m0 + blk_w * 128 + 64 * h + lane;
-        pok[h] = pix < a.M;
-        nok[h] = n0 + blk_w * 128 + 64 * h + lane < a.CoutPad;
-        if (PW) {
-            src[h] = a.in + (size_t)(pok[h] ? pix : 0) * a.Cin;
-        } else {
-            int pb = 0, py = 0, px = 0;
-            if (pok[h]) {
-                pb = pix / (a.Hout * a.Wout);
-                const int rem = pix - pb * a.Hout * a.Wout;
-                py = rem / a.Wout;
-                px = rem - py * a.Wout;
-            }
-            iy0[h] = py * a.stride - a.pad_t;
-            ix0[h] = px * a.stride - a.pad_l;
-            src[h] = a.in + (size_t)pb * a.Hin * a.Win * a.Cin;
-            tw[h].init(a, BK * kb, pok[h], iy0[h], ix0[h]);
-        }
-    }
-    const f32x4 *wcol = wq + n0 + blk_w * 128 + lane;
-    int ks_issue = kb;
-    auto issue = [&]() {                                      // 4 DMAs per wave: A rows x 2, B columns x 2
-        const int st = (ks_issue - kb) % NS2;
-        const unsigned dst = lds_base + st * STAGE2_BYTES + (kq_w * TM2 + blk_w * 128) * 16;
-        const bool live = ks_issue < ke;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const char *g;
-            if (PW) {
-                const int k = BK * ks_issue + 4 * kq_w;
-                g = (live && pok[h] && k < a.K) ? reinterpret_cast<const char *>(src[h] + k) : zero;
-            } else {
-                g = (live && tw[h].ok) ? reinterpret_cast<const char *>(src[h] + tw[h].base + tw[h].cc + 4 * kq_w) : zero;
-                if (live) tw[h].advance(a, BK, pok[h], iy0[h], ix0[h]);
-            }
-#ifndef ZS_EXP_CONV_NO_DMA
-            dma16(g, dst + h * 1024);
-#endif
-        }
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const char *g = (live && nok[h]) ? reinterpret_cast<const char *>(wcol + (size_t)(ks_issue * KQ + kq_w) * a.CoutPad + 64 * h) : zero;
-#ifndef ZS_EXP_CONV_NO_DMA
-            dma16(g, dst + KQ * TM2 * 16 + h * 1024);
-#endif
-        }
-        ks_issue++;
-    };
-
-    f32x16 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-    for (int d = 0; d < DEPTH2; d++) issue();
-
-    for (int ks = kb; ks < ke; ks++) {
-        wait_vm_then_barrier<4 * (DEPTH2 - 1)>();
-        issue();
-        const int st = (ks - kb) % NS2;
-        u32x4 ah[2], al[2], bh[4], bl[4];
-        f32x4 fa[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            fa[i][0] = lds[st][0][half][wm + 32 * i + l32];
-            fa[i][1] = lds[st][0][half + 2][wm + 32 * i + l32];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            bh[j] = __builtin_bit_cast(u32x4, lds[st][1][half][wn + 32 * j + l32]);
-            bl[j] = __builtin_bit_cast(u32x4, lds[st][1][half + 2][wn + 32 * j + l32]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            if (RELU) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    fa[i][0][e] = fmaxf(fa[i][0][e], 0.f);
-                    fa[i][1][e] = fmaxf(fa[i][1][e], 0.f);
-                }
-            }
-            zs::s16::split8(fa[i][0], fa[i][1], ah[i], al[i]);
-        }
-#ifdef ZS_EXP_CONV_NO_MFMA
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) acc[i][j][e] += __builtin_bit_cast(float, ah[i][e] ^ al[i][e] ^ bh[j][e] ^ bl[j][e]);
-#else
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) zs::s16::mfma3(acc[i][j], ah[i], al[i], bh[j], bl[j]);
-#endif
-    }
-
-    auto epilogue = [&](int i, int j, const f32x16 &d) {
-        const int n = n0 + wn + 32 * j + l32;
-        if (n >= a.Cout) return;
-        const float sc = a.scale ? a.scale[n] : 1.0f, sh = a.shift ? a.shift[n] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int m = m0 + wm + 32 * i + 8 * (r >> 2) + 4 * half + (r & 3);
-            if (m >= a.M) continue;
-            const size_t o = (size_t)m * a.Cout + n;
-            float v = d[r] * sc + sh;
-            if (a.res1) v += a.res1[o];
-            if (a.res2) v += a.res2[o];
-            a.out[o] = activate(v, a.act);
-        }
-    };
-    if (kb == 0 && ke == ksteps) {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int i = 0; i < 2; i++) epilogue(i, j, acc[i][j]);
-    } else {   // a share of a tile: see conv_gemm_kernel
-        float *parts = a.ws + WS_COUNTER_FLOATS;
-        int *counters = reinterpret_cast<int *>(a.ws);
-        float *mine = parts + ((size_t)wg * 2 + (it == it_begin ? 0 : 1)) * (TM2 * TN2) + tid;
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-#pragma unroll
-                for (int r = 0; r < 16; r++)
-                    __hip_atomic_store(&mine[((i * 4 + j) * 16 + r) * 512], acc[i][j][r], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("" ::: "memory");
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const int w_first = (tile * ksteps) / a.sk_per, w_last = ((tile + 1) * ksteps - 1) / a.sk_per;
-        if (tid == 0) {
-            const int old = __hip_atomic_fetch_add(&counters[tile], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            sk_last = old == w_last - w_first;
-            if (sk_last) __hip_atomic_store(&counters[tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (sk_last) {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    f32x16 d;
-#pragma unroll
-                    for (int r = 0; r < 16; r++) d[r] = 0.f;
-#pragma unroll 1
-                    for (int w = w_first; w <= w_last; w++) {
-                        const int w_tile0 = (w * a.sk_per) / ksteps;
-                        const float *p = parts + ((size_t)w * 2 + (w_tile0 == tile ? 0 : 1)) * (TM2 * TN2) + tid;
-#pragma unroll
-                        for (int r = 0; r < 16; r++)
-                            d[r] += __hip_atomic_load(&p[((i * 4 + j) * 16 + r) * 512], __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    epilogue(i, j, d);
-                    asm volatile("" ::: "memory");
-                }
-        }
-        __syncthreads();
-    }
-    it += ke - kb;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 #include "nn_conv_patch.h"
@@ -1531,26 +1130,444 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_stats_kernel(ConvArgs 
     }
 }
 
+// ---- launcher: knobs, derived facts, launch helpers ----------------------------------------------------------- //
+
+long long env_num(const char *v, long long dflt) { return v ? atoll(v) : dflt; }
+
+// Every tuning knob of the launcher, read from the environment once, at the first launch.  They choose between live kernels from
+// a layer's shape (INTEGRATION.md lists them); a layer that takes another kernel sums in another order.
+struct ConvKnobs {
+    // fewer than ~3/4 of a wave of 128x128 tiles over the 256 CUs: the small-tile kernels.  (128 is ~1 % faster at batch 28 - 15.3
+    // vs 15.5 ms - but moves the training kernels too: the 300-iteration from-scratch run of tests/test_gpu_trained_weights.py then
+    // takes the trajectory on which the untrained depth head dies; kept at 192)
+    const char *big_min_env = getenv("ZS_CONV_BIG_MIN");
+    long long big_min = env_num(big_min_env, 192);
+    bool big_min_set = big_min_env != nullptr;            // a value given for the threshold holds with a workspace too
+    // With a workspace - the inference engine (nn/ops.py); the training path calls zs_conv2d_nhwc without one and keeps 192 - the
+    // large-tile kernels start at 96 tiles (tools/enc_b28.py on one box: 192 / 128 / 96 / 80 / 64 / 40 tiles = 14.24 / 14.08 /
+    // 14.11 / 14.06 / 14.61 / 14.87 ms per batch-28 forward; batch 1 has no layer in that range)
+    long long big_min_ws = env_num(getenv("ZS_CONV_BIG_MIN_WS"), 96);
+    // 64 x 128 tiles (MI = 1, four workgroups per CU) where 128-row tiles give most CUs a single workgroup - ViT fc2 / proj at
+    // batch 28: 264 tiles on 256 CUs, four waves per CU.  tools/conv_shapes.py, batch 28, threshold 0 / 300 / 600 / 1200:
+    // 17.17 / 16.83 / 16.44 / 16.94 ms of convolutions (fc2 167 -> 148 us, proj 73 -> 55, the 344-tile 1x1 layers 43 -> 32)
+    long long half_below = env_num(getenv("ZS_CONV_HALF_BELOW"), 600);
+    // A/B switches for measurements: generic taps instead of the tap-major walk, no input-patch kernels, the register-staged
+    // kernel instead of the LDS-DMA one
+    bool no_tapmajor = getenv("ZS_CONV_NO_TAPMAJOR") != nullptr;
+    bool no_patch = getenv("ZS_CONV_NO_PATCH") != nullptr;
+    bool no_dma = getenv("ZS_CONV_NO_DMA") != nullptr;
+    // conv3x3_patch128_kernel: from this many workgroups unsplit; below it (14 x 14 maps at batch 28: 112; everything at batch 1)
+    // the slabs are split across ~patch_split_target workgroups.  (patch_split_min was 64: the 56 x 56 fusion layers at batch 1 -
+    // 50 workgroups - took the LDS-DMA kernel + split-K; batch 1 3.00 -> 2.95 ms)
+    long long patch_min = env_num(getenv("ZS_CONV_PATCH_MIN"), 192);
+    long long patch_split_target = env_num(getenv("ZS_CONV_PATCH_SPLIT_TARGET"), 384);
+    long long patch_split_min = env_num(getenv("ZS_CONV_PATCH_SPLIT_MIN"), 32);
+    bool patch_xcd = env_num(getenv("ZS_CONV_PATCH_XCD"), 1) != 0;      // column tiles of a pixel tile on one XCD (nn_conv_patch.h)
+    // 256 x 256 ping-pong tiles (tools/bench_pp256.py, old -> new us: fc1 110 -> 97, qkv 91 -> 73, fc2 142 -> 95, 16,384 x 3,072 x
+    // 768 312 -> 236; it loses where a tile's K loop is short against its 256 KiB epilogue and one workgroup per CU cannot overlap
+    // the two: proj (66 tiles x K 768) 38 -> 44, K <= 512 everywhere)
+    bool pp_on = env_num(getenv("ZS_CONV_PP256"), 1) != 0;
+    long long pp_min_tiles = env_num(getenv("ZS_CONV_PP256_MIN_TILES"), 48);
+    long long pp_min_k = env_num(getenv("ZS_CONV_PP256_MIN_K"), 768);
+    long long pp_long_k = env_num(getenv("ZS_CONV_PP256_LONG_K"), 2048);
+    long long pp_max_split = env_num(getenv("ZS_CONV_PP256_MAX_SPLIT"), 8);
+    long long pp_min_steps = env_num(getenv("ZS_CONV_PP256_MIN_STEPS"), 4);
+    // ... and from K = 256 where the tiles make four rounds or more (the window stage of the transformer coordinate encoder at
+    // batch 28: 356,720 rows - qkv 770 -> 562 us, fc1 1,096 -> 695, fc2 807 -> 560, proj 272 -> 245; at 343 tiles the same K
+    // loses: 56 -> 68): over many rounds the XCDs drift apart and one tile's epilogue runs beside another's loop
+    long long pp_many_k = env_num(getenv("ZS_CONV_PP256_MANY_K"), 256);
+    // LDS-DMA kernel with the k-steps split across blockIdx.z (tools/conv_shapes.py + tools/bench_encoder.py, same box: batch 28
+    // 18.23 -> 17.89 ms - the 768 -> 768 head layers 156 -> 100 us; below ~40 tiles - the ViT fc2 at batch 1: 12 tiles - the reduce
+    // launch costs more than the ranges save)
+    long long dsplit_min_steps = env_num(getenv("ZS_CONV_DMA_SPLIT_MIN_STEPS"), 96);
+    long long dsplit_min_tiles = env_num(getenv("ZS_CONV_DMA_SPLIT_MIN_TILES"), 40);
+    // pointwise layers of few rows: the streaming GEMM kernel (csrc/nn_gemm_stream.hip)
+    bool stream = env_num(getenv("ZS_CONV_STREAM"), 1) != 0;
+    long long stream_max_rows = env_num(getenv("ZS_STREAM_MAX_ROWS"), 1024);
+    // small-tile kernel: 32 x 32 tiles - twice the workgroups - for the smallest problems
+    long long narrow_below = env_num(getenv("ZS_CONV_NARROW_BELOW"), 384);
+    // small-tile kernel, K split across workgroups on the caller's flag (ZS_CONV_SPLIT_SMALL): ~512 workgroups
+    long long split_target = env_num(getenv("ZS_CONV_SPLIT_TARGET"), 512);
+    // ... and, whatever the caller's flag, layers with a LONG contraction on few workgroups (3 x 3 768 -> 768 on 7 x 7 maps at
+    // batch 1: 48 workgroups stream 21 MB of weights in 33.7 us): K >= split_long_k on <= split_long_wgs workgroups split towards
+    // split_long_target workgroups.  The split everywhere at target 512 was a loss at batch 1; restricted to long contractions and
+    // with FEW ranges it pays (tools/enc_b1.py, batch-1 forward):
+    //   off 2.923 ms | K >= 6912: 2.838 | 4096: 2.844 | 2304: 2.792 (target 512) | 2304 at target 384 / 256 / 192: 2.785 / 2.787 /
+    //   2.726 | K >= 2048 at target 192 / 160 / 128 / 96: 2.712 / 2.717 / 2.752 / 2.788 | K >= 1024 at 160: 2.723
+    long long split_long_k = env_num(getenv("ZS_CONV_SPLIT_LONG_K"), 2048);
+    long long split_long_wgs = env_num(getenv("ZS_CONV_SPLIT_LONG_WGS"), 64);
+    long long split_long_target = env_num(getenv("ZS_CONV_SPLIT_LONG_TARGET"), 192);
+};
+const ConvKnobs &knobs() {
+    static const ConvKnobs k;
+    return k;
+}
+
+bool small_is_narrow(long long M, int Cout) { return ((M + SM - 1) / SM) * ((Cout + 63) / 64) < knobs().narrow_below; }
+
+// 1 x 1, stride 1, no padding, no dilation, same map: the operand address is pixel * Cin + k
+bool pointwise_geom(int kh, int kw, int stride, int pad_t, int pad_l, int dil, int Hin, int Win, int Hout, int Wout) {
+    return kh == 1 && kw == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && dil == 1 && Hin == Hout && Win == Wout;
+}
+
+// What the kernel families ask about a call, derived once from the filled ConvArgs
+struct ConvPlan {
+    int flags;
+    const zs_conv_fuse *fuse;
+    void *workspace;
+    hipStream_t st;
+    long long M, big_tiles;       // output pixels; 128 x 128 tiles
+    bool f16, presplit16;         // split-fp16 arithmetic; ... with pre-split weights (what every DMA / patch / streaming kernel takes)
+    bool affine, plain;           // input scale / shift present; no input transform at all (no ReLU either)
+    bool pw_geom, pw;             // pointwise_geom(); pointwise and plain: the kernels' PW operand path
+    bool forced, small;           // a tiling flag is set; the small-tile side of the big_min threshold (or forced there)
+};
+
+void fill_conv_args(ConvArgs &a, const float *in, const float *packed_w, const float *scale, const float *shift, const float *res1,
+                    const float *res2, float *out, int batch, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int kh, int kw,
+                    int stride, int pad_t, int pad_l, int flags, float in_scale, float in_shift, int act, void *workspace) {
+    memset(&a, 0, sizeof a);      // no tail, no fused normalisation, no XCD map, no pp256 tail
+    a.in = in; a.w = packed_w; a.scale = scale; a.shift = shift; a.res1 = res1; a.res2 = res2; a.out = out;
+    a.B = batch; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.Cout = Cout;
+    a.CoutPad = (Cout + BN - 1) / BN * BN;
+    a.kh = kh; a.kw = kw; a.stride = stride; a.pad_t = pad_t; a.pad_l = pad_l;
+    a.K = kh * kw * Cin; a.M = batch * Hout * Wout;
+    a.in_relu = (flags & ZS_CONV_IN_RELU) ? 1 : 0;
+    a.act = act; a.in_scale = in_scale; a.in_shift = in_shift;
+    a.dil = (flags & ZS_CONV_IN_DILATE2) ? 2 : 1;
+    a.ws = static_cast<float *>(workspace);
+    a.splits = 1;
+    a.w_split = (flags & ZS_CONV_W_PRESPLIT) ? 1 : 0;
+}
+
+// The streaming kernel's description of a pointwise layer.  The K16-major layouts do not combine with a K split; otherwise, with
+// a workspace, a long contraction may come back as up to four ranges of raw partial sums for launch_splitk_reduce.
+zs::stream_gemm::Args stream_args(const ConvArgs &a, int flags, void *workspace, int *ranges) {
+    zs::stream_gemm::Args g;
+    memset(&g, 0, sizeof g);
+    g.a = a.in; g.w = a.w; g.scale = a.scale; g.shift = a.shift; g.res1 = a.res1; g.res2 = a.res2; g.out = a.out;
+    g.M = a.M; g.K = a.K; g.N = a.Cout; g.CoutPad = a.CoutPad; g.lda = a.Cin; g.act = a.act; g.in_relu = a.in_relu;
+    g.in_stats = a.fz.in_mode == 2 ? a.fz.in_stats : nullptr;
+    g.in_tiles = a.fz.in_tiles;
+    g.in_eps = a.fz.in_eps;
+    g.out_stats = a.fz.out_mode == 2 ? a.fz.out_stats : nullptr;
+    g.stats_cols = zs_conv2d_fused_cols(a.M, a.Cout);
+    g.parts = workspace ? static_cast<float *>(workspace) + WS_COUNTER_FLOATS : nullptr;
+    g.tickets = static_cast<int *>(workspace);
+    g.parts_bytes = WS_PARTS_BYTES;
+    g.max_tickets = (int)WS_COUNTER_FLOATS;
+    g.a_k16 = (flags & ZS_CONV_IN_K16) ? 1 : 0;
+    g.out_k16 = (flags & ZS_CONV_OUT_K16) ? 1 : 0;
+    g.two_launch_max = !g.a_k16 && !g.out_k16 && workspace && (a.Cout & 3) == 0 ? 4 : 1;
+    g.ranges = ranges;
+    return g;
+}
+bool stream_fuse_ok(const zs_conv_fuse *f) {
+    return !f || ((f->in_mode == 0 || f->in_mode == 2) && (f->out_mode == 0 || f->out_mode == 2));
+}
+
+// out = epilogue(sum of the a.splits raw partial results in ws, in range order).  stats_cols 32 / 64: the layer also writes the
+// statistics of zs_conv_fuse.out_mode, in the layout of an unsplit small-tile launch with tiles that wide
+void launch_splitk_reduce(const ConvArgs &a, hipStream_t st, int stats_cols) {
+    if (stats_cols) {
+        const dim3 grid((unsigned)((a.M + SM - 1) / SM), (unsigned)((a.Cout + stats_cols - 1) / stats_cols));
+        if (stats_cols == 32) hipLaunchKernelGGL(conv_splitk_reduce_stats_kernel<1>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(conv_splitk_reduce_stats_kernel<2>, grid, dim3(256), 0, st, a);
+    } else {
+        const long long total = (long long)a.M * a.Cout;
+        const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a);
+    }
+}
+
+// The operand paths of the register-staged kernels as their template arguments <PW, MODE, PLAIN, F16>: pointwise; tap-major
+// without / with an input transform; generic taps
+template <typename Launch>
+void with_operand_path(bool pw, bool tm, bool plain, bool f16, Launch launch) {
+    using std::bool_constant;
+    using std::integral_constant;
+    auto path = [&](auto F16) {
+        if (pw) launch(bool_constant<true>{}, integral_constant<int, 0>{}, bool_constant<false>{}, F16);
+        else if (tm && plain) launch(bool_constant<false>{}, integral_constant<int, 2>{}, bool_constant<true>{}, F16);
+        else if (tm) launch(bool_constant<false>{}, integral_constant<int, 2>{}, bool_constant<false>{}, F16);
+        else launch(bool_constant<false>{}, integral_constant<int, 0>{}, bool_constant<false>{}, F16);
+    };
+    if (f16) path(bool_constant<true>{});
+    else path(bool_constant<false>{});
+}
+void launch_big(const ConvArgs &a, dim3 grid, hipStream_t st, bool pw, bool tm, bool plain, bool f16) {
+    with_operand_path(pw, tm, plain, f16, [&](auto PW, auto MODE, auto PLAIN, auto F16) {
+        hipLaunchKernelGGL((conv_gemm_kernel<decltype(PW)::value, decltype(MODE)::value, decltype(PLAIN)::value, decltype(F16)::value>), grid, dim3(256), 0, st, a);
+    });
+}
+template <int NJ>
+void launch_small(const ConvArgs &a, dim3 grid, hipStream_t st, bool pw, bool tm, bool plain, bool f16) {
+    with_operand_path(pw, tm, plain, f16, [&](auto PW, auto MODE, auto PLAIN, auto F16) {
+        hipLaunchKernelGGL((conv_gemm_small_kernel<NJ, decltype(PW)::value, decltype(MODE)::value, decltype(PLAIN)::value, decltype(F16)::value>), grid, dim3(256), 0, st, a);
+    });
+}
+// ... with a fused input normalisation (split-fp16): pointwise with in_mode 1 or 2, or tap-major plain with in_mode 1
+template <int NJ>
+void launch_small_xf(const ConvArgs &a, dim3 grid, hipStream_t st, bool pw) {
+    if (!pw) hipLaunchKernelGGL((conv_gemm_small_kernel<NJ, false, 2, true, true, 1>), grid, dim3(256), 0, st, a);
+    else if (a.fz.in_mode == 1) hipLaunchKernelGGL((conv_gemm_small_kernel<NJ, true, 0, false, true, 1>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_gemm_small_kernel<NJ, true, 0, false, true, 2>), grid, dim3(256), 0, st, a);
+}
+// the LDS-DMA kernel: pointwise, or tap-major with / without input ReLU
+template <int MI>
+void launch_dma(const ConvArgs &a, dim3 grid, hipStream_t st, bool pw) {
+    if (pw) hipLaunchKernelGGL((conv_gemm_dma_kernel<true, false, MI>), grid, dim3(256), 0, st, a);
+    else if (a.in_relu) hipLaunchKernelGGL((conv_gemm_dma_kernel<false, true, MI>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_gemm_dma_kernel<false, false, MI>), grid, dim3(256), 0, st, a);
+}
+template <bool UP2 = false>
+void launch_patch32(const ConvArgs &a, hipStream_t st) {
+    const int tx = (a.Wout + patch32::PT - 1) / patch32::PT, ty = (a.Hout + patch32::PT - 1) / patch32::PT;
+    const dim3 grid((unsigned)((long long)a.B * tx * ty));
+    if (a.in_relu) hipLaunchKernelGGL((conv3x3_patch32_kernel<true, 8, UP2>), grid, dim3(512), 0, st, a, tx, ty);
+    else hipLaunchKernelGGL((conv3x3_patch32_kernel<false, 8, UP2>), grid, dim3(512), 0, st, a, tx, ty);
+}
+
+// ---- the kernel families, in the order conv2d_impl asks them: each launches and returns true, or declines -------- //
+
+// 3 x 3 stride-1 pad-1 layers in split-fp16 with pre-split weights: the input-patch kernels (nn_conv_patch.h)
+bool try_patch(ConvArgs &a, const ConvPlan &p) {
+    const ConvKnobs &k = knobs();
+    if (!(p.presplit16 && !k.no_patch && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.dil == 1 && a.pad_t == 1 && a.pad_l == 1 &&
+          a.Hin == a.Hout && a.Win == a.Wout && (a.Cin % BK) == 0 && !p.affine && !p.forced && a.Hout >= 8 && a.Wout >= 8))
+        return false;
+    if (a.Cout <= 32) {
+        launch_patch32(a, p.st);
+        return true;
+    }
+    const int tx = (a.Wout + patch128::TW - 1) / patch128::TW, ty = (a.Hout + patch128::TH - 1) / patch128::TH;
+    const long long mtiles = (long long)a.B * tx * ty, ntl = a.CoutPad / BN, wgs = mtiles * ntl;
+    // few tiles: split the slabs across ~patch_split_target workgroups, partial tiles through the workspace, summed in range
+    // order by conv_splitk_reduce_kernel (which applies the epilogue)
+    long long sp = 1;
+    if (wgs < k.patch_min && p.workspace && wgs >= k.patch_split_min) {
+        sp = (k.patch_split_target + wgs - 1) / wgs;
+        const long long slabs = a.Cin / BK, cap = (long long)(WS_PARTS_BYTES / 4) / (p.M * (long long)a.Cout);
+        if (sp > slabs / 2) sp = slabs / 2;            // at least two slabs (18 tap-steps) per range
+        if (sp > cap) sp = cap;
+    }
+    if (wgs < k.patch_min && sp <= 1) return false;
+    a.splits = (int)(sp > 1 ? sp : 1);
+    dim3 grid((unsigned)mtiles, (unsigned)ntl, (unsigned)a.splits);
+    if (k.patch_xcd && ntl > 1) {
+        a.xcd_ntiles = (int)ntl;
+        grid = dim3((unsigned)((mtiles + 7) / 8 * 8 * ntl), 1, (unsigned)a.splits);
+    }
+    if (a.in_relu) hipLaunchKernelGGL((conv3x3_patch128_kernel<true>), grid, dim3(256), 0, p.st, a, tx, ty);
+    else hipLaunchKernelGGL((conv3x3_patch128_kernel<false>), grid, dim3(256), 0, p.st, a, tx, ty);
+    if (a.splits > 1) launch_splitk_reduce(a, p.st, 0);
+    return true;
+}
+
+// large pointwise layers: 256 x 256 ping-pong tiles (nn_conv_pp256.h)
+bool try_pp256(ConvArgs &a, const ConvPlan &p) {
+    const ConvKnobs &k = knobs();
+    static const int cus = [] {
+        int dev = 0, n = 256;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    const long long T = ((p.M + pp256::TM - 1) / pp256::TM) * ((a.CoutPad + pp256::TN - 1) / pp256::TN);
+    const bool pays = k.pp_on && T >= k.pp_min_tiles &&
+                      ((a.K >= k.pp_min_k && (T >= cus / 2 || a.K >= k.pp_long_k)) || (a.K >= k.pp_many_k && T >= 4LL * cus));
+    if (!(((p.flags & ZS_CONV_FORCE_TILE256) || pays) && p.pw && p.presplit16 && !p.fuse && (a.Cin % pp256::SK) == 0 &&
+          (a.Cout & 3) == 0 && !p.forced))
+        return false;
+    const long long steps = a.K / pp256::SK;
+    // the tail: tiles beyond the last whole round of the CUs (or all of them, when they fill less than half of one)
+    long long tail = T <= cus / 2 ? T : (T % cus < cus / 2 ? T % cus : 0), sp = 1;
+    if (T < cus && T > cus / 2) tail = 0;
+    if (tail && p.workspace) {
+        sp = cus / tail;
+        if (sp > k.pp_max_split) sp = k.pp_max_split;
+        if (sp > steps / k.pp_min_steps) sp = steps / k.pp_min_steps;
+        const long long cap = (long long)(WS_PARTS_BYTES / 4) / ((long long)pp256::TM * pp256::TN);
+        if (tail * sp > cap) sp = cap / tail;
+    }
+    if (sp < 2) { tail = 0; sp = 1; }
+    a.tail_tiles = (int)tail;
+    a.splits = (int)sp;
+    const dim3 grid((unsigned)(T - tail + tail * sp));
+    hipLaunchKernelGGL(pp256::conv_gemm_pp256_kernel, grid, dim3(512), 0, p.st, a);
+    if (tail) hipLaunchKernelGGL(pp256::pp256_tail_kernel, dim3(pp256::MI * pp256::NJ * 4, (unsigned)tail), dim3(512), 0, p.st, a);
+    return true;
+}
+
+// few 128 x 128 tiles but a long contraction (3 x 3 768 -> 768 on 7 x 7 maps at batch 28: 66 tiles, 432 k-steps): the LDS-DMA
+// kernel with the k-steps split across blockIdx.z, ~384 workgroups, >= 24 steps each.  (Unlike the large-tile rule below this
+// one asks for dilation 1 and not for the tap-major switch.)
+bool try_dma_splitk(ConvArgs &a, const ConvPlan &p) {
+    const ConvKnobs &k = knobs();
+    const bool dma_ok = p.presplit16 && (a.Cin % BK) == 0 && !p.affine && a.dil == 1 && !k.no_dma;
+    const long long ksteps = (a.K + BK - 1) / BK;
+    if (!(p.small && !(p.flags & ZS_CONV_FORCE_SMALL) && p.workspace && dma_ok && ksteps >= k.dsplit_min_steps &&
+          p.big_tiles >= k.dsplit_min_tiles))
+        return false;
+    long long sp = (384 + p.big_tiles - 1) / p.big_tiles;
+    const long long cap = (long long)(WS_PARTS_BYTES / 4) / (p.M * (long long)a.Cout);
+    if (sp > ksteps / 24) sp = ksteps / 24;
+    if (sp > cap) sp = cap;
+    if (sp <= 1) return false;
+    a.splits = (int)sp;
+    launch_dma<2>(a, dim3((unsigned)((p.M + BM - 1) / BM), (unsigned)(a.CoutPad / BN), (unsigned)sp), p.st, p.pw);
+    launch_splitk_reduce(a, p.st, 0);
+    return true;
+}
+
+// pointwise layers of few rows: the streaming GEMM kernel (csrc/nn_gemm_stream.hip).  It applies an input ReLU itself, so this
+// rule asks for the pointwise geometry without scale / shift, not for `pw`.
+bool try_stream(ConvArgs &a, const ConvPlan &p) {
+    const ConvKnobs &k = knobs();
+    if (!(k.stream && p.pw_geom && p.presplit16 && !p.affine && p.M <= k.stream_max_rows && stream_fuse_ok(p.fuse))) return false;
+    int ranges = 1;
+    const zs::stream_gemm::Args g = stream_args(a, p.flags, p.workspace, &ranges);
+    if (!zs::stream_gemm::launch(g, p.st)) return false;
+    if (ranges > 1) {             // the kernel wrote raw partial sums of `ranges` K ranges: sum + epilogue (+ statistics) here
+        a.splits = ranges;
+        launch_splitk_reduce(a, p.st, g.out_stats ? g.stats_cols : 0);
+    }
+    return true;
+}
+
+// the small-tile kernel (32 x 64 or 32 x 32 tiles), with or without a K split across workgroups, with or without a fused input
+// normalisation.  Takes every layer; false = an error has been set
+bool launch_small_tiles(ConvArgs &a, const ConvPlan &p) {
+    const ConvKnobs &k = knobs();
+    const zs_conv_fuse *fuse = p.fuse;
+    const bool tm = !p.pw && !k.no_tapmajor && (a.Cin % 8) == 0;
+    const bool narrow = (fuse && fuse->out_mode == 2) ? zs_conv2d_fused_cols(a.M, a.Cout) == 32 : small_is_narrow(p.M, a.Cout);
+    const int cols = narrow ? 32 : 64;
+    const long long wgs = ((p.M + SM - 1) / SM) * ((a.Cout + cols - 1) / cols);
+    // Split K across workgroups while the launch would leave most of the 256 CUs idle (14x14 maps, 197-token matrices at batch
+    // 1: 28-84 workgroups): >= 16 t-steps (K = 128) per split, partial tiles inside the caller's workspace
+    // (zs_conv2d_splitk_workspace_bytes()).  On the caller's flag, or for a long contraction (ConvKnobs::split_long_k) - fused
+    // layers too: their statistics are then written by conv_splitk_reduce_stats_kernel; the vector epilogue needs Cout % 4
+    const bool flagged = (p.flags & ZS_CONV_SPLIT_SMALL) != 0;
+    const bool long_split = p.workspace && (!fuse || (a.Cout & 3) == 0) && a.K >= k.split_long_k && wgs <= k.split_long_wgs;
+    if (p.workspace && (flagged || long_split) && wgs < 256) {
+        const int T = (a.K + BK - 1) / BK * 2;
+        long long sp = ((flagged ? k.split_target : k.split_long_target) + wgs - 1) / wgs;
+        if (sp > T / 16) sp = T / 16;
+        if (sp > 16) sp = 16;
+        const long long cap = (long long)(WS_SPLITK_BYTES / 4) / (p.M * (long long)a.Cout);
+        if (sp > cap) sp = cap;
+        if (sp > 1) a.splits = (int)sp;
+    }
+    const dim3 grid((unsigned)((p.M + SM - 1) / SM), (unsigned)((a.Cout + cols - 1) / cols), (unsigned)a.splits);
+    if (fuse && fuse->in_mode) {
+        if (!(p.pw || (tm && p.plain && fuse->in_mode == 1))) {
+            zs::set_err("zs_conv2d_nhwc_fused: in_mode %d needs a pointwise layer (or, for in_mode 1, Cin %% 8 == 0)", fuse->in_mode);
+            return false;
+        }
+        if (narrow) launch_small_xf<1>(a, grid, p.st, p.pw);
+        else launch_small_xf<2>(a, grid, p.st, p.pw);
+    } else if (narrow) {
+        launch_small<1>(a, grid, p.st, p.pw, tm, p.plain, p.f16);
+    } else {
+        launch_small<2>(a, grid, p.st, p.pw, tm, p.plain, p.f16);
+    }
+    // with statistics: epilogue + statistics of the summed ranges, in the unsplit launch's layout
+    if (a.splits > 1) launch_splitk_reduce(a, p.st, fuse && fuse->out_mode ? cols : 0);
+    return true;
+}
+
+// the 128 x 128 (or 64 x 128) tile kernels, one tile per workgroup.  Split-fp16 with pre-split weights, pointwise or tap-major
+// geometry, no input scale / shift: the LDS-DMA pipelined kernel; otherwise the register-staged one
+void launch_large_tiles(ConvArgs &a, const ConvPlan &p) {
+    const ConvKnobs &k = knobs();
+    const bool tm = !p.pw && !k.no_tapmajor && (a.Cin % BK) == 0;
+    const bool dma = p.presplit16 && !k.no_dma && (p.pw || tm) && !p.affine && (a.Cin % BK) == 0;
+    const unsigned ntl = (unsigned)(a.CoutPad / BN);
+    if (dma && p.big_tiles < k.half_below) launch_dma<1>(a, dim3((unsigned)((p.M + 63) / 64), ntl), p.st, p.pw);
+    else if (dma) launch_dma<2>(a, dim3((unsigned)((p.M + BM - 1) / BM), ntl), p.st, p.pw);
+    else launch_big(a, dim3((unsigned)((p.M + BM - 1) / BM), ntl), p.st, p.pw, tm, p.plain, p.f16);
+}
+
 }  // namespace
 
 extern "C" size_t zs_conv2d_splitk_workspace_bytes(void) {
-    static_assert(WS_PARTS_BYTES == (size_t)SK_MAX_WGS * 2 * BM * BN * 4 && WS_PARTS_BYTES >= WS_SPLITK_BYTES, "workspace regions");
+    static_assert(WS_PARTS_BYTES >= WS_SPLITK_BYTES, "workspace regions");
     return WS_COUNTER_FLOATS * 4 + WS_PARTS_BYTES;
+}
+
+// Column-tile width of the row statistics (out_mode 2): the small-tile kernel's preference (the streaming kernel writes them
+// too - 32 or 64 columns - but with its K split off it refuses these few-tile layers, and the small kernel's narrow tiles are
+// faster on few rows: ViT proj 8.3 vs 9.7 us, fc2 20.4 vs 23.2 us, tools/stream_shapes.py)
+extern "C" int zs_conv2d_fused_cols(int M, int Cout) { return small_is_narrow(M, Cout) || Cout % 64 ? 32 : 64; }
+
+static int conv2d_impl(const float *in, const float *packed_w, const float *scale, const float *shift,
+                       const float *res1, const float *res2, float *out, int batch, int Hin, int Win,
+                       int Cin, int Hout, int Wout, int Cout, int kh, int kw, int stride, int pad_t,
+                       int pad_l, int flags, float in_scale, float in_shift, int act, const zs_conv_fuse *fuse,
+                       void *workspace, void *stream) {
+    if (flags & (ZS_CONV_RETIRED_64 | ZS_CONV_RETIRED_256)) {
+        zs::set_err("zs_conv2d_nhwc: flag bits 64 and 256 (stream-K) are retired: the kernels they selected are gone (flags %d)", flags);
+        return 0;
+    }
+    if (batch < 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || (Cin & 3) || Hout <= 0 || Wout <= 0 || Cout <= 0 ||
+        kh <= 0 || kw <= 0 || stride <= 0 || act < 0 || act > ZS_ACT_RELU_CLAMP1) {
+        zs::set_err("zs_conv2d_nhwc: bad geometry (B=%d in %dx%dx%d out %dx%dx%d k %dx%d s %d act %d; Cin must be "
+                    "a multiple of 4)", batch, Hin, Win, Cin, Hout, Wout, Cout, kh, kw, stride, act);
+        return 0;
+    }
+    if (batch == 0) return 1;
+    if (!in || !packed_w || !out) { zs::set_err("zs_conv2d_nhwc: null pointer"); return 0; }
+    const long long M = (long long)batch * Hout * Wout;
+    if (M > (1LL << 30)) { zs::set_err("zs_conv2d_nhwc: %lld output pixels", M); return 0; }
+    ConvArgs a;
+    fill_conv_args(a, in, packed_w, scale, shift, res1, res2, out, batch, Hin, Win, Cin, Hout, Wout, Cout, kh, kw, stride, pad_t, pad_l,
+                   flags, in_scale, in_shift, act, workspace);
+    if (fuse) a.fz = *fuse;
+    a.fz_tiles_per_sample = fuse && batch > 1 ? 1 : 0;
+    if (a.w_split && !(flags & ZS_CONV_F16X3)) { zs::set_err("zs_conv2d_nhwc: ZS_CONV_W_PRESPLIT needs ZS_CONV_F16X3"); return 0; }
+
+    const ConvKnobs &k = knobs();
+    ConvPlan p;
+    p.flags = flags; p.fuse = fuse; p.workspace = workspace; p.st = static_cast<hipStream_t>(stream);
+    p.M = M;
+    p.big_tiles = ((M + BM - 1) / BM) * (a.CoutPad / BN);
+    p.f16 = (flags & ZS_CONV_F16X3) != 0;
+    p.presplit16 = p.f16 && a.w_split;
+    p.affine = in_scale != 1.0f || in_shift != 0.0f;
+    p.plain = !a.in_relu && !p.affine;
+    p.pw_geom = pointwise_geom(kh, kw, stride, pad_t, pad_l, a.dil, Hin, Win, Hout, Wout);
+    p.pw = p.pw_geom && p.plain;
+    p.forced = (flags & (ZS_CONV_FORCE_SMALL | ZS_CONV_FORCE_LARGE)) != 0;
+    p.small = (flags & ZS_CONV_FORCE_SMALL) ||
+              (!(flags & ZS_CONV_FORCE_LARGE) && p.big_tiles < (workspace && !k.big_min_set ? k.big_min_ws : k.big_min));
+
+    // K16-major activations (ZS_CONV_IN_K16 / ZS_CONV_OUT_K16): only the streaming GEMM kernel reads / writes that layout
+    if (flags & (ZS_CONV_IN_K16 | ZS_CONV_OUT_K16)) {
+        int ranges = 1;
+        if (!(p.pw && p.presplit16 && k.stream && stream_fuse_ok(fuse)) ||
+            !zs::stream_gemm::launch(stream_args(a, flags, workspace, &ranges), p.st)) {
+            zs::set_err("zs_conv2d_nhwc: the K16-major layout flags need a pointwise split-fp16 layer the streaming kernel takes "
+                        "(zs_conv2d_k16_ok; M=%lld Cin=%d Cout=%d)", M, Cin, Cout);
+            return 0;
+        }
+    } else if (try_patch(a, p) || try_pp256(a, p) || try_dma_splitk(a, p) || (p.small && try_stream(a, p))) {
+        // launched
+    } else if (p.small) {
+        if (!launch_small_tiles(a, p)) return 0;
+    } else {
+        launch_large_tiles(a, p);
+    }
+    return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
 }
 
 extern "C" int zs_conv2d_nhwc(const float *in, const float *packed_w, const float *scale, const float *shift,
                               const float *res1, const float *res2, float *out, int batch, int Hin, int Win,
                               int Cin, int Hout, int Wout, int Cout, int kh, int kw, int stride, int pad_t,
                               int pad_l, int flags, float in_scale, float in_shift, int act, void *stream) {
-    return zs_conv2d_nhwc_ws(in, packed_w, scale, shift, res1, res2, out, batch, Hin, Win, Cin, Hout, Wout, Cout, kh, kw,
-                             stride, pad_t, pad_l, flags, in_scale, in_shift, act, nullptr, stream);
+    return conv2d_impl(in, packed_w, scale, shift, res1, res2, out, batch, Hin, Win, Cin, Hout, Wout, Cout, kh, kw, stride,
+                       pad_t, pad_l, flags, in_scale, in_shift, act, nullptr, nullptr, stream);
 }
-
-static int conv2d_impl(const float *in, const float *packed_w, const float *scale, const float *shift,
-                       const float *res1, const float *res2, float *out, int batch, int Hin, int Win,
-                       int Cin, int Hout, int Wout, int Cout, int kh, int kw, int stride, int pad_t,
-                       int pad_l, int flags, float in_scale, float in_shift, int act, const zs_conv_fuse *fuse,
-                       void *workspace, void *stream);
 
 extern "C" int zs_conv2d_nhwc_ws(const float *in, const float *packed_w, const float *scale, const float *shift,
                                  const float *res1, const float *res2, float *out, int batch, int Hin, int Win,
@@ -1561,26 +1578,6 @@ extern "C" int zs_conv2d_nhwc_ws(const float *in, const float *packed_w, const f
                        pad_t, pad_l, flags, in_scale, in_shift, act, nullptr, workspace, stream);
 }
 
-static bool small_is_narrow(long long M, int Cout) {
-    static const long long narrow_below = getenv("ZS_CONV_NARROW_BELOW") ? atoll(getenv("ZS_CONV_NARROW_BELOW")) : 384;
-    return ((M + SM - 1) / SM) * ((Cout + 63) / 64) < narrow_below;      // 32x32 tiles: twice the workgroups for the smallest problems
-}
-
-// out_mode 2 (row statistics per column tile): the small-tile kernel's own tile width; the streaming kernel follows it
-static bool stream_enabled() {
-    static const bool on = getenv("ZS_CONV_STREAM") == nullptr || atoi(getenv("ZS_CONV_STREAM")) != 0;
-    return on;
-}
-static long long stream_max_rows() {
-    static const long long rows = getenv("ZS_STREAM_MAX_ROWS") ? atoll(getenv("ZS_STREAM_MAX_ROWS")) : 1024;
-    return rows;
-}
-
-// Column-tile width of the row statistics (out_mode 2): the small-tile kernel's preference (the streaming kernel writes them
-// too - 32 or 64 columns - but with its K split off it refuses these few-tile layers, and the small kernel's narrow tiles are
-// faster on few rows: ViT proj 8.3 vs 9.7 us, fc2 20.4 vs 23.2 us, tools/stream_shapes.py)
-extern "C" int zs_conv2d_fused_cols(int M, int Cout) { return small_is_narrow(M, Cout) || Cout % 64 ? 32 : 64; }
-
 extern "C" int zs_conv2d_nhwc_fused(const float *in, const float *packed_w, const float *scale, const float *shift,
                                     const float *res1, const float *res2, float *out, int batch, int Hin, int Win,
                                     int Cin, int Hout, int Wout, int Cout, int kh, int kw, int stride, int pad_t,
@@ -1590,7 +1587,7 @@ extern "C" int zs_conv2d_nhwc_fused(const float *in, const float *packed_w, cons
     const int need = ZS_CONV_F16X3 | ZS_CONV_W_PRESPLIT;
     const zs_conv_fuse &f = *fuse;
     const long long hw_in = (long long)Hin * Win, hw_out = (long long)Hout * Wout;
-    const bool pw = kh == 1 && kw == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && Hin == Hout && Win == Wout;
+    const bool pw_geom = pointwise_geom(kh, kw, stride, pad_t, pad_l, 1, Hin, Win, Hout, Wout);     // (dilation is refused below)
     const bool gn_in = f.in_mode == 1;
     int gshift = 0;
     while ((32 << gshift) < Cin) gshift++;
@@ -1600,7 +1597,7 @@ extern "C" int zs_conv2d_nhwc_fused(const float *in, const float *packed_w, cons
         (f.in_mode && !f.in_stats) || (f.out_mode && !f.out_stats) ||
         (gn_in && (!f.in_gamma || !f.in_beta || f.in_groups != 32 || (32 << gshift) != Cin || Cin > XF_MAXC || f.in_tiles <= 0 ||
                    (batch > 1 && hw_in % SM) || (batch > 1 && hw_out % SM))) ||
-        (f.in_mode == 2 && (!pw || f.in_tiles <= 0 || f.in_tiles > 32 || Cin % f.in_tiles)) ||
+        (f.in_mode == 2 && (!pw_geom || f.in_tiles <= 0 || f.in_tiles > 32 || Cin % f.in_tiles)) ||
         (f.out_mode == 1 && (f.out_groups <= 0 || Cout % f.out_groups || (batch > 1 && hw_out % SM))) ||
         (f.out_mode == 2 && Cout % zs_conv2d_fused_cols((int)(batch * hw_out), Cout))) {
         zs::set_err("zs_conv2d_nhwc_fused: unsupported combination (flags %d in_mode %d out_mode %d Cin %d Cout %d k %dx%d s %d)",
@@ -1620,450 +1617,24 @@ extern "C" int zs_conv2d_nhwc_fused(const float *in, const float *packed_w, cons
                        pad_t, pad_l, (flags | ZS_CONV_FORCE_SMALL) & ~ZS_CONV_SPLIT_SMALL, in_scale, in_shift, act, &f2, workspace, stream);
 }
 
-// the streaming kernel's description of a pointwise layer with K16-major operands (shape, fusion and workspace fields; the
-// caller adds the tensors)
-static void k16_stream_args(zs::stream_gemm::Args &g, const ConvArgs &a, int Cin, int Cout, int flags, const zs_conv_fuse *fuse,
-                            void *workspace) {
-    memset(&g, 0, sizeof g);
-    g.M = a.M; g.K = a.K; g.N = Cout; g.CoutPad = a.CoutPad; g.lda = Cin; g.act = a.act; g.in_relu = 0;
-    g.in_stats = fuse && fuse->in_mode == 2 ? fuse->in_stats : nullptr;
-    g.in_tiles = fuse ? fuse->in_tiles : 0;
-    g.in_eps = fuse ? fuse->in_eps : 0.f;
-    g.out_stats = fuse && fuse->out_mode == 2 ? fuse->out_stats : nullptr;
-    g.stats_cols = zs_conv2d_fused_cols(a.M, Cout);
-    g.parts = workspace ? static_cast<float *>(workspace) + WS_COUNTER_FLOATS : nullptr;
-    g.tickets = static_cast<int *>(workspace);
-    g.parts_bytes = WS_PARTS_BYTES;
-    g.max_tickets = (int)WS_COUNTER_FLOATS;
-    g.two_launch_max = 1;
-    g.a_k16 = (flags & ZS_CONV_IN_K16) ? 1 : 0;
-    g.out_k16 = (flags & ZS_CONV_OUT_K16) ? 1 : 0;
-}
-
 // Would zs_conv2d_nhwc[_fused] accept this pointwise layer with the given K16 flags?  (ln_in: fuse.in_mode 2 with `in_tiles` tiles;
 // row_stats_out: fuse.out_mode 2; has_res: a residual is added.)  The caller asks before choosing the layout of a tensor.
 extern "C" int zs_conv2d_k16_ok(int M, int Cin, int Cout, int flags, int ln_in_tiles, int row_stats_out, int has_res) {
-    if (M <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 15) || (Cout & 3) || !stream_enabled() || M > stream_max_rows()) return 0;
+    const ConvKnobs &k = knobs();
+    if (M <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 15) || (Cout & 3) || !k.stream || M > k.stream_max_rows) return 0;
     if (!(flags & (ZS_CONV_IN_K16 | ZS_CONV_OUT_K16))) return 0;
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.M = M; a.K = Cin; a.CoutPad = (Cout + BN - 1) / BN * BN; a.act = 0;
-    zs_conv_fuse f;
-    memset(&f, 0, sizeof f);
     static float dummy[2];
-    if (ln_in_tiles > 0) { f.in_mode = 2; f.in_tiles = ln_in_tiles; f.in_stats = dummy; }
+    ConvArgs a;                  // a plain pointwise layer of M rows; the dry run looks at no tensor
+    fill_conv_args(a, nullptr, nullptr, nullptr, nullptr, has_res ? dummy : nullptr, nullptr, nullptr, 1, 1, M, Cin, 1, M, Cout, 1, 1, 1, 0,
+                   0, 0, 1.0f, 0.0f, 0, nullptr);
+    if (ln_in_tiles > 0) { a.fz.in_mode = 2; a.fz.in_tiles = ln_in_tiles; a.fz.in_stats = dummy; }
     if (row_stats_out) {
         if (Cout % zs_conv2d_fused_cols(M, Cout)) return 0;
-        f.out_mode = 2; f.out_stats = dummy;
+        a.fz.out_mode = 2; a.fz.out_stats = dummy;
     }
-    zs::stream_gemm::Args g;
-    k16_stream_args(g, a, Cin, Cout, flags, &f, dummy);          // (a workspace is always there in the inference engine)
-    g.res1 = has_res ? dummy : nullptr;
     int ranges = 1;
-    g.ranges = &ranges;
-    return zs::stream_gemm::launch(g, nullptr, true) ? 1 : 0;
-}
-
-static int conv2d_impl(const float *in, const float *packed_w, const float *scale, const float *shift,
-                       const float *res1, const float *res2, float *out, int batch, int Hin, int Win,
-                       int Cin, int Hout, int Wout, int Cout, int kh, int kw, int stride, int pad_t,
-                       int pad_l, int flags, float in_scale, float in_shift, int act, const zs_conv_fuse *fuse,
-                       void *workspace, void *stream) {
-    if (batch < 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || (Cin & 3) || Hout <= 0 || Wout <= 0 || Cout <= 0 ||
-        kh <= 0 || kw <= 0 || stride <= 0 || act < 0 || act > ZS_ACT_RELU_CLAMP1) {
-        zs::set_err("zs_conv2d_nhwc: bad geometry (B=%d in %dx%dx%d out %dx%dx%d k %dx%d s %d act %d; Cin must be "
-                    "a multiple of 4)", batch, Hin, Win, Cin, Hout, Wout, Cout, kh, kw, stride, act);
-        return 0;
-    }
-    if (batch == 0) return 1;
-    if (!in || !packed_w || !out) { zs::set_err("zs_conv2d_nhwc: null pointer"); return 0; }
-    const long long M = (long long)batch * Hout * Wout;
-    if (M > (1LL << 30)) { zs::set_err("zs_conv2d_nhwc: %lld output pixels", M); return 0; }
-    ConvArgs a;
-    a.slab_major = 0;
-    a.tail_w = a.tail_b = nullptr;
-    a.tail_act = 0;
-    if (fuse) a.fz = *fuse; else memset(&a.fz, 0, sizeof a.fz);
-    a.fz_tiles_per_sample = fuse && batch > 1 ? 1 : 0;
-    a.in = in; a.w = packed_w; a.scale = scale; a.shift = shift; a.res1 = res1; a.res2 = res2; a.out = out;
-    a.B = batch; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.Cout = Cout;
-    a.CoutPad = (Cout + BN - 1) / BN * BN;
-    a.kh = kh; a.kw = kw; a.stride = stride; a.pad_t = pad_t; a.pad_l = pad_l;
-    a.K = kh * kw * Cin; a.M = (int)M;
-    a.in_relu = (flags & ZS_CONV_IN_RELU) ? 1 : 0;
-    a.act = act; a.in_scale = in_scale; a.in_shift = in_shift;
-    a.dil = (flags & ZS_CONV_IN_DILATE2) ? 2 : 1;
-    a.ws = static_cast<float *>(workspace);
-    a.splits = 1;
-    a.sk_per = 0;
-    a.w_split = (flags & ZS_CONV_W_PRESPLIT) ? 1 : 0;
-    if (a.w_split && !(flags & ZS_CONV_F16X3)) { zs::set_err("zs_conv2d_nhwc: ZS_CONV_W_PRESPLIT needs ZS_CONV_F16X3"); return 0; }
-    // fewer than ~3/4 of a wave of 128x128 tiles over the 256 CUs: use the small-tile split-K variant
-    const long long big_tiles = ((M + BM - 1) / BM) * (a.CoutPad / BN);
-    static const long long big_min = getenv("ZS_CONV_BIG_MIN") ? atoll(getenv("ZS_CONV_BIG_MIN")) : 192;   // (128 is ~1 % faster at batch 28 - 15.3 vs 15.5 ms - but moves the training kernels too: the 300-iteration from-scratch run of tests/test_gpu_trained_weights.py then takes the trajectory on which the untrained depth head dies; kept at 192)
-    // With a workspace - the inference engine (nn/ops.py); the training path calls zs_conv2d_nhwc without one and keeps 192 - the
-    // large-tile kernels start at 96 tiles (round 5, tools/enc_b28.py on one box: 192 / 128 / 96 / 80 / 64 / 40 tiles = 14.24 / 14.08 /
-    // 14.11 / 14.06 / 14.61 / 14.87 ms per batch-28 forward; batch 1 has no layer in that range)
-    static const long long big_min_ws = getenv("ZS_CONV_BIG_MIN_WS") ? atoll(getenv("ZS_CONV_BIG_MIN_WS")) : 96;
-    const long long big_min_eff = workspace && !getenv("ZS_CONV_BIG_MIN") ? big_min_ws : big_min;
-    const bool small = (flags & ZS_CONV_FORCE_SMALL) || (!(flags & ZS_CONV_FORCE_LARGE) && big_tiles < big_min_eff);
-    const bool pw = kh == 1 && kw == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && a.dil == 1 && !a.in_relu &&
-                    in_scale == 1.0f && in_shift == 0.0f && Hin == Hout && Win == Wout;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool plain = !a.in_relu && in_scale == 1.0f && in_shift == 0.0f;
-    static const bool no_tm = getenv("ZS_CONV_NO_TAPMAJOR") != nullptr;       // A/B switch for measurements
-    const bool f16 = (flags & ZS_CONV_F16X3) != 0;
-#define ZS_LAUNCH1(KERNEL, F, ...)                                                                                  \
-    do {                                                                                                            \
-        if (pw) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, 0, false, F>), grid, dim3(256), 0, st, a);              \
-        else if (tm && plain) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, 2, true, F>), grid, dim3(256), 0, st, a); \
-        else if (tm) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, 2, false, F>), grid, dim3(256), 0, st, a);        \
-        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, 0, false, F>), grid, dim3(256), 0, st, a);                \
-    } while (0)
-#define ZS_LAUNCH(KERNEL, ...)                            \
-    do {                                                  \
-        if (f16) ZS_LAUNCH1(KERNEL, true, __VA_ARGS__);   \
-        else ZS_LAUNCH1(KERNEL, false, __VA_ARGS__);      \
-    } while (0)
-#define ZS_LAUNCH_BIG(F, SKF)                                                                                              \
-    do {                                                                                                                   \
-        if (pw) hipLaunchKernelGGL((conv_gemm_kernel<true, 0, false, F, SKF>), grid, dim3(256), 0, st, a);                  \
-        else if (tm && plain) hipLaunchKernelGGL((conv_gemm_kernel<false, 2, true, F, SKF>), grid, dim3(256), 0, st, a);    \
-        else if (tm) hipLaunchKernelGGL((conv_gemm_kernel<false, 2, false, F, SKF>), grid, dim3(256), 0, st, a);            \
-        else hipLaunchKernelGGL((conv_gemm_kernel<false, 0, false, F, SKF>), grid, dim3(256), 0, st, a);                    \
-    } while (0)
-    // ---- K16-major activations (ZS_CONV_IN_K16 / ZS_CONV_OUT_K16): only the streaming GEMM kernel reads / writes that layout ----
-    if (flags & (ZS_CONV_IN_K16 | ZS_CONV_OUT_K16)) {
-        const bool ok = kh == 1 && kw == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && a.dil == 1 && Hin == Hout && Win == Wout &&
-                        f16 && a.w_split && in_scale == 1.0f && in_shift == 0.0f && !a.in_relu && stream_enabled() &&
-                        (!fuse || ((fuse->in_mode == 0 || fuse->in_mode == 2) && (fuse->out_mode == 0 || fuse->out_mode == 2)));
-        zs::stream_gemm::Args g;
-        k16_stream_args(g, a, Cin, Cout, flags, fuse, workspace);
-        g.a = in; g.w = packed_w; g.scale = scale; g.shift = shift; g.res1 = res1; g.res2 = res2; g.out = out;
-        int ranges = 1;
-        g.ranges = &ranges;
-        if (!ok || !zs::stream_gemm::launch(g, st)) {
-            zs::set_err("zs_conv2d_nhwc: the K16-major layout flags need a pointwise split-fp16 layer the streaming kernel takes "
-                        "(zs_conv2d_k16_ok; M=%lld Cin=%d Cout=%d)", M, Cin, Cout);
-            return 0;
-        }
-        return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
-    }
-    // 3 x 3 stride-1 pad-1 layers in split-fp16 with pre-split weights: the input-patch kernels (nn_conv_patch.h)
-    static const bool no_patch = getenv("ZS_CONV_NO_PATCH") != nullptr;          // A/B switch for measurements
-    const bool patch_geom = f16 && a.w_split && !no_patch && kh == 3 && kw == 3 && stride == 1 && a.dil == 1 && pad_t == 1 &&
-                            pad_l == 1 && Hin == Hout && Win == Wout && (Cin % BK) == 0 && in_scale == 1.0f && in_shift == 0.0f &&
-                            !(flags & (ZS_CONV_FORCE_SMALL | ZS_CONV_FORCE_LARGE));
-    if (patch_geom && Cout <= 32 && Hout >= 8 && Wout >= 8) {
-        const int tx = (Wout + patch32::PT - 1) / patch32::PT, ty = (Hout + patch32::PT - 1) / patch32::PT;
-        const dim3 grid((unsigned)((long long)batch * tx * ty));
-        static const int nw = getenv("ZS_CONV_PATCH_WAVES") ? atoi(getenv("ZS_CONV_PATCH_WAVES")) : 8;      // A/B: 4 or 8
-        if (nw == 4) {
-            if (a.in_relu) hipLaunchKernelGGL((conv3x3_patch32_kernel<true, 4>), grid, dim3(256), 0, st, a, tx, ty);
-            else hipLaunchKernelGGL((conv3x3_patch32_kernel<false, 4>), grid, dim3(256), 0, st, a, tx, ty);
-        } else {
-            if (a.in_relu) hipLaunchKernelGGL((conv3x3_patch32_kernel<true, 8>), grid, dim3(512), 0, st, a, tx, ty);
-            else hipLaunchKernelGGL((conv3x3_patch32_kernel<false, 8>), grid, dim3(512), 0, st, a, tx, ty);
-        }
-        return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
-    }
-    static const long long patch_min = getenv("ZS_CONV_PATCH_MIN") ? atoll(getenv("ZS_CONV_PATCH_MIN")) : 192;
-    if (patch_geom && Cout > 32 && Hout >= 8 && Wout >= 8) {
-        const int tx = (Wout + patch128::TW - 1) / patch128::TW, ty = (Hout + patch128::TH - 1) / patch128::TH;
-        const long long wgs = (long long)batch * tx * ty * (a.CoutPad / BN);
-        // few tiles (14 x 14 maps at batch 28: 112; everything at batch 1): split the slabs across ~384 workgroups, partial
-        // tiles through the workspace, summed in range order by conv_splitk_reduce_kernel (which applies the epilogue)
-        static const long long split_target = getenv("ZS_CONV_PATCH_SPLIT_TARGET") ? atoll(getenv("ZS_CONV_PATCH_SPLIT_TARGET")) : 384;
-        static const long long split_min = getenv("ZS_CONV_PATCH_SPLIT_MIN") ? atoll(getenv("ZS_CONV_PATCH_SPLIT_MIN")) : 32;   // (64 until round 4: the 56 x 56 fusion layers at batch 1 - 50 workgroups - took the LDS-DMA kernel + split-K; batch 1 3.00 -> 2.95 ms)
-        long long sp = 1;
-        if (wgs < patch_min && workspace && wgs >= split_min) {
-            sp = (split_target + wgs - 1) / wgs;
-            const long long slabs = Cin / BK, cap = (long long)(WS_PARTS_BYTES / 4) / (M * (long long)Cout);
-            if (sp > slabs / 2) sp = slabs / 2;            // at least two slabs (18 tap-steps) per range
-            if (sp > cap) sp = cap;
-        }
-        if (wgs >= patch_min || sp > 1) {
-            a.splits = (int)(sp > 1 ? sp : 1);
-            static const bool xcd_map = getenv("ZS_CONV_PATCH_XCD") ? atoi(getenv("ZS_CONV_PATCH_XCD")) != 0 : true;
-            const long long mtiles = (long long)batch * tx * ty, ntl = a.CoutPad / BN;
-            dim3 grid((unsigned)mtiles, (unsigned)ntl, (unsigned)a.splits);
-            if (xcd_map && ntl > 1) {
-                a.sk_per = (int)ntl;
-                grid = dim3((unsigned)((mtiles + 7) / 8 * 8 * ntl), 1, (unsigned)a.splits);
-            }
-            if (a.in_relu) hipLaunchKernelGGL((conv3x3_patch128_kernel<true>), grid, dim3(256), 0, st, a, tx, ty);
-            else hipLaunchKernelGGL((conv3x3_patch128_kernel<false>), grid, dim3(256), 0, st, a, tx, ty);
-            if (a.splits > 1) {
-                const long long total = M * (long long)Cout;
-                const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-                hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a);
-            }
-            return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
-        }
-    }
-    // ---- large pointwise layers: 256 x 256 ping-pong tiles (nn_conv_pp256.h) ----
-    {
-        static const int pp_on = getenv("ZS_CONV_PP256") ? atoi(getenv("ZS_CONV_PP256")) : 1;
-        // (tools/bench_pp256.py, old -> new us: fc1 110 -> 97, qkv 91 -> 73, fc2 142 -> 95, 16,384 x 3,072 x 768 312 -> 236; it loses
-        // where a tile's K loop is short against its 256 KiB epilogue and one workgroup per CU cannot overlap the two: proj
-        // (66 tiles x K 768) 38 -> 44, K <= 512 everywhere)
-        static const long long pp_min_tiles = getenv("ZS_CONV_PP256_MIN_TILES") ? atoll(getenv("ZS_CONV_PP256_MIN_TILES")) : 48;
-        static const long long pp_min_k = getenv("ZS_CONV_PP256_MIN_K") ? atoll(getenv("ZS_CONV_PP256_MIN_K")) : 768;
-        static const long long pp_long_k = getenv("ZS_CONV_PP256_LONG_K") ? atoll(getenv("ZS_CONV_PP256_LONG_K")) : 2048;
-        static const int pp_max_split = getenv("ZS_CONV_PP256_MAX_SPLIT") ? atoi(getenv("ZS_CONV_PP256_MAX_SPLIT")) : 8;
-        static const int pp_min_steps = getenv("ZS_CONV_PP256_MIN_STEPS") ? atoi(getenv("ZS_CONV_PP256_MIN_STEPS")) : 4;
-        static const int cus = [] { int dev = 0, n = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-        const long long T = ((M + pp256::TM - 1) / pp256::TM) * ((a.CoutPad + pp256::TN - 1) / pp256::TN);
-        const bool pp_forced = (flags & ZS_CONV_FORCE_TILE256) != 0;
-        // ... and from K = 256 where the tiles make four rounds or more (the window stage of the transformer coordinate encoder at
-        // batch 28: 356,720 rows - qkv 770 -> 562 us, fc1 1,096 -> 695, fc2 807 -> 560, proj 272 -> 245; at 343 tiles the same K
-        // loses: 56 -> 68): over many rounds the XCDs drift apart and one tile's epilogue runs beside another's loop
-        static const long long pp_many_k = getenv("ZS_CONV_PP256_MANY_K") ? atoll(getenv("ZS_CONV_PP256_MANY_K")) : 256;
-        const bool pp_pays = pp_on && T >= pp_min_tiles &&
-                             ((a.K >= pp_min_k && (T >= cus / 2 || a.K >= pp_long_k)) || (a.K >= pp_many_k && T >= 4LL * cus));
-        if ((pp_forced || pp_pays) && pw && f16 && a.w_split && !fuse && (Cin % pp256::SK) == 0 && (Cout & 3) == 0 &&
-            !(flags & (ZS_CONV_FORCE_SMALL | ZS_CONV_FORCE_LARGE))) {
-            const long long steps = a.K / pp256::SK;
-            // the tail: tiles beyond the last whole round of the CUs (or all of them, when they fill less than half of one)
-            long long tail = T <= cus / 2 ? T : (T % cus < cus / 2 ? T % cus : 0), sp = 1;
-            if (T < cus && T > cus / 2) tail = 0;
-            if (tail && workspace) {
-                sp = cus / tail;
-                if (sp > pp_max_split) sp = pp_max_split;
-                if (sp > steps / pp_min_steps) sp = steps / pp_min_steps;
-                const long long cap = (long long)(WS_PARTS_BYTES / 4) / ((long long)pp256::TM * pp256::TN);
-                if (tail * sp > cap) sp = cap / tail;
-            }
-            if (sp < 2) { tail = 0; sp = 1; }
-            a.sk_per = (int)tail;
-            a.splits = (int)sp;
-            const dim3 grid((unsigned)(T - tail + tail * sp));
-            hipLaunchKernelGGL(pp256::conv_gemm_pp256_kernel, grid, dim3(512), 0, st, a);
-            if (tail) hipLaunchKernelGGL(pp256::pp256_tail_kernel, dim3(pp256::MI * pp256::NJ * 4, (unsigned)tail), dim3(512), 0, st, a);
-            return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
-        }
-    }
-    // few 128 x 128 tiles but a long contraction (3 x 3 768 -> 768 on 7 x 7 maps at batch 28: 66 tiles, 432 k-steps): the
-    // LDS-DMA kernel with the k-steps split across blockIdx.z, ~384 workgroups, >= 24 steps each
-    // (tools/conv_shapes.py + tools/bench_encoder.py, same box: batch 28 18.23 -> 17.89 ms - the 768 -> 768 head layers 156 ->
-    // 100 us; below ~40 tiles - the ViT fc2 at batch 1: 12 tiles - the reduce launch costs more than the ranges save)
-    static const long long dsplit_min_steps = getenv("ZS_CONV_DMA_SPLIT_MIN_STEPS") ? atoll(getenv("ZS_CONV_DMA_SPLIT_MIN_STEPS")) : 96;
-    static const long long dsplit_min_tiles = getenv("ZS_CONV_DMA_SPLIT_MIN_TILES") ? atoll(getenv("ZS_CONV_DMA_SPLIT_MIN_TILES")) : 40;
-    {
-        const bool pw_ = kh == 1 && kw == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && a.dil == 1 && !a.in_relu &&
-                         in_scale == 1.0f && in_shift == 0.0f && Hin == Hout && Win == Wout;
-        const bool dma_ok = f16 && a.w_split && (Cin % BK) == 0 && in_scale == 1.0f && in_shift == 0.0f && a.dil == 1 &&
-                            getenv("ZS_CONV_NO_DMA") == nullptr;
-        const long long ksteps = (a.K + BK - 1) / BK;
-        if (small && !(flags & ZS_CONV_FORCE_SMALL) && workspace && dma_ok && ksteps >= dsplit_min_steps && big_tiles >= dsplit_min_tiles) {
-            long long sp = (384 + big_tiles - 1) / big_tiles;
-            const long long cap = (long long)(WS_PARTS_BYTES / 4) / (M * (long long)Cout);
-            if (sp > ksteps / 24) sp = ksteps / 24;
-            if (sp > cap) sp = cap;
-            if (sp > 1) {
-                a.splits = (int)sp;
-                const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CoutPad / BN), (unsigned)sp);
-                if (pw_) hipLaunchKernelGGL((conv_gemm_dma_kernel<true, false, false, 3, 2>), grid, dim3(256), 0, st, a);
-                else if (a.in_relu) hipLaunchKernelGGL((conv_gemm_dma_kernel<false, true, false, 3, 2>), grid, dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((conv_gemm_dma_kernel<false, false, false, 3, 2>), grid, dim3(256), 0, st, a);
-                const long long total = M * (long long)Cout;
-                const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-                hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a);
-                return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
-            }
-        }
-    }
-    if (small) {
-        const bool tm = !pw && !no_tm && (Cin % 8) == 0;
-        const bool narrow = (fuse && fuse->out_mode == 2) ? zs_conv2d_fused_cols((int)M, Cout) == 32 : small_is_narrow(M, Cout);
-        // ---- pointwise layers of few rows: the streaming GEMM kernel (csrc/nn_gemm_stream.hip) ----
-        const bool pw_geom = kh == 1 && kw == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && a.dil == 1 && Hin == Hout && Win == Wout;
-        if (stream_enabled() && pw_geom && f16 && a.w_split && in_scale == 1.0f && in_shift == 0.0f && M <= stream_max_rows() &&
-            (!fuse || ((fuse->in_mode == 0 || fuse->in_mode == 2) && (fuse->out_mode == 0 || fuse->out_mode == 2)))) {
-            zs::stream_gemm::Args g;
-            g.a = in; g.w = packed_w; g.scale = scale; g.shift = shift; g.res1 = res1; g.res2 = res2; g.out = out;
-            g.M = (int)M; g.K = a.K; g.N = Cout; g.CoutPad = a.CoutPad; g.lda = Cin; g.act = act; g.in_relu = a.in_relu;
-            g.in_stats = fuse && fuse->in_mode == 2 ? fuse->in_stats : nullptr;
-            g.in_tiles = fuse ? fuse->in_tiles : 0;
-            g.in_eps = fuse ? fuse->in_eps : 0.f;
-            g.out_stats = fuse && fuse->out_mode == 2 ? fuse->out_stats : nullptr;
-            g.stats_cols = zs_conv2d_fused_cols((int)M, Cout);
-            g.parts = workspace ? static_cast<float *>(workspace) + WS_COUNTER_FLOATS : nullptr;
-            g.tickets = static_cast<int *>(workspace);
-            g.parts_bytes = WS_PARTS_BYTES;
-            g.max_tickets = (int)WS_COUNTER_FLOATS;
-            int ranges = 1;
-            g.two_launch_max = workspace && (Cout & 3) == 0 ? 4 : 1;
-            g.ranges = &ranges;
-            g.a_k16 = g.out_k16 = 0;
-            if (zs::stream_gemm::launch(g, st)) {
-                if (ranges > 1) {           // the kernel wrote raw partial sums of `ranges` K ranges: sum + epilogue (+ statistics) here
-                    a.splits = ranges;
-                    if (g.out_stats) {
-                        const int cols = g.stats_cols;
-                        const dim3 rgrid((unsigned)((M + SM - 1) / SM), (unsigned)((Cout + cols - 1) / cols));
-                        if (cols == 32) hipLaunchKernelGGL(conv_splitk_reduce_stats_kernel<1>, rgrid, dim3(256), 0, st, a);
-                        else hipLaunchKernelGGL(conv_splitk_reduce_stats_kernel<2>, rgrid, dim3(256), 0, st, a);
-                    } else {
-                        const long long total = M * (long long)Cout;
-                        const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-                        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a);
-                    }
-                }
-                return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
-            }
-        }
-        const long long wgs = ((M + SM - 1) / SM) * ((Cout + (narrow ? 31 : 63)) / (narrow ? 32 : 64));
-        // Split K across workgroups while the launch would leave most of the 256 CUs idle (14x14 maps,
-        // 197-token matrices at batch 1: 28-84 workgroups): ~512 workgroups, >= 16 t-steps (K = 128) per
-        // split, partial tiles inside the caller's workspace (zs_conv2d_splitk_workspace_bytes()).
-        static const int split_target = getenv("ZS_CONV_SPLIT_TARGET") ? atoi(getenv("ZS_CONV_SPLIT_TARGET")) : 512;
-        // ... and, whatever the caller's flag, layers with a LONG contraction on few workgroups (3 x 3 768 -> 768 on 7 x 7 maps at
-        // batch 1: 48 workgroups stream 21 MB of weights in 33.7 us): K >= ZS_CONV_SPLIT_LONG_K on <= ZS_CONV_SPLIT_LONG_WGS workgroups
-        // split towards ZS_CONV_SPLIT_LONG_TARGET workgroups.  Round 3 had tried the split everywhere at target 512 and found it a
-        // loss at batch 1; restricted to long contractions and with FEW ranges it pays (tools/enc_b1.py, batch-1 forward):
-        //   off 2.923 ms | K >= 6912: 2.838 | 4096: 2.844 | 2304: 2.792 (target 512) | 2304 at target 384 / 256 / 192: 2.785 / 2.787 /
-        //   2.726 | K >= 2048 at target 192 / 160 / 128 / 96: 2.712 / 2.717 / 2.752 / 2.788 | K >= 1024 at 160: 2.723
-        static const long long long_k = getenv("ZS_CONV_SPLIT_LONG_K") ? atoll(getenv("ZS_CONV_SPLIT_LONG_K")) : 2048;
-        static const long long long_wgs = getenv("ZS_CONV_SPLIT_LONG_WGS") ? atoll(getenv("ZS_CONV_SPLIT_LONG_WGS")) : 64;
-        static const int long_target = getenv("ZS_CONV_SPLIT_LONG_TARGET") ? atoi(getenv("ZS_CONV_SPLIT_LONG_TARGET")) : 192;
-        const bool flagged = (flags & ZS_CONV_SPLIT_SMALL) != 0;
-        // (fused layers too - their statistics are then written by conv_splitk_reduce_stats_kernel; the vector epilogue needs Cout % 4)
-        const bool long_split = workspace && (!fuse || (Cout & 3) == 0) && a.K >= long_k && wgs <= long_wgs;
-        if (workspace && (flagged || long_split) && wgs < 256) {
-            const int T = (a.K + BK - 1) / BK * 2;
-            const int target = flagged ? split_target : long_target;
-            long long sp = (target + wgs - 1) / wgs;
-            if (sp > T / 16) sp = T / 16;
-            if (sp > 16) sp = 16;
-            const long long cap = (long long)(WS_SPLITK_BYTES / 4) / (M * (long long)Cout);
-            if (sp > cap) sp = cap;
-            if (sp > 1) a.splits = (int)sp;
-        }
-        if (fuse && fuse->in_mode) {
-            // fused input normalisation: pointwise (in_mode 1, 2, 3) or tap-major plain (in_mode 1) geometry, split-fp16
-            if (!(pw || (tm && plain && fuse->in_mode == 1))) {
-                zs::set_err("zs_conv2d_nhwc_fused: in_mode %d needs a pointwise layer (or, for in_mode 1, Cin %% 8 == 0)", fuse->in_mode);
-                return 0;
-            }
-#define ZS_LAUNCH_XF(NJ_, XF_)                                                                                                 \
-    do {                                                                                                                       \
-        if (pw) hipLaunchKernelGGL((conv_gemm_small_kernel<NJ_, true, 0, false, true, XF_>), grid, dim3(256), 0, st, a);          \
-        else hipLaunchKernelGGL((conv_gemm_small_kernel<NJ_, false, 2, true, true, (XF_ == 1 ? 1 : 0)>), grid, dim3(256), 0, st, a); \
-    } while (0)
-            const dim3 grid((unsigned)((M + SM - 1) / SM), (unsigned)((Cout + (narrow ? 31 : 63)) / (narrow ? 32 : 64)), (unsigned)a.splits);
-            if (narrow) {
-                if (fuse->in_mode == 1) ZS_LAUNCH_XF(1, 1); else ZS_LAUNCH_XF(1, 2);
-            } else {
-                if (fuse->in_mode == 1) ZS_LAUNCH_XF(2, 1); else ZS_LAUNCH_XF(2, 2);
-            }
-#undef ZS_LAUNCH_XF
-        } else if (narrow) {
-            const dim3 grid((unsigned)((M + SM - 1) / SM), (unsigned)((Cout + 31) / 32), (unsigned)a.splits);
-            ZS_LAUNCH(conv_gemm_small_kernel, 1,);
-        } else {
-            const dim3 grid((unsigned)((M + SM - 1) / SM), (unsigned)((Cout + 63) / 64), (unsigned)a.splits);
-            ZS_LAUNCH(conv_gemm_small_kernel, 2,);
-        }
-        if (a.splits > 1) {
-            if (fuse && fuse->out_mode) {           // epilogue + statistics of the summed ranges, in the unsplit launch's layout
-                const dim3 rgrid((unsigned)((M + SM - 1) / SM), (unsigned)((Cout + (narrow ? 31 : 63)) / (narrow ? 32 : 64)));
-                if (narrow) hipLaunchKernelGGL(conv_splitk_reduce_stats_kernel<1>, rgrid, dim3(256), 0, st, a);
-                else hipLaunchKernelGGL(conv_splitk_reduce_stats_kernel<2>, rgrid, dim3(256), 0, st, a);
-            } else {
-                const long long total = M * (long long)Cout;
-                const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-                hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a);
-            }
-        }
-    } else {
-        const bool tm = !pw && !no_tm && (Cin % BK) == 0;
-        // Stream-K (ZS_CONV_STREAM_K + a workspace): a fixed number of workgroups share the (tile, k-step) space
-        // evenly, so a layer whose tile count is 1.03 x the number of CUs (ViT fc2 / proj at batch 28: 264 tiles)
-        // does not run a second, almost empty round.  Whole multiples of the machine keep one tile per workgroup.
-        static const int sk_wgs = getenv("ZS_CONV_SK_WGS") ? atoi(getenv("ZS_CONV_SK_WGS")) : 512;
-        const long long ksteps = (a.K + BK - 1) / BK, iters = big_tiles * ksteps;
-        // (for the 128 x 128 kernels only where one round would leave most of the 768 slots empty and K is long:
-        // elsewhere the kernels are bound by the bytes they move, a short last round runs faster, and the exchange of
-        // shares costs more than the balance gains - measured, tools/conv_ns.sh)
-        static const bool sk_env = getenv("ZS_CONV_SK_ALWAYS") != nullptr;
-        const bool sk_always = sk_env || (flags & ZS_CONV_STREAM_K_ALWAYS);
-        const bool sk = workspace && (flags & ZS_CONV_STREAM_K) && sk_wgs >= 1 && sk_wgs <= SK_MAX_WGS &&
-                        big_tiles <= (long long)WS_COUNTER_FLOATS && iters < (1LL << 30) && iters >= 4LL * sk_wgs &&
-                        (sk_always || (big_tiles * 2 <= sk_wgs && ksteps >= 128));
-        // split-fp16 with pre-split weights, pointwise or tap-major geometry, no input scale / shift: the LDS-DMA
-        // pipelined kernel (ZS_CONV_NO_DMA=1: the register-staged one, for A/B measurements)
-        static const bool no_dma = getenv("ZS_CONV_NO_DMA") != nullptr;
-        const bool dma = f16 && a.w_split && !no_dma && (pw || tm) && in_scale == 1.0f && in_shift == 0.0f && (Cin % BK) == 0;
-        // ZS_CONV_SLAB_MAJOR=1: kh x kw layers walk K slab-major (SlabWalk).  OFF: measured slower (see SlabWalk)
-        static const bool slab_major = getenv("ZS_CONV_SLAB_MAJOR") && atoi(getenv("ZS_CONV_SLAB_MAJOR")) != 0;
-        a.slab_major = dma && !pw && slab_major && a.kh * a.kw > 1 ? 1 : 0;
-        // Variants kept for A/B runs, all measured inside the batch-28 encoder (tools/conv_shapes.py, 19.8 ms of
-        // GEMM time with the default): ZS_CONV_DMA_MI=4 = 256 x 128 workgroup tiles (wave tile 128 x 64, two workgroups
-        // per CU, 25 % fewer bytes through LDS per MFMA): SLOWER, 21.1 ms (3x3 476 vs 425 us, fc1 179 vs 140 us);
-        // ZS_CONV_DMA_NS=2 = two stages, four workgroups per CU, one step of lead: the same, 19.7 ms.  Fewer bytes with
-        // fewer loads in flight loses; more workgroups with less lead changes nothing.
-        static const int dma_mi = getenv("ZS_CONV_DMA_MI") ? atoi(getenv("ZS_CONV_DMA_MI")) : 2;
-        const long long tall_tiles = ((M + 255) / 256) * (a.CoutPad / BN);
-        const bool tall = dma_mi == 4 && tall_tiles >= 1;
-        // 64 x 128 tiles (MI = 1, four workgroups per CU) where 128-row tiles give most CUs a single workgroup - ViT fc2 /
-        // proj at batch 28: 264 tiles on 256 CUs, four waves per CU.  tools/conv_shapes.py, batch 28, threshold 0 / 300 / 600 / 1200:
-        // 17.17 / 16.83 / 16.44 / 16.94 ms of convolutions (fc2 167 -> 148 us, proj 73 -> 55, the 344-tile 1x1 layers 43 -> 32)
-        static const long long half_below = getenv("ZS_CONV_HALF_BELOW") ? atoll(getenv("ZS_CONV_HALF_BELOW")) : 600;
-        const bool half_tall = dma_mi == 1 || (dma_mi == 2 && big_tiles < half_below);
-#define ZS_LAUNCH_DMA1(SKF, NS, MI_)                                                                                     \
-    do {                                                                                                                 \
-        if (pw) hipLaunchKernelGGL((conv_gemm_dma_kernel<true, false, SKF, NS, MI_>), grid, dim3(256), 0, st, a);         \
-        else if (a.in_relu) hipLaunchKernelGGL((conv_gemm_dma_kernel<false, true, SKF, NS, MI_>), grid, dim3(256), 0, st, a); \
-        else hipLaunchKernelGGL((conv_gemm_dma_kernel<false, false, SKF, NS, MI_>), grid, dim3(256), 0, st, a);           \
-    } while (0)
-        static const int dma_ns = getenv("ZS_CONV_DMA_NS") ? atoi(getenv("ZS_CONV_DMA_NS")) : 3;
-#define ZS_LAUNCH_DMA(SKF)                              \
-    do {                                                \
-        if (dma_ns == 2) ZS_LAUNCH_DMA1(SKF, 2, 2);     \
-        else ZS_LAUNCH_DMA1(SKF, 3, 2);                 \
-    } while (0)
-        // 256 x 256 tiles over 256 persistent workgroups (layers with >= 192 output channels): OPT-IN
-        // (ZS_CONV_256_MIN_KSTEPS=128 selects it for K >= 2048).  Run back to back on hot caches it beats the
-        // 128 x 128 kernel on the long contractions (tools/conv_ns.sh, batch 28: ViT fc2 152 vs 177 us, 3x3 256 -> 256
-        // at 56 x 56 419 vs 476 us; fc1 158 vs 142, proj 95 vs 57: the exchange of 256 KiB tile shares), but inside
-        // the encoder, where every layer's input has just been written, it loses everywhere (tools/conv_shapes.py:
-        // fc2 242 vs 195 us, the 3x3 462 vs 424 us): one workgroup per CU has a third of the loads in flight.
-        static const bool no_256 = getenv("ZS_CONV_NO_256") != nullptr;
-        static const long long min_ksteps_256 = getenv("ZS_CONV_256_MIN_KSTEPS") ? atoll(getenv("ZS_CONV_256_MIN_KSTEPS")) : (1LL << 40);
-        const long long tiles2 = ((M + TM2 - 1) / TM2) * ((a.CoutPad + TN2 - 1) / TN2), iters2 = tiles2 * ksteps;
-        if (dma && workspace && (flags & ZS_CONV_STREAM_K) && !no_256 && Cout >= 192 && (ksteps >= min_ksteps_256 || sk_always) && iters2 >= 8LL * 256 &&
-            iters2 < (1LL << 30) && tiles2 <= (long long)WS_COUNTER_FLOATS) {
-            a.sk_per = (int)((iters2 + 255) / 256);
-            const dim3 grid((unsigned)((iters2 + a.sk_per - 1) / a.sk_per));
-            if (pw) hipLaunchKernelGGL((conv_gemm_dma256_kernel<true, false>), grid, dim3(512), 0, st, a);
-            else if (a.in_relu) hipLaunchKernelGGL((conv_gemm_dma256_kernel<false, true>), grid, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((conv_gemm_dma256_kernel<false, false>), grid, dim3(512), 0, st, a);
-        } else if (sk) {
-            a.sk_per = (int)((iters + sk_wgs - 1) / sk_wgs);
-            const dim3 grid((unsigned)((iters + a.sk_per - 1) / a.sk_per));
-            if (dma) ZS_LAUNCH_DMA(true);
-            else if (f16) ZS_LAUNCH_BIG(true, true);
-            else ZS_LAUNCH_BIG(false, true);
-        } else if (dma && tall) {
-            const dim3 grid((unsigned)((M + 255) / 256), (unsigned)(a.CoutPad / BN));
-            ZS_LAUNCH_DMA1(false, 3, 4);
-        } else if (dma && half_tall) {
-            const dim3 grid((unsigned)((M + 63) / 64), (unsigned)(a.CoutPad / BN));
-            ZS_LAUNCH_DMA1(false, 3, 1);
-        } else {
-            const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CoutPad / BN));
-            if (dma) ZS_LAUNCH_DMA(false);
-            else if (f16) ZS_LAUNCH_BIG(true, false);
-            else ZS_LAUNCH_BIG(false, false);
-        }
-#undef ZS_LAUNCH_DMA
-#undef ZS_LAUNCH_DMA1
-    }
-#undef ZS_LAUNCH_BIG
-#undef ZS_LAUNCH
-#undef ZS_LAUNCH1
-    return zs::check_launch("zs_conv2d_nhwc") ? 1 : 0;
+    // (a workspace is always there in the inference engine)
+    return zs::stream_gemm::launch(stream_args(a, flags, dummy, &ranges), nullptr, true) ? 1 : 0;
 }
 
 extern "C" int zs_conv3x3_tail_nhwc(const float *in, const float *packed_w, const float *scale, const float *shift, float *out,
@@ -2082,26 +1653,13 @@ extern "C" int zs_conv3x3_tail_nhwc(const float *in, const float *packed_w, cons
     if (!in || !packed_w || !out || !tail_w) { zs::set_err("zs_conv3x3_tail_nhwc: null pointer"); return 0; }
     const long long M = (long long)batch * H * W;
     if (M > (1LL << 30)) { zs::set_err("zs_conv3x3_tail_nhwc: %lld output pixels", M); return 0; }
-    ConvArgs a;
-    a.slab_major = 0;
-    memset(&a.fz, 0, sizeof a.fz);
-    a.fz_tiles_per_sample = 0;
-    a.in = in; a.w = packed_w; a.scale = scale; a.shift = shift; a.res1 = nullptr; a.res2 = nullptr; a.out = out;
     const bool up2 = (flags & ZS_CONV_IN_UPSAMPLE2) != 0;
-    a.B = batch; a.Hin = up2 ? H / 2 : H; a.Win = up2 ? W / 2 : W; a.Cin = Cin; a.Hout = H; a.Wout = W; a.Cout = Cout;
-    a.CoutPad = (Cout + BN - 1) / BN * BN;
-    a.kh = 3; a.kw = 3; a.stride = 1; a.pad_t = 1; a.pad_l = 1; a.K = 9 * Cin; a.M = (int)M;
-    a.in_relu = (flags & ZS_CONV_IN_RELU) ? 1 : 0;
-    a.act = act; a.in_scale = 1.0f; a.in_shift = 0.0f; a.dil = 1; a.ws = nullptr; a.splits = 1; a.sk_per = 0; a.w_split = 1;
+    ConvArgs a;
+    fill_conv_args(a, in, packed_w, scale, shift, nullptr, nullptr, out, batch, up2 ? H / 2 : H, up2 ? W / 2 : W, Cin, H, W, Cout, 3, 3, 1,
+                   1, 1, flags, 1.0f, 0.0f, act, nullptr);
     a.tail_w = tail_w; a.tail_b = tail_b; a.tail_act = tail_act;
-    const int tx = (W + patch32::PT - 1) / patch32::PT, ty = (H + patch32::PT - 1) / patch32::PT;
-    const dim3 grid((unsigned)((long long)batch * tx * ty));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (up2) {
-        if (a.in_relu) hipLaunchKernelGGL((conv3x3_patch32_kernel<true, 8, true>), grid, dim3(512), 0, st, a, tx, ty);
-        else hipLaunchKernelGGL((conv3x3_patch32_kernel<false, 8, true>), grid, dim3(512), 0, st, a, tx, ty);
-    } else if (a.in_relu) hipLaunchKernelGGL((conv3x3_patch32_kernel<true, 8>), grid, dim3(512), 0, st, a, tx, ty);
-    else hipLaunchKernelGGL((conv3x3_patch32_kernel<false, 8>), grid, dim3(512), 0, st, a, tx, ty);
+    if (up2) launch_patch32<true>(a, static_cast<hipStream_t>(stream));
+    else launch_patch32(a, static_cast<hipStream_t>(stream));
     return zs::check_launch("zs_conv3x3_tail_nhwc") ? 1 : 0;
 }
 

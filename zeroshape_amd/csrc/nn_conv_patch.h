@@ -365,14 +365,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
     const f32x4 *zero = zs_zero_page;
 
     const int per_image = tiles_x * tiles_y;
-    // a.sk_per = number of column tiles when the launch is 1-D and XCD-aware: workgroup L runs on XCD L % 8 (round-robin
+    // a.xcd_ntiles = number of column tiles when the launch is 1-D and XCD-aware: workgroup L runs on XCD L % 8 (round-robin
     // dispatch), so the column tiles of one pixel tile are given consecutive slots of ONE XCD - the second one finds the patch in
     // that XCD's L2 - and consecutive pixel tiles (shared halos) go round the XCDs as before.  0: grid (pixel tiles, column tiles)
     int mt = (int)blockIdx.x, nt = (int)blockIdx.y;
-    if (a.sk_per > 0) {
+    if (a.xcd_ntiles > 0) {
         const int k = (int)blockIdx.x >> 3;
-        nt = k % a.sk_per;
-        mt = (k / a.sk_per) * 8 + ((int)blockIdx.x & 7);
+        nt = k % a.xcd_ntiles;
+        mt = (k / a.xcd_ntiles) * 8 + ((int)blockIdx.x & 7);
         if (mt >= a.B * per_image) return;
     }
     const int b = mt / per_image, trem = mt - b * per_image;

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(512) void conv_gemm_pp256_kernel(ConvArgs a) {
     // workgroup -> unit.  Units [0, full) are whole tiles, dealt so that each XCD (workgroup b runs on XCD b % 8) owns a
     // contiguous run of them (bijective for any count); units beyond are the K ranges of the tail tiles, round-robin over the
     // XCDs as dispatched: unit full + s * tail + tt = range s of tail tile tt
-    const int full = ntiles - a.sk_per;                           // a.sk_per = number of tail tiles, a.splits = ranges per tail tile
+    const int full = ntiles - a.tail_tiles;                           // a.tail_tiles = number of tail tiles, a.splits = ranges per tail tile
     int tile, t_lo = 0, steps = steps_all, range = -1;
     if ((int)blockIdx.x < full) {
         const int xcd = (int)blockIdx.x & 7, q8 = full >> 3, r8 = full & 7;
@@ -63,8 +63,8 @@ __global__ __launch_bounds__(512) void conv_gemm_pp256_kernel(ConvArgs a) {
             const int nu = (int)gridDim.x, xcd = u & 7, q8 = nu >> 3, r8 = nu & 7;
             u = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (u >> 3);
         }
-        tile = full + u % a.sk_per;
-        range = u / a.sk_per;
+        tile = full + u % a.tail_tiles;
+        range = u / a.tail_tiles;
         t_lo = (int)(((long long)range * steps_all) / a.splits);
         steps = (int)(((long long)(range + 1) * steps_all) / a.splits) - t_lo;
     }
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(512) void conv_gemm_pp256_kernel(ConvArgs a) {
 __global__ __launch_bounds__(512) void pp256_tail_kernel(ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
     const int slot = blockIdx.x, q = slot & 3, j = (slot >> 2) % NJ, i = slot / (4 * NJ);
-    const int ntn = (a.CoutPad + TN - 1) / TN, ntm = (a.M + TM - 1) / TM, full = ntm * ntn - a.sk_per;
+    const int ntn = (a.CoutPad + TN - 1) / TN, ntm = (a.M + TM - 1) / TM, full = ntm * ntn - a.tail_tiles;
     const int tile = full + blockIdx.y;
     const int m = (tile / ntn) * TM + (wave & 3) * 64 + 32 * i + l32;
     const int n = (tile % ntn) * TN + (wave >> 2) * 128 + 32 * j + 8 * q + 4 * half;

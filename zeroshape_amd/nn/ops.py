@@ -13,7 +13,8 @@ from .pack import out_size
 # zs_act_backward only.
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_CLAMP1, ACT_SOFTPLUS = 0, 1, 2, 3, 4
 CONV_IN_RELU, CONV_FORCE_LARGE, CONV_FORCE_SMALL, CONV_IN_DILATE2, CONV_F16X3 = 1, 2, 4, 8, 16
-CONV_SPLIT_SMALL, CONV_STREAM_K, CONV_W_PRESPLIT, CONV_STREAM_K_ALWAYS = 32, 64, 128, 256
+CONV_SPLIT_SMALL, CONV_W_PRESPLIT = 32, 128
+CONV_RETIRED_64, CONV_RETIRED_256 = 64, 256         # retired bits: the library refuses a call that sets either
 CONV_IN_UPSAMPLE2, CONV_FORCE_TILE256, CONV_OUT_K16, CONV_IN_K16 = 512, 1024, 2048, 4096
 
 
@@ -40,13 +41,6 @@ CONV_PRECISION = os.environ.get("ZS_ENCODER_PRECISION", "f16x3")
 SPLIT_K = os.environ.get("ZS_CONV_SPLIT_K", "0") != "0"
 # (The workspace itself is always passed: the 3x3 input-patch kernels and the LDS-DMA kernel split the contraction of layers
 # with few tiles through it by their own rules - csrc/nn_conv.hip, round 3.)
-# Stream-K for the large-tile launches (ZS_CONV_STREAM_K): a fixed number of workgroups share the (tile, k-step)
-# space evenly instead of one tile each.  Built, tested (test_conv2d_stream_k) and OFF by default: measured inside the
-# batch-28 encoder (tools/conv_shapes.py) the large-tile kernels are bound by the bytes they pull into LDS, a short
-# last round simply runs faster, and the exchange of tile shares costs more than the balance gains (22.9 vs 20.6 ms
-# of convolution time with it everywhere).  ZS_CONV_STREAM_K=1 enables the kernel's own shape rule,
-# "always" (tests) forces it wherever supported.
-STREAM_K = {"0": False, "1": True, "always": "always"}[os.environ.get("ZS_CONV_STREAM_K", "0")]
 # f16x3: the weights' fp16 halves are computed once per layer (zs_conv2d_presplit_weight) instead of in every
 # workgroup of every launch.  ZS_CONV_PRESPLIT=0: split at run time (A/B measurements).
 PRESPLIT = os.environ.get("ZS_CONV_PRESPLIT", "1") != "0"
@@ -84,8 +78,7 @@ def splitk_workspace(device):
 
 
 def conv_flags():
-    return (CONV_F16X3 if CONV_PRECISION == "f16x3" else 0) | (CONV_SPLIT_SMALL if SPLIT_K else 0) | \
-        (CONV_STREAM_K if STREAM_K else 0) | (CONV_STREAM_K_ALWAYS if STREAM_K == "always" else 0)
+    return (CONV_F16X3 if CONV_PRECISION == "f16x3" else 0) | (CONV_SPLIT_SMALL if SPLIT_K else 0)
 
 
 class Stats:
