@@ -87,6 +87,59 @@ def test_argument_errors_are_reported_without_touching_the_gpu(lib):
     assert lib.zs_sdf_query_points(None, 0, 0, None, 5, None, None, None, None, None) == 1
 
 
+def test_decoder_query_arguments_are_checked_before_anything_is_touched(lib):
+    """All six zs_sdf_query_* entry points, both arithmetics: 0 + a message that starts with the called entry point's own
+    name, or 1 for an empty problem - before any pointer is dereferenced or anything is launched (a 64-byte host buffer
+    stands in for every non-null pointer)."""
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    pb = lib.zs_sdf_program_bytes()
+
+    def fails(name, call, what):
+        assert call == 0, (name, what)
+        msg = lib.zs_last_error()
+        assert msg.startswith(name.encode() + b": ") and what.encode() in msg, (name, what, msg)
+
+    for name in ("zs_sdf_query_points", "zs_sdf_query_points_split"):
+        fn = getattr(lib, name)
+        opt = (None,) if name == "zs_sdf_query_points" else ()        # (the attention map of the fp32 form)
+
+        def points(prog, stride, batch, m, data):
+            return fn(prog, stride, batch, data, m, data, *opt, None, data, None)
+
+        fails(name, points(p, pb, -1, 5, p), "negative size")
+        fails(name, points(p, pb, 2, -5, p), "negative size")
+        assert points(None, 0, 0, 5, None) == 1 and points(None, 0, 2, 0, None) == 1
+        fails(name, points(p, pb, 2, 300, None), "null pointer")
+        fails(name, points(None, pb, 2, 300, p), "null pointer")
+        fails(name, points(p, pb + 8, 2, 300, p), "bad program stride")
+        fails(name, points(p, pb - 16, 2, 300, p), "bad program stride")
+        fails(name, points(p, pb, 200, 2 ** 31 - 1, p), "too many tiles")
+
+    # G = 9: slices of 81 points, 729 points
+    forms = [("zs_sdf_query_grid", 9, 10, "split the slab", 2048), ("zs_sdf_query_grid_split", 9, 10, "split the slab", 2048),
+             ("zs_sdf_query_grid_range", 729, 730, "split the range", 2048 ** 3),
+             ("zs_sdf_query_grid_range_split", 729, 730, "split the range", 2048 ** 3)]
+    for name, whole, past, hint, whole_2048 in forms:
+        fn = getattr(lib, name)
+
+        def grid(prog, stride, batch, G, begin, end, data):
+            return fn(prog, stride, batch, data, G, begin, end, 1, data, None, data, None)
+
+        fails(name, grid(p, pb, -1, 9, 0, whole, p), "bad range")
+        fails(name, grid(p, pb, 2, 0, 0, 0, p), "bad range")
+        fails(name, grid(p, pb, 2, 9, 3, 2, p), "bad range")
+        fails(name, grid(p, pb, 2, 9, 0, past, p), "bad range")
+        fails(name, grid(p, pb, 2, 9, -1, whole, p), "bad range")
+        assert grid(None, 0, 0, 9, 0, whole, None) == 1 and grid(None, 0, 2, 9, 4, 4, None) == 1
+        fails(name, grid(p, pb, 2, 9, 0, whole, None), "null pointer")
+        fails(name, grid(None, pb, 2, 9, 0, whole, p), "null pointer")
+        fails(name, grid(p, pb + 8, 2, 9, 0, whole, p), "bad program stride")
+        fails(name, grid(p, pb - 16, 2, 9, 0, whole, p), "bad program stride")
+        fails(name, grid(p, pb, 1, 2048, 0, whole_2048, p), "exceed 2^31")
+        assert hint.encode() in lib.zs_last_error()
+
+
 def test_product_path_fails_loudly_without_library(monkeypatch):
     from zeroshape_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

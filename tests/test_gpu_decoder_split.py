@@ -493,6 +493,25 @@ def test_per_image_check_sends_an_outlier_image_to_the_exact_kernels():
     assert torch.equal(m.query_grid(lat, axis, apply_sigmoid=False, state=st0), g)
 
 
+def test_calibration_and_image_check_leave_the_callers_tile_flags_and_guard():
+    """The calibration and the per-image check of prepare() measure the raw split arithmetic through the query path: that
+    must neither replace the caller's last_tile_flags nor touch envelope_guard.  Batch 2 x 300 points: two full 128-point
+    tiles and a 44-point tail per image."""
+    m, _ = _scaled_net(3, 1.0)
+    m.precision, m.calibrate, m.image_check = "f16x3", True, True
+    latent = torch.from_numpy(syn.seeded_latent(seed=3, batch=2)).cuda()
+    pts = torch.from_numpy(syn.seeded_cloud(91, 2, 300, -1.5, 1.5)).cuda()
+    m.query_points(m.prepare(latent, calibrate=False), pts)          # guarded split query
+    kept = m.last_tile_flags
+    assert kept is not None and kept.shape == (2 * 3,)
+    # other weights, their first call: _calibrate and _image_check both run
+    m.load_state_dict(_scaled_net(5, 1.0)[1], strict=True)
+    assert m._calibration is None
+    st = m.prepare(latent)
+    assert st.precision == "f16x3" and st.image_flags is not None and m._calibration is not None
+    assert m.last_tile_flags is kept and m.envelope_guard is True
+
+
 def test_verdict_statistics_of_both_output_spaces(net):
     """Implicit._verdict_stats (one launch of zs_sdf_verdict_stats per check): a confident network's raw error fails the raw
     rule while its occupancies agree; a flip counts only outside the band; a non-finite value fails both rules; the numbers

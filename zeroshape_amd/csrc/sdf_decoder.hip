@@ -26,6 +26,7 @@
 #include "zs_common.h"
 #include "sdf_layout.h"
 #include "sdf_math.h"
+#include "sdf_query.h"
 #include "../../include/zeroshape_hip.h"
 
 #include <math.h>
@@ -34,20 +35,16 @@
 namespace {
 
 using namespace zs::lay;
+using namespace zs::qry;    // tile geometry, workspace layout, argument checks
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int WAVES = 4;
-constexpr int PTS_PER_WAVE = 32;
-constexpr int PTS_PER_BLOCK = WAVES * PTS_PER_WAVE;
-constexpr int MAX_WGS = 256;                       // one persistent workgroup per CU
 constexpr int SLAB_F4 = NT * 4 * 64;               // one activation array as float4 groups: 32 KiB
-constexpr int ZSLAB_F4 = 3 * SLAB_F4;              // three skip layers' feat partial products
+static_assert(ZSLAB_F4 == 3 * SLAB_F4, "the workspace slab holds three skip layers' feat partial products");
 constexpr int ATTN_P_F4 = BLOCKS * HEADS * LT * 4 * 64;      // raw P tiles per wave tile (float4)
 constexpr int ATTN_ST_F = BLOCKS * HEADS * 9 * 64;          // 7 reference maxima + final max + 1/Z per lane
 constexpr int ATTN_WT_F4 = ATTN_P_F4 + ATTN_ST_F / 4;       // per wave tile
-constexpr size_t WORKSPACE_BYTES = (size_t)MAX_WGS * WAVES * ZSLAB_F4 * sizeof(f32x4) + 4096;  // + debug tail
 
 #define DEV __device__ __forceinline__
 
@@ -710,7 +707,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(240))
         const f32x4 *recs = uniform_ptr(reinterpret_cast<const f32x4 *>(prog));
 #ifdef ZS_EXP_TIMING
         unsigned long long *dbg = (blockIdx.x == 0 && threadIdx.x == 0 && tile == 0)
-            ? reinterpret_cast<unsigned long long *>(workspace + (size_t)MAX_WGS * WAVES * ZSLAB_F4) : nullptr;
+            ? timing_stamps(workspace) : nullptr;
 #else
         unsigned long long *dbg = nullptr;
 #endif
@@ -752,9 +749,16 @@ __global__ __launch_bounds__(256) void attn_reduce_kernel(const f32x4 *__restric
     }
 }
 
-int decode_grid_size(int batch, int m) {
-    const long long tiles = (long long)batch * ((m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK);
-    return (int)(tiles < MAX_WGS ? tiles : MAX_WGS);
+// The one launch of sdf_decode_kernel over the query q.  `raw` non-null: the ATTN variant of a point list, which also dumps
+// its raw attention tiles there (and takes no tile mask).
+void launch_decode(const void *programs, size_t program_stride_bytes, int batch, const Query &q, float *out, f32x4 *raw,
+                   const int *tile_mask, void *workspace, hipStream_t st) {
+    auto *kernel = raw ? sdf_decode_kernel<false, true> : q.points ? sdf_decode_kernel<false, false>
+                                                                   : sdf_decode_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(decode_grid_size(batch, q.m)), dim3(WAVES * 64), 0, st,
+                       static_cast<const float *>(programs), program_stride_bytes / sizeof(float), batch, q.points, q.axis,
+                       q.G, q.first_point, q.m, out, q.apply_sigmoid, static_cast<f32x4 *>(workspace), raw,
+                       raw ? nullptr : tile_mask);
 }
 
 // ---- z-mean attention of grid columns (the demo's heat-map GIF, utils/eval_3D.py:47-80) ---------- //
@@ -917,10 +921,7 @@ extern "C" int zs_sdf_grid_attn_zmean(const void *programs, size_t program_strid
         zs::set_err("zs_sdf_grid_attn_zmean: null pointer");
         return 0;
     }
-    if (program_stride_bytes % 16 != 0 || program_stride_bytes < zs_sdf_program_bytes()) {
-        zs::set_err("zs_sdf_grid_attn_zmean: bad program stride %zu", program_stride_bytes);
-        return 0;
-    }
+    if (!check_programs("zs_sdf_grid_attn_zmean", programs, program_stride_bytes)) return 0;
     if (reinterpret_cast<uintptr_t>(scratch) % 16 != 0) {
         zs::set_err("zs_sdf_grid_attn_zmean: scratch must be 16-byte aligned");
         return 0;
@@ -940,9 +941,8 @@ extern "C" int zs_sdf_grid_attn_zmean(const void *programs, size_t program_strid
             const long long n_pts = (long long)imgs * m;
             hipLaunchKernelGGL(column_points_kernel, dim3((int)((n_pts + 255) / 256 < 1024 ? (n_pts + 255) / 256 : 1024)),
                                dim3(256), 0, st, axis, G, columns + 2 * (size_t)col0, cols, p.zt, imgs, points);
-            hipLaunchKernelGGL((sdf_decode_kernel<false, true>), dim3(decode_grid_size(imgs, m)), dim3(WAVES * 64), 0,
-                               st, prog, program_stride_bytes / sizeof(float), imgs, points, nullptr, 0, 0LL, m, logits,
-                               0, static_cast<f32x4 *>(workspace), raw, nullptr);
+            launch_decode(prog, program_stride_bytes, imgs, Query{points, nullptr, 0, 0LL, m, 0}, logits, raw, nullptr,
+                          workspace, st);
             hipLaunchKernelGGL(attn_zmean_kernel, dim3(imgs * cols * LT), dim3(256), 0, st, raw,
                                zmean + ((size_t)img0 * n_cols + col0) * L, cols, n_cols, tiles_per_img, p.zt, G);
         }
@@ -961,108 +961,53 @@ extern "C" size_t zs_sdf_attn_scratch_bytes(int batch, int m) {
 extern "C" int zs_sdf_query_points(const void *programs, size_t program_stride_bytes, int batch,
                                    const float *points, int m, float *logits, float *attn,
                                    const int *tile_mask, void *workspace, void *stream) {
-    if (batch < 0 || m < 0) {
-        zs::set_err("zs_sdf_query_points: negative size (batch=%d m=%d)", batch, m);
-        return 0;
-    }
-    if (batch == 0 || m == 0) return 1;
-    if (!programs || !points || !logits || !workspace) {
-        zs::set_err("zs_sdf_query_points: null pointer");
-        return 0;
-    }
-    if (program_stride_bytes % 16 != 0 || program_stride_bytes < zs_sdf_program_bytes()) {
-        zs::set_err("zs_sdf_query_points: bad program stride %zu", program_stride_bytes);
-        return 0;
-    }
-    if ((long long)batch * ((m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK) > 0x7fffffffLL) {
-        zs::set_err("zs_sdf_query_points: too many tiles");
+    static const char who[] = "zs_sdf_query_points";
+    Query q;
+    if (!points_query(who, programs, program_stride_bytes, batch, points, m, logits, workspace, q)) return 0;
+    if (q.m == 0) return 1;
+    if (attn && tile_mask) {
+        zs::set_err("%s: the attention map cannot be combined with a tile mask", who);
         return 0;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!attn) {
-        hipLaunchKernelGGL((sdf_decode_kernel<false, false>), dim3(decode_grid_size(batch, m)),
-                           dim3(WAVES * 64), 0, st, static_cast<const float *>(programs),
-                           program_stride_bytes / sizeof(float), batch, points, nullptr, 0, 0LL, m, logits,
-                           0, static_cast<f32x4 *>(workspace), nullptr, tile_mask);
-    } else {
-        if (tile_mask) {
-            zs::set_err("zs_sdf_query_points: the attention map cannot be combined with a tile mask");
-            return 0;
-        }
-        // raw tiles live behind the fixed part of the workspace (zs_sdf_attn_scratch_bytes)
-        f32x4 *raw = reinterpret_cast<f32x4 *>(static_cast<char *>(workspace) + WORKSPACE_BYTES);
-        hipLaunchKernelGGL((sdf_decode_kernel<false, true>), dim3(decode_grid_size(batch, m)),
-                           dim3(WAVES * 64), 0, st, static_cast<const float *>(programs),
-                           program_stride_bytes / sizeof(float), batch, points, nullptr, 0, 0LL, m, logits,
-                           0, static_cast<f32x4 *>(workspace), raw, nullptr);
+    // raw tiles live behind the fixed part of the workspace (zs_sdf_attn_scratch_bytes)
+    f32x4 *raw = attn ? reinterpret_cast<f32x4 *>(static_cast<char *>(workspace) + WORKSPACE_BYTES) : nullptr;
+    launch_decode(programs, program_stride_bytes, batch, q, logits, raw, tile_mask, workspace, st);
+    if (attn) {
         const long long total = (long long)batch * m * L;
         int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
         hipLaunchKernelGGL(attn_reduce_kernel, dim3(blocks), dim3(256), 0, st, raw, attn, batch, m);
     }
-    return zs::check_launch("zs_sdf_query_points") ? 1 : 0;
+    return zs::check_launch(who) ? 1 : 0;
 }
 
 extern "C" int zs_sdf_query_grid_range(const void *programs, size_t program_stride_bytes, int batch,
                                        const float *axis, int G, long long point_begin,
                                        long long point_end, int apply_sigmoid, float *out,
                                        const int *tile_mask, void *workspace, void *stream) {
-    const long long P = (long long)G * G * G;
-    if (batch < 0 || G <= 0 || point_begin < 0 || point_end > P || point_begin > point_end) {
-        zs::set_err("zs_sdf_query_grid_range: bad range (batch=%d G=%d points=[%lld,%lld))", batch, G,
-                    point_begin, point_end);
+    static const char who[] = "zs_sdf_query_grid_range";
+    Query q;
+    if (!grid_range_query(who, "range", programs, program_stride_bytes, batch, axis, G, point_begin, point_end,
+                          apply_sigmoid, out, workspace, q))
         return 0;
-    }
-    const long long mm = point_end - point_begin;
-    if (batch == 0 || mm == 0) return 1;
-    if (!programs || !axis || !out || !workspace) {
-        zs::set_err("zs_sdf_query_grid_range: null pointer");
-        return 0;
-    }
-    if (mm > 0x7fffffffLL - PTS_PER_BLOCK) {
-        zs::set_err("zs_sdf_query_grid_range: %lld points per launch exceed 2^31; split the range", mm);
-        return 0;
-    }
-    if (program_stride_bytes % 16 != 0 || program_stride_bytes < zs_sdf_program_bytes()) {
-        zs::set_err("zs_sdf_query_grid_range: bad program stride %zu", program_stride_bytes);
-        return 0;
-    }
-    const int m = (int)mm;
-    hipLaunchKernelGGL((sdf_decode_kernel<true, false>), dim3(decode_grid_size(batch, m)),
-                       dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const float *>(programs), program_stride_bytes / sizeof(float), batch,
-                       nullptr, axis, G, point_begin, m, out, apply_sigmoid,
-                       static_cast<f32x4 *>(workspace), nullptr, tile_mask);
-    return zs::check_launch("zs_sdf_query_grid_range") ? 1 : 0;
+    if (q.m == 0) return 1;
+    launch_decode(programs, program_stride_bytes, batch, q, out, nullptr, tile_mask, workspace,
+                  static_cast<hipStream_t>(stream));
+    return zs::check_launch(who) ? 1 : 0;
 }
 
 extern "C" int zs_sdf_query_grid(const void *programs, size_t program_stride_bytes, int batch,
                                  const float *axis, int G, int slice_begin, int slice_end,
                                  int apply_sigmoid, float *out, const int *tile_mask, void *workspace,
                                  void *stream) {
-    if (batch < 0 || G <= 0 || slice_begin < 0 || slice_end > G || slice_begin > slice_end) {
-        zs::set_err("zs_sdf_query_grid: bad range (batch=%d G=%d slices=[%d,%d))", batch, G,
-                    slice_begin, slice_end);
+    static const char who[] = "zs_sdf_query_grid";
+    Query q;
+    if (!grid_slices(who, batch, G, slice_begin, slice_end) ||
+        !grid_range_query(who, "slab", programs, program_stride_bytes, batch, axis, G, (long long)slice_begin * G * G,
+                          (long long)slice_end * G * G, apply_sigmoid, out, workspace, q))
         return 0;
-    }
-    const long long mm = (long long)(slice_end - slice_begin) * G * G;
-    if (batch == 0 || mm == 0) return 1;
-    if (!programs || !axis || !out || !workspace) {
-        zs::set_err("zs_sdf_query_grid: null pointer");
-        return 0;
-    }
-    if (mm > 0x7fffffffLL - PTS_PER_BLOCK) {
-        zs::set_err("zs_sdf_query_grid: %lld points per launch exceed 2^31; split the slab", mm);
-        return 0;
-    }
-    if (program_stride_bytes % 16 != 0 || program_stride_bytes < zs_sdf_program_bytes()) {
-        zs::set_err("zs_sdf_query_grid: bad program stride %zu", program_stride_bytes);
-        return 0;
-    }
-    const int m = (int)mm;
-    hipLaunchKernelGGL((sdf_decode_kernel<true, false>), dim3(decode_grid_size(batch, m)),
-                       dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const float *>(programs), program_stride_bytes / sizeof(float), batch,
-                       nullptr, axis, G, (long long)slice_begin * G * G, m, out, apply_sigmoid,
-                       static_cast<f32x4 *>(workspace), nullptr, tile_mask);
-    return zs::check_launch("zs_sdf_query_grid") ? 1 : 0;
+    if (q.m == 0) return 1;
+    launch_decode(programs, program_stride_bytes, batch, q, out, nullptr, tile_mask, workspace,
+                  static_cast<hipStream_t>(stream));
+    return zs::check_launch(who) ? 1 : 0;
 }

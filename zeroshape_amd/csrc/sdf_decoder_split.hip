@@ -44,6 +44,7 @@
 #include "sdf_layout.h"
 #include "sdf_math.h"
 #include "zs_split16.h"
+#include "sdf_query.h"
 #include "../../include/zeroshape_hip.h"
 
 #include <math.h>
@@ -53,6 +54,7 @@
 namespace {
 
 using namespace zs::lay;
+using namespace zs::qry;    // tile geometry, workspace layout, argument checks
 using zs::dm::gelu_erf;
 using zs::dm::softplus100;
 
@@ -62,10 +64,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float S_GUARD = 64.0f;  // program.py: S_GUARD
-constexpr int WAVES = 4;
-constexpr int PTS_PER_WAVE = 32;
-constexpr int PTS_PER_BLOCK = WAVES * PTS_PER_WAVE;
-constexpr int MAX_WGS = 256;                        // one persistent workgroup per CU
 constexpr int KB_U4 = 128;                          // one K-block: [hi: 64 lanes x 16 B][lo: 64 lanes x 16 B]
 constexpr int CK = 8;                               // K-blocks per staged chunk: two per wave
 constexpr int KPW = CK / WAVES;                     // K-blocks a wave stages per chunk
@@ -77,7 +75,8 @@ constexpr int STAGE_FLOATS = NBUF * CHUNK_BYTES / 4;
 constexpr int SLAB_TILES = NT - 1;                  // tiles of an activation array kept in LDS (the last: registers)
 constexpr int SLAB_U4 = SLAB_TILES * 4 * 64;        // ... as packed (hi, lo) K-blocks: 28 KiB per wave
 constexpr int ZTILES_F4 = NT * 4 * 64;              // one skip layer's fp32 feat partial products (workspace)
-constexpr int ZSLAB_F4 = 3 * ZTILES_F4;
+static_assert(ZSLAB_F4 == 3 * ZTILES_F4, "the workspace slab holds three skip layers' feat partial products");
+static_assert(B0_TABLE_FLOATS == PRM_WINDOW, "an image's block-0 tables are loaded as one params window");
 constexpr int LDS_FLOATS = PRM_WINDOW + STAGE_FLOATS + WAVES * SLAB_U4 * 4;
 static_assert(LDS_FLOATS * 4 == 160 * 1024, "the kernel owns the whole LDS of a CU");
 static_assert(KB_TOTAL % CK == 0 && CK % WAVES == 0 && KPW * 2048 <= 4096, "chunking");
@@ -1158,7 +1157,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
     // The counter is the LIBRARY's: launch_counter_reset() zeroes it on the stream in front of every launch (a
     // caller's un-zeroed workspace, or a faulted launch that left it non-zero, must not decide which tiles get evaluated),
     // and a fetched index is used only when it is a real one (unsigned compare).
-    int *tile_counter = reinterpret_cast<int *>(workspace + (size_t)MAX_WGS * WAVES * ZSLAB_F4) + 256;   // 1 KiB into the tail
+    int *tile_counter = zs::qry::tile_counter(workspace);
     int *tile_slot = tile_counter + 16 + blockIdx.x;
     const int dyn_tiles = total > (int)gridDim.x ? total - (int)gridDim.x : 0;
     for (int tile = blockIdx.x;;) {
@@ -1188,7 +1187,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
         }
 #ifdef ZS_EXP_TIMING
         unsigned long long *dbg = (blockIdx.x == 0 && threadIdx.x == 0 && tile == 0)
-            ? reinterpret_cast<unsigned long long *>(workspace + (size_t)MAX_WGS * WAVES * ZSLAB_F4) : nullptr;
+            ? timing_stamps(workspace) : nullptr;
 #else
         unsigned long long *dbg = nullptr;
 #endif
@@ -1414,28 +1413,35 @@ const float *launch_block0_tables(const void *split_programs, size_t program_str
                                   hipStream_t st) {
     const char *e = getenv("ZS_SPLIT_BLOCK0_GEMM");
     if (e && atoi(e) != 0) return nullptr;
-    if ((size_t)batch * PRM_WINDOW * sizeof(float) > (size_t)MAX_WGS * WAVES * ZSLAB_F4 * sizeof(f32x4)) return nullptr;
+    if (!block0_tables_fit(batch)) return nullptr;
     float *tables = static_cast<float *>(workspace);
     hipLaunchKernelGGL(block0_window_kernel, dim3(HEADS * 3, batch), dim3(B0_THREADS), 0, st,
                        static_cast<const char *>(split_programs), program_stride_bytes, tables);
     return tables;
 }
 
-int decode_grid_size(int batch, int m) {
-    const long long tiles = (long long)batch * ((m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK);
-    return (int)(tiles < MAX_WGS ? tiles : MAX_WGS);
+// in front of every split launch: the dynamic tile order's counter (in the workspace tail) starts at zero whatever
+// the caller's workspace held (a memset node when the stream is being captured); -> static_order of the launch
+int launch_counter_reset(void *workspace, hipStream_t st) {
+    const char *e = getenv("ZS_SPLIT_STATIC_TILES");                  // read per launch: tools/ab_tile_order.py alternates the arms in one process
+    if (e && atoi(e) != 0) return 1;
+    (void)hipMemsetAsync(tile_counter(workspace), 0, sizeof(int), st);
+    return 0;
 }
 
-bool check_programs(const char *what, const void *programs, size_t stride) {
-    if (!programs) {
-        zs::set_err("%s: null pointer", what);
-        return false;
-    }
-    if (stride % 16 != 0 || stride < zs_sdf_program_bytes()) {
-        zs::set_err("%s: bad program stride %zu", what, stride);
-        return false;
-    }
-    return true;
+// The one launch of sdf_decode_split_kernel over the query q, behind the counter reset and the block-0 tables of its images.
+int launch_decode_split(const char *who, const void *split_programs, size_t program_stride_bytes, int batch, const Query &q,
+                        float *out, int *tile_flags, void *workspace, void *stream) {
+    if (q.m == 0) return 1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int static_order = launch_counter_reset(workspace, st);
+    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, st);
+    hipLaunchKernelGGL(q.points ? sdf_decode_split_kernel<false> : sdf_decode_split_kernel<true>,
+                       dim3(decode_grid_size(batch, q.m)), dim3(WAVES * 64), 0, st,
+                       static_cast<const char *>(split_programs), program_stride_bytes, batch, q.points, q.axis, q.G,
+                       q.first_point, q.m, out, q.apply_sigmoid, static_cast<f32x4 *>(workspace), tile_flags, static_order,
+                       b0_tables);
+    return zs::check_launch(who) ? 1 : 0;
 }
 
 }  // namespace
@@ -1484,100 +1490,36 @@ extern "C" int zs_sdf_block0_tables(const void *split_programs, size_t program_s
     return zs::check_launch("zs_sdf_block0_tables") ? 1 : 0;
 }
 
-// in front of every split launch: the dynamic tile order's counter (1 KiB into the workspace tail) starts at zero whatever
-// the caller's workspace held (a memset node when the stream is being captured); -> static_order of the launch
-static int launch_counter_reset(void *workspace, hipStream_t st) {
-    const char *e = getenv("ZS_SPLIT_STATIC_TILES");                  // read per launch: tools/ab_tile_order.py alternates the arms in one process
-    if (e && atoi(e) != 0) return 1;
-    int *tile_counter = reinterpret_cast<int *>(static_cast<f32x4 *>(workspace) + (size_t)MAX_WGS * WAVES * ZSLAB_F4) + 256;
-    (void)hipMemsetAsync(tile_counter, 0, sizeof(int), st);
-    return 0;
-}
-
 extern "C" int zs_sdf_query_points_split(const void *split_programs, size_t program_stride_bytes,
                                          int batch, const float *points, int m, float *logits,
                                          int *tile_flags, void *workspace, void *stream) {
-    if (batch < 0 || m < 0) {
-        zs::set_err("zs_sdf_query_points_split: negative size (batch=%d m=%d)", batch, m);
-        return 0;
-    }
-    if (batch == 0 || m == 0) return 1;
-    if (!points || !logits || !workspace) {
-        zs::set_err("zs_sdf_query_points_split: null pointer");
-        return 0;
-    }
-    if (!check_programs("zs_sdf_query_points_split", split_programs, program_stride_bytes)) return 0;
-    if ((long long)batch * ((m + PTS_PER_BLOCK - 1) / PTS_PER_BLOCK) > 0x7fffffffLL) {
-        zs::set_err("zs_sdf_query_points_split: too many tiles");
-        return 0;
-    }
-    const int static_order = launch_counter_reset(workspace, static_cast<hipStream_t>(stream));
-    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL((sdf_decode_split_kernel<false>), dim3(decode_grid_size(batch, m)),
-                       dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const char *>(split_programs), program_stride_bytes, batch, points,
-                       nullptr, 0, 0LL, m, logits, 0, static_cast<f32x4 *>(workspace), tile_flags, static_order, b0_tables);
-    return zs::check_launch("zs_sdf_query_points_split") ? 1 : 0;
+    static const char who[] = "zs_sdf_query_points_split";
+    Query q;
+    if (!points_query(who, split_programs, program_stride_bytes, batch, points, m, logits, workspace, q)) return 0;
+    return launch_decode_split(who, split_programs, program_stride_bytes, batch, q, logits, tile_flags, workspace, stream);
 }
 
 extern "C" int zs_sdf_query_grid_range_split(const void *split_programs, size_t program_stride_bytes,
                                              int batch, const float *axis, int G, long long point_begin,
                                              long long point_end, int apply_sigmoid, float *out,
                                              int *tile_flags, void *workspace, void *stream) {
-    const long long P = (long long)G * G * G;
-    if (batch < 0 || G <= 0 || point_begin < 0 || point_end > P || point_begin > point_end) {
-        zs::set_err("zs_sdf_query_grid_range_split: bad range (batch=%d G=%d points=[%lld,%lld))", batch, G,
-                    point_begin, point_end);
+    static const char who[] = "zs_sdf_query_grid_range_split";
+    Query q;
+    if (!grid_range_query(who, "range", split_programs, program_stride_bytes, batch, axis, G, point_begin, point_end,
+                          apply_sigmoid, out, workspace, q))
         return 0;
-    }
-    const long long mm = point_end - point_begin;
-    if (batch == 0 || mm == 0) return 1;
-    if (!axis || !out || !workspace) {
-        zs::set_err("zs_sdf_query_grid_range_split: null pointer");
-        return 0;
-    }
-    if (mm > 0x7fffffffLL - PTS_PER_BLOCK) {
-        zs::set_err("zs_sdf_query_grid_range_split: %lld points per launch exceed 2^31; split the range", mm);
-        return 0;
-    }
-    if (!check_programs("zs_sdf_query_grid_range_split", split_programs, program_stride_bytes)) return 0;
-    const int m = (int)mm;
-    const int static_order = launch_counter_reset(workspace, static_cast<hipStream_t>(stream));
-    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL((sdf_decode_split_kernel<true>), dim3(decode_grid_size(batch, m)),
-                       dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const char *>(split_programs), program_stride_bytes, batch, nullptr,
-                       axis, G, point_begin, m, out, apply_sigmoid, static_cast<f32x4 *>(workspace), tile_flags, static_order, b0_tables);
-    return zs::check_launch("zs_sdf_query_grid_range_split") ? 1 : 0;
+    return launch_decode_split(who, split_programs, program_stride_bytes, batch, q, out, tile_flags, workspace, stream);
 }
 
 extern "C" int zs_sdf_query_grid_split(const void *split_programs, size_t program_stride_bytes,
                                        int batch, const float *axis, int G, int slice_begin,
                                        int slice_end, int apply_sigmoid, float *out, int *tile_flags,
                                        void *workspace, void *stream) {
-    if (batch < 0 || G <= 0 || slice_begin < 0 || slice_end > G || slice_begin > slice_end) {
-        zs::set_err("zs_sdf_query_grid_split: bad range (batch=%d G=%d slices=[%d,%d))", batch, G,
-                    slice_begin, slice_end);
+    static const char who[] = "zs_sdf_query_grid_split";
+    Query q;
+    if (!grid_slices(who, batch, G, slice_begin, slice_end) ||
+        !grid_range_query(who, "slab", split_programs, program_stride_bytes, batch, axis, G,
+                          (long long)slice_begin * G * G, (long long)slice_end * G * G, apply_sigmoid, out, workspace, q))
         return 0;
-    }
-    const long long mm = (long long)(slice_end - slice_begin) * G * G;
-    if (batch == 0 || mm == 0) return 1;
-    if (!axis || !out || !workspace) {
-        zs::set_err("zs_sdf_query_grid_split: null pointer");
-        return 0;
-    }
-    if (mm > 0x7fffffffLL - PTS_PER_BLOCK) {
-        zs::set_err("zs_sdf_query_grid_split: %lld points per launch exceed 2^31; split the slab", mm);
-        return 0;
-    }
-    if (!check_programs("zs_sdf_query_grid_split", split_programs, program_stride_bytes)) return 0;
-    const int m = (int)mm;
-    const int static_order = launch_counter_reset(workspace, static_cast<hipStream_t>(stream));
-    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL((sdf_decode_split_kernel<true>), dim3(decode_grid_size(batch, m)),
-                       dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const char *>(split_programs), program_stride_bytes, batch, nullptr,
-                       axis, G, (long long)slice_begin * G * G, m, out, apply_sigmoid,
-                       static_cast<f32x4 *>(workspace), tile_flags, static_order, b0_tables);
-    return zs::check_launch("zs_sdf_query_grid_split") ? 1 : 0;
+    return launch_decode_split(who, split_programs, program_stride_bytes, batch, q, out, tile_flags, workspace, stream);
 }

@@ -89,8 +89,6 @@ class DecoderState(object):
 
     def __init__(self, programs, batch, precision="f32", exact=None):
         self.programs, self.batch, self.precision, self.exact = programs, batch, precision, exact
-        # split states from a calibrating prepare(): int32 [batch] on the device, 1 = this image's probe points differed by
-        # more than CALIBRATION_TOL between the two arithmetics -> every tile of the image is re-evaluated in fp32
         self.image_flags = None       # int32 [B] from prepare()'s per-image check (1: evaluate this image in fp32), raw-logit rule
         self.image_flags_occ = None   # the same under the occupancy rule (calls that return sigmoid(logit))
         self.check_event = None       # recorded behind that check on its side stream; consumers wait for it on THEIR stream
@@ -313,14 +311,9 @@ class Implicit(nn.Module):
             raise RuntimeError("Implicit.prepare: the f16x3 calibration of new weights needs one host read; run one "
                                "eager prepare() before capturing, or request precision='f32'")
         pts = self._probe_points(split.device)
-        guard, flags = self.envelope_guard, self.last_tile_flags
-        self.envelope_guard = False                 # the raw arithmetic is what is being measured
-        try:
-            raw = DecoderState(split[:1], 1, "f16x3", exact=exact[:1])
-            got = self.query_points(raw, pts)
-        finally:
-            self.envelope_guard, self.last_tile_flags = guard, flags
-        want = self.query_points(DecoderState(exact[:1], 1), pts)
+        raw = dict(envelope_guard=False, record_flags=False)       # the raw arithmetic is what is being measured
+        got = self._points_logits(DecoderState(split[:1], 1, "f16x3", exact=exact[:1]), pts, **raw)
+        want = self._points_logits(DecoderState(exact[:1], 1), pts, **raw)
         stats = self._verdict_stats(got, want)[0][0].cpu()
         if not bool(torch.isfinite(stats[2])):
             # the exact kernel itself is not finite on this image (NaN latent): no verdict on the weights - this
@@ -393,28 +386,6 @@ class Implicit(nn.Module):
                 return state
         return DecoderState(programs, B)
 
-    def _sharded_image_check(self, split, exact, shard, streams=None):
-        """_image_check() of this rank's images (rank, rank + world, ...) + the exchange that completes the flags: the same
-        four tensors, over the whole batch (the maxima of the other ranks' images are not exchanged: -1)."""
-        rank, world, exchange = shard
-        B = split.shape[0]
-        k = (B + world - 1) // world
-        a = streams[0] if streams is not None else None
-        ctx = (lambda st: torch.cuda.stream(st)) if streams is not None else (lambda st: contextlib.nullcontext())
-        mine = len(range(rank, B, world))
-        if mine:
-            # (a strided view of the programs: the C ABI takes the program stride)
-            f, f_occ, mx, mx_occ = self._image_check(split[rank::world], exact[rank::world], streams=streams)
-        with ctx(a):
-            own = torch.zeros(k, 2, dtype=torch.int32, device=split.device)
-            maxima = torch.full((B,), -1.0, dtype=torch.float32, device=split.device)
-            maxima_occ = maxima.clone()
-            if mine:
-                own[:mine, 0], own[:mine, 1] = f, f_occ
-                maxima[rank::world], maxima_occ[rank::world] = mx, mx_occ
-            flags = exchange(own, B)                    # [B, 2] on every rank
-            return flags[:, 0].contiguous(), flags[:, 1].contiguous(), maxima, maxima_occ
-
     def _launch_image_check(self, state, split, exact, shard=None):
         """The per-image check on a SIDE stream, so that it runs beside the first grid launch instead of in front of it: the
         fp32 probe launch alone is the latency of one fp32 wave tile (1.2 ms however few points).  The state carries the
@@ -423,88 +394,90 @@ class Implicit(nn.Module):
         capture the check runs inline (a fork that the capture might not join is not worth the risk)."""
         dev = split.device
         main = torch.cuda.current_stream(dev)
-        if torch.cuda.is_current_stream_capturing() or os.environ.get("ZS_DECODER_CHECK_INLINE", "0") != "0":
-            state.image_flags, state.image_flags_occ, maxima, maxima_occ = \
-                self._image_check(split, exact) if shard is None else self._sharded_image_check(split, exact, shard)
-            self._last_check_event = None
-        else:
-            pair = self._check_streams.get(str(dev))
-            if pair is None:
+        streams = None
+        if not torch.cuda.is_current_stream_capturing():
+            streams = self._check_streams.get(str(dev))
+            if streams is None:
                 # HIGH priority: when the prologue ends, the probe launches and the caller's grid launch become ready together;
                 # a resident persistent grid launch would keep the probes waiting until its workgroups retire
-                pair = self._check_streams[str(dev)] = (torch.cuda.Stream(device=dev, priority=-1),
-                                                        torch.cuda.Stream(device=dev, priority=-1))
-            side, side2 = pair
+                streams = self._check_streams[str(dev)] = (torch.cuda.Stream(device=dev, priority=-1),
+                                                           torch.cuda.Stream(device=dev, priority=-1))
+            side, side2 = streams
             side.wait_stream(main)                          # the programs are ready
             side2.wait_stream(main)
             # ... and the caller's stream waits for a marker at the HEAD of each side stream: when the prologue ends all three
             # queues become ready at once, and whichever launch is dispatched first takes the CUs.  Behind the markers the probe
             # launches are the next packets of their queues, while the caller's queue first has to resolve its barrier: the
             # probes start first (vox 128 without the markers: the grid launch won the race and the fp32 probe ran AFTER its 28 ms)
-            for st_ in (side, side2):
+            for st_ in streams:
                 head = torch.cuda.Event()
                 head.record(st_)
                 main.wait_event(head)
-            state.image_flags, state.image_flags_occ, maxima, maxima_occ = \
-                self._image_check(split, exact, streams=(side, side2)) if shard is None else \
-                self._sharded_image_check(split, exact, shard, streams=(side, side2))
+        state.image_flags, state.image_flags_occ, maxima, maxima_occ = self._image_check(split, exact, shard, streams)
+        if streams is not None:
             state.check_event = torch.cuda.Event()
             state.check_event.record(side)
             # the side streams read `split` / `exact` (10 MB per image each): they must outlive that work even if the caller drops
             # the state at once.  Not record_stream() - it parks the blocks behind events and makes the allocator grow its pool
             # with fresh 10 MB hipMallocs for several calls - but a reference held here until the check's event has completed
-            if os.environ.get("ZS_DECODER_CHECK_RECORD_STREAM", "0") != "0":      # A/B: the allocator-side alternative
-                for t in (split, exact):
-                    t.record_stream(side)
-                    t.record_stream(side2)
-            else:
-                while self._check_keepalive and self._check_keepalive[0][0].query():
-                    self._check_keepalive.pop(0)
-                self._check_keepalive.append((state.check_event, split, exact))
+            while self._check_keepalive and self._check_keepalive[0][0].query():
+                self._check_keepalive.pop(0)
+            self._check_keepalive.append((state.check_event, split, exact))
             for t in (state.image_flags, state.image_flags_occ, maxima, maxima_occ):
                 t.record_stream(main)                       # written over there, read here
-            self._last_check_event = state.check_event
+        self._last_check_event = state.check_event
         self._last_calibration = dict(self._last_calibration, per_image_max_abs_diff=maxima, per_image_max_abs_occ_diff=maxima_occ)
 
     @torch.no_grad()
-    def _image_check(self, split, exact, streams=None):
+    def _image_check(self, split, exact, shard=None, streams=None):
         """The f16x3 error also depends on the image's K / V records, and the per-weights verdict above was measured on the
         first image seen.  So every prepare() runs the probe points of EVERY image through both kernels and flags - on the
         device, no host read - the images that fail the raw-logit rule / the occupancy rule (or are not finite): the fp32
         launch behind every split launch re-evaluates them entirely (_join_image_check).  `streams` = (a, b): the fp32 probes
         on a, the split probes on b (concurrently), the comparison on a; None: everything on the current stream.
+        `shard` = (rank, world, exchange) (prepare()): only this rank's images (rank, rank + world, ...) are probed, and the
+        exchange, on a, completes the flags; the maxima of the other ranks' images are not exchanged: -1.
         -> (int32 flags [B] under the raw-logit rule, int32 flags [B] under the occupancy rule, float32 max |dlogit| [B],
         float32 max |docc| [B]), all device tensors."""
         B = split.shape[0]
         a, b = streams if streams is not None else (None, None)
-        ctx = (lambda st: torch.cuda.stream(st)) if streams is not None else (lambda st: contextlib.nullcontext())
-        with ctx(a):
-            pts = self._probe_points(split.device).expand(B, -1, -1).contiguous()
-        if b is not None:
-            b.wait_stream(a)                            # pts (before a's probe launch: b must not wait for THAT)
-        with ctx(a):
-            want = self.query_points(DecoderState(exact, B), pts)
-        guard, flags = self.envelope_guard, self.last_tile_flags
-        self.envelope_guard = False                 # the raw arithmetic is what is being measured
-        try:
-            with ctx(b):
-                got = self.query_points(DecoderState(split, B, "f16x3", exact=exact), pts)
-        finally:
-            self.envelope_guard, self.last_tile_flags = guard, flags
-        if b is not None:
-            a.wait_stream(b)
-            got.record_stream(a)
-            pts.record_stream(b)
-        with ctx(a):
-            st, flags = self._verdict_stats(got, want)       # [B, 5], [B, 2] (NaN / inf anywhere: both flags set)
-            return flags[:, 0], flags[:, 1], st[:, 0], st[:, 3]
+        if shard is not None:
+            rank, world, exchange = shard
+            split, exact = split[rank::world], exact[rank::world]      # (strided views: the C ABI takes the program stride)
+        mine = split.shape[0]
+        probe = mine > 0 or shard is None           # (a rank beyond the batch has no image to probe, only the exchange)
+        raw = dict(envelope_guard=False, record_flags=False)       # the raw arithmetic is what is being measured
+        if probe:
+            with self._on(a):
+                pts = self._probe_points(split.device).expand(mine, -1, -1).contiguous()
+            if b is not None:
+                b.wait_stream(a)                            # pts (before a's probe launch: b must not wait for THAT)
+            with self._on(a):
+                want = self._points_logits(DecoderState(exact, mine), pts, **raw)
+            with self._on(b):
+                got = self._points_logits(DecoderState(split, mine, "f16x3", exact=exact), pts, **raw)
+            if b is not None:
+                a.wait_stream(b)
+                got.record_stream(a)
+                pts.record_stream(b)
+        with self._on(a):
+            if probe:
+                st, flags = self._verdict_stats(got, want)       # [mine, 5], [mine, 2] (NaN / inf anywhere: both flags set)
+                if shard is None:
+                    return flags[:, 0], flags[:, 1], st[:, 0], st[:, 3]
+            own = torch.zeros((B + world - 1) // world, 2, dtype=torch.int32, device=split.device)
+            maxima = torch.full((B,), -1.0, dtype=torch.float32, device=split.device)
+            maxima_occ = maxima.clone()
+            if probe:
+                own[:mine, 0], own[:mine, 1] = flags[:, 0], flags[:, 1]
+                maxima[rank::world], maxima_occ[rank::world] = st[:, 0], st[:, 3]
+            flags = exchange(own, B)                    # [B, 2] on every rank
+            return flags[:, 0].contiguous(), flags[:, 1].contiguous(), maxima, maxima_occ
 
-    def _tile_flags(self, batch, m, device, state=None):
-        """Tile flags of one split launch: zero - the kernel sets the tiles that leave its envelope, _join_image_check() adds
-        the images the per-image check of prepare() flagged.  None: neither guard is on.  No host read anywhere."""
-        if not self.envelope_guard and getattr(state, "image_flags", None) is None:
-            return None
-        return torch.zeros(batch * ((m + 127) // 128), dtype=torch.int32, device=device)
+    @staticmethod
+    def _on(stream):
+        """Run on `stream`, or (None) on the current one."""
+        return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
     @staticmethod
     def _for_space(state, occupancy):
@@ -526,47 +499,67 @@ class Implicit(nn.Module):
             torch.cuda.current_stream(flags.device).wait_event(state.check_event)
         flags.view(state.batch, -1).bitwise_or_(image_flags[:, None])
 
+    def _query(self, state, m, occupancy, split, exact, device, attn_bytes=0, envelope_guard=None, record_flags=True):
+        """The launch sequence of every query: `m` points per image on `state`, returning occupancies or raw logits.
+        `split` / `exact` = (entry point, its arguments between the batch and the tile flags / tile mask) for the two
+        arithmetics; split None: the call has no split form (the attention map, whose raw tiles take `attn_bytes` more
+        workspace).  An fp32 state: the exact launch.  A split state: zeroed tile flags, the split launch - the kernel sets the
+        tiles that leave its envelope, _join_image_check() adds the images prepare()'s check flagged - then the exact launch
+        over the flagged tiles; no flags, and no exact launch, when neither guard is on.  No host read anywhere.
+        `envelope_guard`: None = self.envelope_guard; `record_flags`: keep the flags as last_tile_flags."""
+        lib = _lib.load()
+        guard = self.envelope_guard if envelope_guard is None else envelope_guard
+        state = self._for_space(state, occupancy)
+        is_split = state.precision == "f16x3"
+        if is_split and split is None:
+            raise ValueError("the attention map needs an fp32 DecoderState (prepare(..., precision='f32'))")
+        ws, st = _lib.ptr(self.workspace(device, attn_bytes)), _lib.current_stream_ptr(device)
+
+        def launch(call, programs, flags):
+            name, middle = call
+            _lib.check(getattr(lib, name)(_lib.ptr(programs), programs.stride(0) * 4, state.batch, *middle, _lib.ptr(flags),
+                                          ws, st), name)
+
+        with _lib.on(device):
+            if not is_split:
+                return launch(exact, state.programs, None)
+            flags = None
+            if guard or state.image_flags is not None:
+                flags = torch.zeros(state.batch * ((m + 127) // 128), dtype=torch.int32, device=device)
+            launch(split, state.programs, flags)
+            self._join_image_check(state, flags, occupancy)
+            if flags is not None:
+                launch(exact, state.exact, flags)       # flagged tiles (outside the split arithmetic's envelope) again, exactly
+        if record_flags:
+            self.last_tile_flags = flags
+
+    def _points_logits(self, state, pts, envelope_guard=None, record_flags=True):
+        """query_points() behind its argument checks: pts [B,M,3] fp32 contiguous -> logits [B,M].  With the guard off and
+        recording off (_calibrate, _image_check) a split state returns its raw arithmetic and last_tile_flags stays."""
+        M = pts.shape[1]
+        out = torch.empty(state.batch, M, dtype=torch.float32, device=pts.device)
+        mid = (_lib.ptr(pts), M, _lib.ptr(out))
+        self._query(state, M, False, ("zs_sdf_query_points_split", mid), ("zs_sdf_query_points", mid + (None,)), pts.device,
+                    envelope_guard=envelope_guard, record_flags=record_flags)
+        return out
+
     @torch.no_grad()
     def query_points(self, state, points_3D, need_attn=False):
         """state from prepare(); points_3D [B,M,3] -> logits [B,M] fp32 (and, with need_attn,
         the attention map [B,M,197] of implicit.py:277)."""
-        lib = _lib.load()
-        state = self._for_space(state, False)
         pts = points_3D.detach().to(torch.float32).contiguous()
         if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[0] != state.batch:
             raise ValueError("points_3D must be [%d,M,3], got %s" % (state.batch, tuple(pts.shape)))
         if pts.device != state.programs.device:
             raise ValueError("points_3D and latent_depth live on different devices")
+        if not need_attn:
+            return self._points_logits(state, pts)
         M = pts.shape[1]
         out = torch.empty(state.batch, M, dtype=torch.float32, device=pts.device)
-        attn, extra = None, 0
-        if state.precision == "f16x3":
-            if need_attn:
-                raise ValueError("the attention map needs an fp32 DecoderState (prepare(..., precision='f32'))")
-            flags = self._tile_flags(state.batch, M, pts.device, state)
-            ws, st = _lib.ptr(self.workspace(pts.device)), _lib.current_stream_ptr(pts.device)
-            with _lib.on(pts.device):
-                rc = lib.zs_sdf_query_points_split(_lib.ptr(state.programs), state.stride_bytes, state.batch,
-                                                   _lib.ptr(pts), M, _lib.ptr(out), _lib.ptr(flags), ws, st)
-                _lib.check(rc, "zs_sdf_query_points_split")
-                # flagged tiles (outside the split arithmetic's envelope) again, exactly
-                self._join_image_check(state, flags)
-                if flags is not None:
-                    rc = lib.zs_sdf_query_points(_lib.ptr(state.exact), state.exact.stride(0) * 4, state.batch,
-                                                 _lib.ptr(pts), M, _lib.ptr(out), None, _lib.ptr(flags), ws, st)
-            _lib.check(rc, "zs_sdf_query_points")
-            self.last_tile_flags = flags
-            return out
-        if need_attn:
-            attn = torch.empty(state.batch, M, P.L, dtype=torch.float32, device=pts.device)
-            extra = lib.zs_sdf_attn_scratch_bytes(state.batch, M)
-        with _lib.on(pts.device):
-            rc = lib.zs_sdf_query_points(_lib.ptr(state.programs), state.stride_bytes, state.batch,
-                                         _lib.ptr(pts), M, _lib.ptr(out), _lib.ptr(attn), None,
-                                         _lib.ptr(self.workspace(pts.device, extra)),
-                                         _lib.current_stream_ptr(pts.device))
-        _lib.check(rc, "zs_sdf_query_points")
-        return (out, attn) if need_attn else out
+        attn = torch.empty(state.batch, M, P.L, dtype=torch.float32, device=pts.device)
+        self._query(state, M, False, None, ("zs_sdf_query_points", (_lib.ptr(pts), M, _lib.ptr(out), _lib.ptr(attn))),
+                    pts.device, attn_bytes=_lib.load().zs_sdf_attn_scratch_bytes(state.batch, M))
+        return out, attn
 
     @torch.no_grad()
     def query_grid(self, latent_depth, axis, apply_sigmoid=True, slice_begin=0, slice_end=None,
@@ -574,10 +567,8 @@ class Implicit(nn.Module):
         """Dense-grid query (get_dense_3D_grid + compute_level_grid, utils/eval_3D.py:11-46)
         without a points tensor: ``axis`` = torch.linspace(range_min, range_max, G) on the GPU.
         Returns [B, slice_end - slice_begin, G, G] (x slowest, z fastest)."""
-        lib = _lib.load()
         if state is None:
             state = self.prepare(latent_depth)
-        state = self._for_space(state, bool(apply_sigmoid))
         axis = axis.detach().to(torch.float32).contiguous()
         if axis.device != state.programs.device:
             raise ValueError("axis and latent_depth live on different devices")
@@ -585,64 +576,24 @@ class Implicit(nn.Module):
         slice_end = G if slice_end is None else slice_end
         out = torch.empty(state.batch, slice_end - slice_begin, G, G, dtype=torch.float32,
                           device=axis.device)
-        if state.precision == "f16x3":
-            flags = self._tile_flags(state.batch, (slice_end - slice_begin) * G * G, axis.device, state)
-            ws, st = _lib.ptr(self.workspace(axis.device)), _lib.current_stream_ptr(axis.device)
-            with _lib.on(axis.device):
-                rc = lib.zs_sdf_query_grid_split(_lib.ptr(state.programs), state.stride_bytes, state.batch,
-                                                 _lib.ptr(axis), G, slice_begin, slice_end,
-                                                 1 if apply_sigmoid else 0, _lib.ptr(out), _lib.ptr(flags), ws, st)
-                _lib.check(rc, "zs_sdf_query_grid_split")
-                self._join_image_check(state, flags, occupancy=bool(apply_sigmoid))
-                if flags is not None:
-                    rc = lib.zs_sdf_query_grid(_lib.ptr(state.exact), state.exact.stride(0) * 4, state.batch,
-                                               _lib.ptr(axis), G, slice_begin, slice_end,
-                                               1 if apply_sigmoid else 0, _lib.ptr(out), _lib.ptr(flags), ws, st)
-            _lib.check(rc, "zs_sdf_query_grid")
-            self.last_tile_flags = flags
-            return out
-        with _lib.on(axis.device):
-            rc = lib.zs_sdf_query_grid(_lib.ptr(state.programs), state.stride_bytes, state.batch,
-                                       _lib.ptr(axis), G, slice_begin, slice_end,
-                                       1 if apply_sigmoid else 0, _lib.ptr(out), None,
-                                       _lib.ptr(self.workspace(axis.device)),
-                                       _lib.current_stream_ptr(axis.device))
-        _lib.check(rc, "zs_sdf_query_grid")
+        mid = (_lib.ptr(axis), G, slice_begin, slice_end, 1 if apply_sigmoid else 0, _lib.ptr(out))
+        self._query(state, (slice_end - slice_begin) * G * G, bool(apply_sigmoid), ("zs_sdf_query_grid_split", mid),
+                    ("zs_sdf_query_grid", mid), axis.device)
         return out
 
     @torch.no_grad()
     def query_grid_range(self, latent_depth, axis, point_begin, point_end, apply_sigmoid=True, state=None):
         """Points [point_begin, point_end) of the dense grid in memory order (x slowest, z fastest):
         [B, point_end - point_begin].  The unit of the multi-GPU sharding (parallel.py)."""
-        lib = _lib.load()
         if state is None:
             state = self.prepare(latent_depth)
-        state = self._for_space(state, bool(apply_sigmoid))
         axis = axis.detach().to(torch.float32).contiguous()
         if axis.device != state.programs.device:
             raise ValueError("axis and latent_depth live on different devices")
-        G = axis.numel()
         out = torch.empty(state.batch, point_end - point_begin, dtype=torch.float32, device=axis.device)
-        ws, st = _lib.ptr(self.workspace(axis.device)), _lib.current_stream_ptr(axis.device)
-        sig = 1 if apply_sigmoid else 0
-        with _lib.on(axis.device):
-            if state.precision == "f16x3":
-                flags = self._tile_flags(state.batch, point_end - point_begin, axis.device, state)
-                rc = lib.zs_sdf_query_grid_range_split(_lib.ptr(state.programs), state.stride_bytes, state.batch,
-                                                       _lib.ptr(axis), G, point_begin, point_end, sig, _lib.ptr(out),
-                                                       _lib.ptr(flags), ws, st)
-                _lib.check(rc, "zs_sdf_query_grid_range_split")
-                self._join_image_check(state, flags, occupancy=bool(apply_sigmoid))
-                if flags is not None:
-                    rc = lib.zs_sdf_query_grid_range(_lib.ptr(state.exact), state.exact.stride(0) * 4, state.batch,
-                                                     _lib.ptr(axis), G, point_begin, point_end, sig, _lib.ptr(out),
-                                                     _lib.ptr(flags), ws, st)
-                self.last_tile_flags = flags
-            else:
-                rc = lib.zs_sdf_query_grid_range(_lib.ptr(state.programs), state.stride_bytes, state.batch,
-                                                 _lib.ptr(axis), G, point_begin, point_end, sig, _lib.ptr(out),
-                                                 None, ws, st)
-        _lib.check(rc, "zs_sdf_query_grid_range")
+        mid = (_lib.ptr(axis), axis.numel(), point_begin, point_end, 1 if apply_sigmoid else 0, _lib.ptr(out))
+        self._query(state, point_end - point_begin, bool(apply_sigmoid), ("zs_sdf_query_grid_range_split", mid),
+                    ("zs_sdf_query_grid_range", mid), axis.device)
         return out
 
     @staticmethod
