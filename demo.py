@@ -7,7 +7,12 @@
 
 <datadir>/images/*.png|jpg with <datadir>/masks/<same name>.png -> <datadir>/preds/: the cropped
 input and mask, and for the shape task the reconstructed mesh (marching cubes at 0.5 of the
-(vox_res+1)^3 occupancy grid, as OBJ), for the depth task the depth map.  Same preprocessing as the
+(vox_res+1)^3 occupancy grid, as OBJ), for the depth task the depth map and two textured meshes of the
+surface the camera sees, <name>_seen_surface_fixed.obj/.mtl from the fixed intrinsics and
+<name>_seen_surface_pred.obj/.mtl from the predicted ones (the pair that shows what the intrinsics head
+does; written when the graph has one), both textured with <name>_image_input.png.  The predicted depth is
+unprojected on the GPU and the meshes - validity, edge tests, vertex and face order of the reference's
+create_seen_surface - come from one kernel call each (csrc/seen_mesh.hip).  Same preprocessing as the
 reference (demo.py:27-70: mask binarised at 127, square crop 1.2x the mask's bounding box, resize to
 image_size, white background, intrinsics f = 1.3875 * W).  Everything after image loading runs on
 the GPU through the HIP library.
@@ -33,7 +38,7 @@ compat.install()
 import utils.options as options                                              # noqa: E402
 from utils.eval_3D import compute_level_grid, convert_to_explicit, get_dense_3D_grid   # noqa: E402
 from utils.util import EasyDict as edict                                     # noqa: E402
-from zeroshape_amd.utils import util_vis                                     # noqa: E402
+from zeroshape_amd.utils import camera, util_vis                             # noqa: E402
 
 
 def bbox_from_mask(mask, thr):
@@ -126,6 +131,15 @@ def main():
                 if viz:
                     util_vis.dump_attentions(opt, [name], "attn", var.attn_vis, folder='preds')
                     util_vis.dump_meshes_viz(opt, [name], "mesh_viz", var.mesh_pred, save_frames=False, folder='preds')
+            elif opt.task == 'depth':
+                # demo.py:205-214 of the reference; the mask goes to the kernel in place of its `* mask + (1 - mask) * -1`
+                B, _, H, W = var.depth_pred.shape
+                for tag, intr in (("fixed", var.intr), ("pred", var.intr_pred if 'intr_pred' in var else None)):
+                    if intr is None:
+                        continue
+                    seen = camera.unproj_depth(opt, var.depth_pred, intr).view(B, H, W, 3)
+                    util_vis.dump_seen_surface(opt, [name], "seen_surface_" + tag, "image_input", seen, folder='preds',
+                                               masks=var.mask_input_map)
         print("{}: done".format(name))
 
 

@@ -26,6 +26,8 @@
  *                           marching_cubes + trimesh.sample on the host)
  *   zs_mesh_stats, zs_render_frames <- dump_meshes_viz, scale_to_unit_cube, visualize_mesh,
  *                           utils/util_vis.py:112-127, 310-405 (trimesh + pyrender on OpenGL)
+ *   zs_seen_mesh_workspace_bytes, zs_seen_mesh <- create_seen_surface, utils/util_vis.py:137-170
+ *                           (a Python loop over every pixel with a host sync per test)
  *   zs_seen_surface, zs_unproj_depth, zs_valid_norm_fac, zs_masked_resample,
  *   zs_intr_param2mtx    <- the seen-surface geometry of Graph.forward,
  *                           model/compute_graph/graph_shape.py:89-113,131-144, with
@@ -50,7 +52,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 42
+#define ZS_ABI_VERSION 43
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -426,6 +428,34 @@ size_t zs_render_zbuffer_bytes(int frames, int H, int W);
 int zs_render_frames(const float *tris, int n_tris, const float *xform, const float *cams,
                      int frames, int H, int W, float yfov, float znear, const float *base_rgb,
                      uint8_t *rgb, float *depth, int *tri, void *zbuffer, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Seen-surface mesh (replaces create_seen_surface, utils/util_vis.py:137-170): the textured
+ * mesh of the surface the camera sees, from a camera-frame point map, in the reference's order.
+ *   xyz  [B][H][W][3] : camera-frame points
+ *   mask [B][H][W]    : or NULL; a pixel with mask <= 0.5 is invalid
+ * A pixel is a vertex iff z > 0 (NaN is not) and its mask allows it; vertices are numbered from
+ * 1 in raster order (y outer, x inner) per image.  Cells (y, x), y < H-1, x < W-1, in raster
+ * order, the upper triangle first, then the lower:
+ *   upper (y,x), (y,x+1), (y+1,x)     : three vertices, |P(y,x) - P(y,x+1)| < thr and
+ *                                       |P(y,x) - P(y+1,x)| < thr
+ *   lower (y,x+1), (y+1,x+1), (y+1,x) : three vertices, |P(y,x+1) - P(y+1,x+1)| < thr and
+ *                                       |P(y,x+1) - P(y+1,x)| < thr
+ * with |d| = sqrtf(dx*dx + dy*dy + dz*dz) in fp32 as written; a NaN length rejects.
+ *   vert_id    [B][H][W]              : 1-based OBJ index of the pixel's vertex, 0 = none
+ *   vert_pixel [B][H*W]               : compacted: raster index y*W + x of vertex k
+ *   verts      [B][H*W][3]            : compacted: xyz of vertex k, bits unchanged
+ *   faces      [B][2*(H-1)*(W-1)][3]  : compacted: 1-based vertex indices in the order above
+ *                                       (may be NULL when H == 1 or W == 1: no cells)
+ *   counts     [B][2]                 : (n_verts, n_faces)
+ * Rows of the compacted buffers beyond `counts` are left unwritten.  Compaction is by prefix
+ * scan, no atomics: the order is the reference's and two runs give the same bits.  workspace:
+ * zs_seen_mesh_workspace_bytes(batch, H, W) bytes, 8-byte aligned.  batch, H or W == 0 does
+ * nothing; batch * H * W <= 2^30 (the size function returns 0 beyond that). */
+size_t zs_seen_mesh_workspace_bytes(int batch, int H, int W);
+int zs_seen_mesh(const float *xyz, const float *mask, int batch, int H, int W, float connect_thres,
+                 int *vert_id, int *vert_pixel, float *verts, int *faces, int *counts,
+                 void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Seen-surface geometry front-end (model/compute_graph/graph_shape.py:131-144).

@@ -110,6 +110,8 @@ SIGNATURES = {
     "zs_render_zbuffer_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
     "zs_render_frames": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_float), _c_void_p, _c_int, _c_int, _c_int, _c_float,
                                   _c_float, ctypes.POINTER(_c_float), _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_seen_mesh_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+    "zs_seen_mesh": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float] + [_c_void_p] * 7),
     "zs_intr_param2mtx": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "zs_unproj_depth": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "zs_valid_norm_fac": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
@@ -219,7 +221,7 @@ SIGNATURES = {
     "zs_readout_concat_bwd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
 }
 
-ABI_VERSION = 42
+ABI_VERSION = 43
 _lib = None
 
 

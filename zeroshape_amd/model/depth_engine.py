@@ -3,9 +3,11 @@ graph_depth.Graph.  Training (setup_optimizer :77-101: two AdamW groups; train /
 train_iteration :124-236) shares the loop of the shape engine - HIP autograd forward / backward, MiDaS
 depth loss + intrinsics loss, bucketed RCCL gradient averaging, fused AdamW.  Evaluation (:270-382):
 DepthMetric (scale/shift aligned d>thr / rmse / l1 / abs_rel, one fused launch per batch), per-sample
-metrics gathered over the ranks, best_val.txt in the reference's format."""
+metrics gathered over the ranks, best_val.txt in the reference's format; with `--eval.dump_results` the per-sample
+images, depth maps and seen-surface clouds of dump_results (:410-438)."""
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -89,6 +91,10 @@ class Runner(shape_engine.Runner):
             mask = var.mask_eroded if 'mask_eroded' in var else var.mask_input_map
             sample_metrics, var.depth_pred_aligned = self.depth_metric.compute_metrics(var.depth_pred, var.depth_input_map,
                                                                                        mask)
+            if not training and getattr(opt.eval, "dump_results", False) \
+                    and (not dist.is_available() or not dist.is_initialized() or dist.get_rank() == 0):    # :352-354, opt-in here
+                var.rmse = sample_metrics['rmse']
+                self.dump_results(opt, var, ep, write_new=(it == 0))
             rows.append(torch.stack([sample_metrics[k].float() for k in keys], 1))
             ids.append(torch.as_tensor(var.idx).view(-1).to(opt.device))
         ids, (rows,) = parallel.gather_sample_rows(torch.cat(ids).long(), [torch.cat(rows)])
@@ -105,3 +111,36 @@ class Runner(shape_engine.Runner):
             self.last_metrics = metric_avg
             return dict(metric_avg, cd=metric_avg['l1_err']) if training else metric_avg['l1_err']
         return dict(cd=float('inf')) if training else float('inf')
+
+    @torch.no_grad()
+    def dump_results(self, opt, var, ep, write_new=False, train=False):
+        """:410-438: under <output_path>/dump/ (vis_<ep>/ with `train`) the input image and mask, the predicted and the GT
+        depth, the predicted-versus-GT seen-surface cloud and - with `depth_pred_aligned` in `var` - both depth maps
+        stretched by the masked per-sample range of the GT (background 1, clamped), that arithmetic on the host in numpy
+        like the other dumps; `image_eroded` (the image with the eroded mask as alpha; the rmse is not drawn onto it)
+        when `var` has `mask_eroded` and `rmse`."""
+        from ..utils import util_vis
+        folder = "vis_{}".format(ep) if train else "dump"
+        os.makedirs(os.path.join(opt.output_path, folder), exist_ok=True)
+        idx = torch.as_tensor(var.idx).view(-1).tolist()
+        util_vis.dump_images(opt, idx, "image_input", var.rgb_input_map, masks=None, from_range=(0, 1), folder=folder)
+        util_vis.dump_images(opt, idx, "mask_input", var.mask_input_map, folder=folder)
+        util_vis.dump_depths(opt, idx, "depth_pred", var.depth_pred, var.mask_input_map, rescale=True, folder=folder)
+        util_vis.dump_depths(opt, idx, "depth_input", var.depth_input_map, var.mask_input_map, rescale=True, folder=folder)
+        if 'seen_points_pred' in var and 'seen_points_gt' in var:
+            util_vis.dump_pointclouds_compare(opt, idx, "seen_surface", var.seen_points_pred, var.seen_points_gt,
+                                              folder=folder)
+        if "depth_pred_aligned" in var:
+            host = lambda t: t.detach().float().cpu().numpy()                                      # noqa: E731
+            B = var.depth_input_map.shape[0]
+            mask = host(var.mask_eroded if 'mask_eroded' in var else var.mask_input_map)
+            gt, pred = host(var.depth_input_map), host(var.depth_pred_aligned)
+            lo = (gt * mask + (1 - mask) * 1000).reshape(B, -1).min(1).reshape(B, 1, 1, 1)
+            hi = (gt * mask).reshape(B, -1).max(1).reshape(B, 1, 1, 1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                vis = [np.clip((d - lo) / (hi - lo) * mask + (1 - mask), 0, 1) for d in (gt, pred)]
+            for name, d in zip(("depth_gt_aligned", "depth_pred_aligned"), vis):
+                util_vis.dump_depths(opt, idx, name, torch.from_numpy(d), None, rescale=False, folder=folder)
+            if "mask_eroded" in var and "rmse" in var:
+                util_vis.dump_images(opt, idx, "image_eroded", var.rgb_input_map, masks=var.mask_eroded, from_range=(0, 1),
+                                     folder=folder)

@@ -378,9 +378,9 @@ class Runner:
 
     @torch.no_grad()
     def evaluate(self, opt, ep=0, training=False):
-        """:335-516 without the visual dumps: returns dict(cd, dist_acc, dist_cov, f_scores) and, on
-        rank 0 with `opt.output_path`, writes <dataset>_full_results.txt / quantitative_<dataset>.txt /
-        cd_cat.txt in the reference's formats."""
+        """:335-516: returns dict(cd, dist_acc, dist_cov, f_scores) and, on rank 0 with `opt.output_path`, writes
+        <dataset>_full_results.txt / quantitative_<dataset>.txt / cd_cat.txt in the reference's formats.  The
+        per-sample visual dumps (dump_results) are opt-in: `--eval.dump_results`."""
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         if self.reducer is not None and training:      # every rank validates with rank 0's BatchNorm statistics
             self.reducer.sync_buffers()
@@ -389,6 +389,8 @@ class Runner:
         for it, batch in enumerate(self.test_loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it)
             eval_3D.eval_metrics(opt, var, self.graph.impl_network)
+            if not training and rank == 0 and getattr(opt.eval, "dump_results", False):     # :455-456, opt-in here
+                self.dump_results(opt, var, ep, write_new=(it == 0))
             cd_accs.append(var.cd_acc.float().view(-1))
             cd_comps.append(var.cd_comp.float().view(-1))
             f_scores.append(var.f_score.float().view(len(var.cd_acc.view(-1)), -1))
@@ -432,3 +434,31 @@ class Runner:
                     f.write("%.4f %.4f %.4f %5d %s\n" % ((a + c) / 2, a, c, int(sel.sum()),
                                                         label2cat[i] if label2cat else str(i)))
         return out
+
+    @torch.no_grad()
+    def dump_results(self, opt, var, ep, write_new=False, train=False):
+        """:564-591: the per-sample outputs of a batch under <output_path>/dump_<dataset_test>/ (vis_<ep>/ with `train`):
+        input image and mask, mesh and its turntable, depth maps, the predicted-versus-GT seen-surface cloud, and -
+        where `var` carries them - the attention animation, the attention cloud and the predicted-versus-GT dense cloud.
+        Poses are not drawn onto the image; the HTML index is not written."""
+        from ..utils import util_vis
+        folder = "vis_{}".format(ep) if train else "dump_{}".format(opt.data.dataset_test)
+        os.makedirs(os.path.join(opt.output_path, folder), exist_ok=True)
+        idx = torch.as_tensor(var.idx).view(-1).tolist()
+        util_vis.dump_images(opt, idx, "image_input", var.rgb_input_map, masks=None, from_range=(0, 1), folder=folder)
+        util_vis.dump_images(opt, idx, "mask_input", var.mask_input_map, folder=folder)
+        util_vis.dump_meshes(opt, idx, "mesh", var.mesh_pred, folder=folder)
+        util_vis.dump_meshes_viz(opt, idx, "mesh_viz", var.mesh_pred, folder=folder)           # image frames + gif
+        if 'depth_pred' in var:
+            util_vis.dump_depths(opt, idx, "depth_est", var.depth_pred, var.mask_input_map, rescale=True, folder=folder)
+        if 'depth_input_map' in var:
+            util_vis.dump_depths(opt, idx, "depth_input", var.depth_input_map, var.mask_input_map, rescale=True,
+                                 folder=folder)
+        if 'gt_surf_points' in var and 'seen_points' in var:
+            util_vis.dump_pointclouds_compare(opt, idx, "seen_surface", var.seen_points, var.gt_surf_points, folder=folder)
+        if 'attn_vis' in var:
+            util_vis.dump_attentions(opt, idx, "attn", var.attn_vis, folder=folder)
+        if 'attn_pc' in var:
+            util_vis.dump_pointclouds(opt, idx, "attn_pc", var.attn_pc["points"], var.attn_pc["colors"], folder=folder)
+        if 'dpc' in var and 'dpc_pred' in var:
+            util_vis.dump_pointclouds_compare(opt, idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)

@@ -7,7 +7,8 @@
     an error.
   * ``load_options(fname)``: a YAML file, with ``_parent_`` inheritance (:56-69).
   * ``override_options`` (:71-89): recursive merge; with safe_check a key that does not exist in the
-    file is an ERROR here (the reference asks interactively; a batch job cannot answer).
+    file is an ERROR here (the reference asks interactively; a batch job cannot answer), except the
+    opt-in switches of ``COMMAND_LINE_ONLY``, which no yaml file carries.
   * ``process_options`` (:91-112): seeds, ``output_path = output_root/group/name``, ``device``,
     ``H, W``, default ``freq.eval``.
   * ``set(opt_cmd)`` (:36-54): the three together, as train.py / evaluate.py / demo.py call it.
@@ -88,13 +89,18 @@ def load_options(fname):
     return opt
 
 
+# switches that are off unless the command line gives them: absent from the yaml files on purpose, so that the option
+# files (and the options.yaml a run saves) stay what they are
+COMMAND_LINE_ONLY = ("eval.dump_results",)
+
+
 def override_options(opt, opt_over, key_stack=None, safe_check=False):
     key_stack = key_stack or []
     for key, value in opt_over.items():
         if isinstance(value, dict):
             opt[key] = override_options(opt.get(key, EasyDict()), value, key_stack + [key], safe_check)
         else:
-            if safe_check and key not in opt:
+            if safe_check and key not in opt and ".".join(key_stack + [key]) not in COMMAND_LINE_ONLY:
                 raise KeyError("option %s is not in the yaml file (the reference prompts here; add it to the "
                                "file or pass safe_check=False)" % ".".join(key_stack + [key]))
             opt[key] = value

@@ -1,9 +1,12 @@
-"""Result dumps for demo.py.  The reference's utils/util_vis.py renders with pyrender / cv2 / trimesh, which this image
-does not have (and pyrender needs OpenGL, which a headless compute node does not have either).  Here: input image and
-mask as PNG, depth maps as 16-bit PNG, meshes as Wavefront OBJ with welded vertices, attention maps as .npy or - given the
-frames of ``compute_level_grid(vis_attn=True)`` - as GIF, and the rotating mesh render of ``dump_meshes_viz`` /
-``visualize_mesh`` from the library's own rasteriser (csrc/render.hip: all frames in one call, one copy back to the host).
-Its geometry and shading formula are pinned by tests; pyrender's PBR pixels are not reproduced (parity unpinned).
+"""Result dumps for demo.py and Runner.dump_results.  The reference's utils/util_vis.py renders with pyrender / cv2 /
+trimesh, which this image does not have (and pyrender needs OpenGL, which a headless compute node does not have either).
+Here: input image and mask as PNG, depth maps as 16-bit PNG, meshes as Wavefront OBJ with welded vertices, attention maps as
+.npy or - given the frames of ``compute_level_grid(vis_attn=True)`` - as GIF, the rotating mesh render of ``dump_meshes_viz``
+/ ``visualize_mesh`` from the library's own rasteriser (csrc/render.hip: all frames in one call, one copy back to the host),
+the textured seen-surface mesh of ``dump_seen_surface`` / ``create_seen_surface`` (csrc/seen_mesh.hip: validity, edge tests
+and the order-preserving compaction of a whole batch in one call; the .obj / .mtl text is the reference's byte for byte) and
+the coloured point clouds of ``dump_pointclouds_compare`` / ``dump_pointclouds`` as binary PLY.
+The turntable's geometry and shading formula are pinned by tests; pyrender's PBR pixels are not reproduced (parity unpinned).
 File names follow the reference's `<output_path>/<folder>/<idx>_<name>.<ext>` pattern."""
 import os
 
@@ -249,3 +252,162 @@ def dump_meshes_viz(opt, idx, name, meshes, save_frames=True, folder="dump"):
             continue
         fname = _path(opt, folder, i, name, "gif")[:-4]
         visualize_mesh(mesh, fname, write_frames=save_frames, pose_normalize=True, device=getattr(opt, "device", "cuda"))
+
+
+# ---- seen-surface mesh (utils/util_vis.py:129-170) ----
+
+def seen_mesh_buffers(xyz, mask=None, connect_thres=0.005):
+    """zs_seen_mesh on a GPU point map ``xyz`` [B,H,W,3] (``mask``: B*H*W values, a pixel with mask <= 0.5 is no vertex) ->
+    the GPU tensors (vert_id int32 [B,H,W], vert_pixel int32 [B,H*W], verts fp32 [B,H*W,3], faces int32
+    [B,2(H-1)(W-1),3], counts int32 [B,2]).  Rows of the three compacted buffers beyond ``counts`` are unwritten."""
+    import torch
+    from .. import _lib
+    if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda):
+        raise ValueError("seen_surface_mesh: xyz must be a GPU tensor (there is no CPU path)")
+    if xyz.dim() != 4 or xyz.shape[3] != 3:
+        raise ValueError("seen_surface_mesh: xyz must be [B,H,W,3], got %s" % (tuple(xyz.shape),))
+    lib = _lib.load()
+    dev = xyz.device
+    B, H, W = xyz.shape[:3]
+    xyz = xyz.detach().to(torch.float32).contiguous()
+    if mask is not None:
+        if not mask.is_cuda or mask.numel() != B * H * W:
+            raise ValueError("seen_surface_mesh: mask must be a GPU tensor of B*H*W values")
+        mask = mask.detach().to(torch.float32).contiguous()
+    cells = max(H - 1, 0) * max(W - 1, 0)
+    vert_id = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    vert_pixel = torch.empty(B, H * W, dtype=torch.int32, device=dev)
+    verts = torch.empty(B, H * W, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(B, 2 * cells, 3, dtype=torch.int32, device=dev)
+    counts = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+    if B * H * W:
+        ws = torch.empty(max(lib.zs_seen_mesh_workspace_bytes(B, H, W) // 8, 1), dtype=torch.int64, device=dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_seen_mesh(_lib.ptr(xyz), _lib.ptr(mask), B, H, W, float(connect_thres), _lib.ptr(vert_id),
+                                        _lib.ptr(vert_pixel), _lib.ptr(verts), _lib.ptr(faces) if cells else None,
+                                        _lib.ptr(counts), _lib.ptr(ws), _lib.current_stream_ptr(dev)), "zs_seen_mesh")
+    return vert_id, vert_pixel, verts, faces, counts
+
+
+def seen_surface_mesh(xyz, mask=None, connect_thres=0.005):
+    """The seen-surface meshes of a batch of camera-frame point maps, by the rules of create_seen_surface
+    (utils/util_vis.py:137-170): ``xyz`` GPU tensor [B,H,W,3] -> per image (verts float32 [n,3], pixels int32 [n] = raster
+    index y*W+x of every vertex, faces int32 [m,3] = 1-based vertex indices) as numpy arrays.  One kernel call for the
+    batch; the copy back is the counts first, then only the used prefixes of the three buffers (one copy each)."""
+    import torch
+    _, vert_pixel, verts, faces, counts = seen_mesh_buffers(xyz, mask, connect_thres)
+    n = counts.cpu().numpy()
+    B = n.shape[0]
+    if B == 0:
+        return []
+
+    def used(buf, col):
+        return torch.cat([buf[b, :int(n[b, col])] for b in range(B)]).cpu().numpy()
+
+    v, p, f = used(verts, 0), used(vert_pixel, 0), used(faces, 1)
+    vo, fo = np.concatenate([[0], np.cumsum(n[:, 0])]), np.concatenate([[0], np.cumsum(n[:, 1])])
+    return [(v[vo[b]:vo[b + 1]], p[vo[b]:vo[b + 1]], f[fo[b]:fo[b + 1]]) for b in range(B)]
+
+
+def write_seen_surface_obj(output_folder, sample_ID, obj_name, img_path, verts, pixels, faces, H, W):
+    """The host half of create_seen_surface: ``<output_folder>/<sample_ID>_<obj_name>.mtl`` and ``.obj`` with the
+    reference's text byte for byte (utils/util_vis.py:141-170) - per vertex ``v %.4f %.4f %.4f`` and ``vt %.8f %.8f`` with
+    u = x / W, v = 1 - y / H in float64 from the pixel index (fp32 uv would change the eighth decimal), then ``usemtl`` and
+    one ``f a/a b/b c/c`` per face.  Formatted in bulk: one % per block, one write per file."""
+    verts = np.asarray(verts, np.float32).reshape(-1, 3)
+    pixels = np.asarray(pixels, np.int64).reshape(-1)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    assert len(verts) == len(pixels)
+    stem = "{}/{}_{}".format(output_folder, sample_ID, obj_name)
+    with open(stem + ".mtl", "w") as f:
+        f.write("newmtl material_0\n"
+                "Ka 0.200000 0.200000 0.200000\n"
+                "Kd 0.752941 0.752941 0.752941\n"
+                "Ks 1.000000 1.000000 1.000000\n"
+                "Tr 1.000000\n"
+                "illum 2\n"
+                "Ns 0.000000\n"
+                "map_Ka %s\n"
+                "map_Kd %s\n" % (img_path, img_path))
+    y, x = pixels // W, pixels % W
+    u, v = x.astype(np.float64) / float(W), 1.0 - y.astype(np.float64) / float(H)
+    rows = np.concatenate([verts.astype(np.float64), u[:, None], v[:, None]], axis=1)
+    text = ["mtllib {}_{}.mtl\n".format(sample_ID, obj_name),
+            ("v %.4f %.4f %.4f\nvt %.8f %.8f\n" * len(rows)) % tuple(rows.ravel().tolist()),
+            "usemtl material_0\n",
+            ("f %d/%d %d/%d %d/%d\n" * len(faces)) % tuple(np.repeat(faces, 2, axis=1).ravel().tolist())]
+    with open(stem + ".obj", "w") as f:
+        f.write("".join(text))
+
+
+def create_seen_surface(sample_ID, img_path, XYZ, output_folder, obj_name, connect_thres=0.005):
+    """utils/util_vis.py:137-170 for one GPU point map ``XYZ`` [H,W,3]: the mesh from zs_seen_mesh, the files from
+    write_seen_surface_obj."""
+    H, W = XYZ.shape[:2]
+    (verts, pixels, faces), = seen_surface_mesh(XYZ[None], None, connect_thres)
+    write_seen_surface_obj(output_folder, sample_ID, obj_name, img_path, verts, pixels, faces, H, W)
+
+
+def dump_seen_surface(opt, idx, obj_name, img_name, seen_projs, folder='dump', masks=None):
+    """utils/util_vis.py:129-134: ``seen_projs`` [B,H,W,3] on the GPU -> ``<idx>_<obj_name>.obj/.mtl`` per sample, textured
+    with ``<idx>_<img_name>.png`` of the same folder.  The whole batch goes through one kernel call; ``masks`` (B*H*W
+    values, optional) is the kernel's validity mask."""
+    out_folder = "{}/{}".format(opt.output_path, folder)
+    os.makedirs(out_folder, exist_ok=True)
+    H, W = seen_projs.shape[1:3]
+    for i, (verts, pixels, faces) in zip(idx, seen_surface_mesh(seen_projs, masks)):
+        write_seen_surface_obj(out_folder, i, obj_name, "{}_{}.png".format(i, img_name), verts, pixels, faces, H, W)
+
+
+# ---- coloured point clouds (utils/util_vis.py:172-197) ----
+
+_PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                        ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
+
+
+def write_pointcloud_ply(path, points, colors):
+    """``points`` [N,3] and ``colors`` [N,3] uint8 -> binary little-endian PLY: ``element vertex N``, ``property float
+    x/y/z``, ``property uchar red/green/blue/alpha`` (alpha 255) - the layout trimesh writes for a coloured PointCloud.
+    trimesh is not a dependency of this package: byte parity with its exporter (its header comment included) is unpinned."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    colors = np.asarray(colors, np.uint8).reshape(-1, 3)
+    assert len(points) == len(colors)
+    rec = np.empty(len(points), _PLY_VERTEX)
+    rec["x"], rec["y"], rec["z"] = points[:, 0], points[:, 1], points[:, 2]
+    rec["red"], rec["green"], rec["blue"], rec["alpha"] = colors[:, 0], colors[:, 1], colors[:, 2], 255
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n"
+              "property float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n"
+              "end_header\n" % len(points))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def dump_pointclouds_compare(opt, idx, name, preds, gts, folder='dump'):
+    """utils/util_vis.py:172-184: ``<idx>_<name>.ply`` with the prediction [N1,3] in red (255,0,0) and the ground truth
+    [N2,3] in green (0,255,0), prediction rows first (binary PLY of write_pointcloud_ply; parity with trimesh unpinned)."""
+    for b, i in enumerate(idx):
+        pred, gt = _host(preds[b]).reshape(-1, 3), _host(gts[b]).reshape(-1, 3)
+        colors = np.zeros((len(pred) + len(gt), 3), np.uint8)
+        colors[:len(pred), 0] = 255
+        colors[len(pred):, 1] = 255
+        write_pointcloud_ply(_path(opt, folder, i, name, "ply"), np.vstack([pred, gt]), colors)
+
+
+def dump_pointclouds(opt, idx, name, pcs, colors, folder='dump', colormap='jet'):
+    """utils/util_vis.py:186-197: ``<idx>_<name>.ply`` of every cloud [N,3]; ``colors`` [N,3] uint8, or [N,1] in [0,1] mapped
+    through the 256-entry jet table of eval_3D._jet_lut (entry floor(255 c); matplotlib is not a dependency, another
+    colormap raises).  Binary PLY of write_pointcloud_ply; parity with trimesh unpinned."""
+    if colormap != 'jet':
+        raise ValueError("dump_pointclouds: only the 'jet' colormap is built in, got %r" % (colormap,))
+    from .eval_3D import _jet_lut
+    for i, pc, color in zip(idx, pcs, colors):
+        color = _host(color)
+        if color.ndim == 2 and color.shape[1] == 1:
+            color = _jet_lut()[np.uint8(255 * np.clip(color[:, 0].astype(np.float64), 0.0, 1.0))]
+        write_pointcloud_ply(_path(opt, folder, i, name, "ply"), _host(pc), color[:, :3])
