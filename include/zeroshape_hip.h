@@ -24,6 +24,8 @@
  *   zs_fscore            <- compute_fscore, utils/eval_3D.py:215-231
  *   zs_mc_*, zs_mesh_*   <- convert_to_explicit, utils/eval_3D.py:233-263 (PyMCubes
  *                           marching_cubes + trimesh.sample on the host)
+ *   zs_mesh_weld, zs_mesh_weld_vertices <- the (vertices, triangles) mcubes.marching_cubes
+ *                           returns and trimesh's vertex_normals, utils/eval_3D.py:250-256
  *   zs_mesh_stats, zs_render_frames <- dump_meshes_viz, scale_to_unit_cube, visualize_mesh,
  *                           utils/util_vis.py:112-127, 310-405 (trimesh + pyrender on OpenGL)
  *   zs_seen_mesh_workspace_bytes, zs_seen_mesh <- create_seen_surface, utils/util_vis.py:137-170
@@ -52,7 +54,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 43
+#define ZS_ABI_VERSION 44
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -385,6 +387,36 @@ int zs_mc_emit(const float *vol, int G, float iso, const int8_t *tri_table, int 
                float *tris, int n_tris, void *stream);
 int zs_mesh_sample(const float *tris, int n_tris, int n_samples, uint64_t seed, double *cum_area,
                    float *points, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Welding a triangle soup tris[n_tris][3][3] fp32 into the indexed form mcubes.marching_cubes
+ * returns (utils/eval_3D.py:250-256), with the vertex normals trimesh derives for free.  Any
+ * soup: corners weld when their coordinates are equal, whatever produced them.
+ *   key of a corner : the uint32 bit patterns of (x + 0.0f, y + 0.0f, z + 0.0f): -0.0 and 0.0
+ *                     are one vertex
+ *   vertex order    : ascending (x, y, z) key, lexicographic, compared as UNSIGNED INTEGERS -
+ *                     the row order of np.unique(keys, axis=0), not float order (negative
+ *                     coordinates come after positive ones, descending)
+ *   vertices [V][3] : the unchanged bits of the FIRST corner in soup order that has the key
+ *   faces [n_tris][3]: int32, faces[t][k] = index of the vertex of corner 3 t + k
+ *   normals [V][3]  : or NULL.  N = sum of cross(v1 - v0, v2 - v0) over the triangles of the
+ *                     vertex's corners in ascending soup order (a triangle that holds the vertex
+ *                     twice counts twice), every operation in fp64 as written; N / |N| in fp64,
+ *                     rounded to fp32; (0, 0, 0) when |N| is zero, infinite or NaN
+ * A stable radix sort of the corners, head flags, one scan, a scatter; a thread per vertex for
+ * the vertices and normals.  No atomics: two runs give the same bits.
+ *   zs_mesh_weld          writes faces and the vertex count *n_verts (device int); the caller
+ *                         reads those 4 bytes, allocates, and calls
+ *   zs_mesh_weld_vertices with the SAME tris, n_tris and scratch, untouched in between.
+ *                         n_verts above the weld's own count writes only the weld's vertices.
+ * scratch: zs_mesh_weld_scratch_bytes(n_tris) bytes, 8-byte aligned (0 for n_tris <= 0 and
+ * beyond the limit n_tris <= 2^29).  n_tris == 0 is a mesh of zero vertices: both calls return 1
+ * and touch nothing, *n_verts included.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_weld_scratch_bytes(int n_tris);
+int zs_mesh_weld(const float *tris, int n_tris, int *faces, int *n_verts, void *scratch, void *stream);
+int zs_mesh_weld_vertices(const float *tris, int n_tris, const void *scratch, int n_verts,
+                          float *vertices, float *normals, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Mesh turntable renderer (replaces dump_meshes_viz / scale_to_unit_cube / visualize_mesh,

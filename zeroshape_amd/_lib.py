@@ -105,6 +105,9 @@ SIGNATURES = {
     "zs_mc_emit": (_c_int, [_c_void_p, _c_int, ctypes.c_float, _c_void_p, _c_int, _c_void_p, _c_void_p,
                             ctypes.c_float, ctypes.c_float, _c_void_p, _c_int, _c_void_p]),
     "zs_mesh_sample": (_c_int, [_c_void_p, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_weld_scratch_bytes": (_c_size_t, [_c_int]),
+    "zs_mesh_weld": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_weld_vertices": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_stats_scratch_bytes": (_c_size_t, [_c_int]),
     "zs_mesh_stats": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "zs_render_zbuffer_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
@@ -221,7 +224,7 @@ SIGNATURES = {
     "zs_readout_concat_bwd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
 }
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 _lib = None
 
 

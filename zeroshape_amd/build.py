@@ -41,6 +41,8 @@ EXTRA = {
     "attn_vis.hip": ["-ffp-contract=off"],
     # edge lengths reproducible op for op by the numpy restatement in tests/seen_mesh_ref.py
     "seen_mesh.hip": ["-ffp-contract=off"],
+    # fp64 normals reproducible op for op by the numpy restatement in utils/eval_3D.py (vertex_normals_host)
+    "mesh_weld.hip": ["-ffp-contract=off"],
 }
 
 

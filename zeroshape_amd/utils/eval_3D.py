@@ -19,7 +19,8 @@ ICP, iso-surface extraction - is a HIP kernel behind the C ABI and raises if
 libzeroshape_hip.so is missing (no fallback).
 
 ``convert_to_explicit`` (utils/eval_3D.py:233-263: PyMCubes + trimesh on the host in the
-reference) runs on the GPU here: csrc/marching_cubes.hip.
+reference) runs on the GPU here: csrc/marching_cubes.hip.  The meshes it returns keep
+their triangles in HBM; the indexed form and the vertex normals come from csrc/mesh_weld.hip (``weld_mesh``) when read.
 """
 
 import numpy as np
@@ -549,7 +550,7 @@ def _surface_clouds(opt, level_vox, seed=0):
     range_min, range_max = opt.eval.range
     for i in range(level_vox.shape[0]):
         tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
-        meshes.append(SimpleMesh(tris.cpu().numpy()))
+        meshes.append(SimpleMesh(tris))                  # stays in HBM until a dump reads it
         clouds.append(pts)
     return meshes, torch.stack(clouds, dim=0)
 
@@ -660,13 +661,37 @@ class SimpleMesh(object):
     ``triangles`` [n,3,3] = the iso-surface kernel's triangle soup (what sampling reads); ``vertices`` [v,3] / ``faces`` [n,3] =
     the INDEXED form ``mcubes.marching_cubes`` returns (utils/eval_3D.py:250-256), welded lazily on first access: a vertex on
     a grid edge is computed from the same two corner values by every cube sharing the edge, so equal vertices are equal bit
-    for bit and welding = unique rows of the soup (``vertices[faces]`` reproduces ``triangles`` exactly)."""
+    for bit and welding = unique rows of the soup (``vertices[faces]`` reproduces ``triangles`` exactly).
+    ``vertex_normals`` [v,3] float32 (trimesh's name): the area-weighted formula of vertex_normals_host; parity with
+    trimesh's own weighting is unpinned (trimesh is not a dependency of this package).
+
+    Built from a GPU tensor the mesh stays in HBM: ``device_triangles`` is that tensor (the turntable renders from it),
+    the weld and the normals come from weld_mesh (csrc/mesh_weld.hip) on first access, and ``triangles`` / ``vertices`` /
+    ``faces`` / ``vertex_normals`` are host copies made when somebody reads them - float32, float32, int64, float32, the same
+    values either way.  Built from an array nothing needs a GPU (``device_triangles`` is None): the numpy weld below, which is
+    also the kernels' checker."""
 
     def __init__(self, triangles):
-        self.triangles = np.asarray(triangles, np.float32).reshape(-1, 3, 3)
-        self._indexed = None
+        self.device_triangles = self._triangles = self._indexed = self._normals = None
+        if isinstance(triangles, torch.Tensor) and triangles.is_cuda:
+            self.device_triangles = triangles.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
+        else:
+            self._triangles = np.asarray(triangles, np.float32).reshape(-1, 3, 3)
 
-    def _weld(self):
+    @property
+    def triangles(self):
+        if self._triangles is None:
+            self._triangles = self.device_triangles.cpu().numpy()
+        return self._triangles
+
+    def _weld(self, normals=False):
+        if self.device_triangles is not None:
+            if self._indexed is None or (normals and self._normals is None):
+                out = [t.cpu().numpy() for t in weld_mesh(self.device_triangles, normals=normals)]
+                self._indexed = (out[0], out[1].astype(np.int64))
+                if normals:
+                    self._normals = out[2]
+            return self._indexed
         if self._indexed is None:
             soup = np.ascontiguousarray(self.triangles.reshape(-1, 3))
             if len(soup) == 0:
@@ -675,6 +700,8 @@ class SimpleMesh(object):
                 keys = (soup + np.float32(0.0)).view(np.uint32)          # -0.0 and 0.0 are one vertex
                 _, first, inverse = np.unique(keys, axis=0, return_index=True, return_inverse=True)
                 self._indexed = (soup[first], inverse.reshape(-1, 3).astype(np.int64))
+        if normals and self._normals is None:
+            self._normals = vertex_normals_host(self.triangles, self._indexed[1], len(self._indexed[0]))
         return self._indexed
 
     @property
@@ -684,6 +711,61 @@ class SimpleMesh(object):
     @property
     def faces(self):
         return self._weld()[1]
+
+    @property
+    def vertex_normals(self):
+        self._weld(normals=True)
+        return self._normals
+
+
+def vertex_normals_host(triangles, faces, n_vertices):
+    """The normals of zs_mesh_weld_vertices restated in numpy, operation for operation: per vertex the sum of
+    cross(v1 - v0, v2 - v0) over its corners' triangles in ascending soup order (``np.add.at`` adds in index order; a triangle
+    that holds the vertex twice counts twice) in float64, normalised in float64, rounded to float32; a zero or non-finite sum
+    gives (0, 0, 0).  ``triangles`` [n,3,3] float32, ``faces`` [n,3] -> [n_vertices,3] float32."""
+    t = np.asarray(triangles, np.float32).reshape(-1, 3, 3).astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        a, b = t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]
+        face_n = np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1],
+                           a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                           a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+        total = np.zeros((int(n_vertices), 3), np.float64)
+        np.add.at(total, np.asarray(faces, np.int64).reshape(-1), np.repeat(face_n, 3, axis=0))
+        length = np.sqrt(total[:, 0] * total[:, 0] + total[:, 1] * total[:, 1] + total[:, 2] * total[:, 2])
+        ok = (length > 0.0) & (length < np.inf)
+        return np.where(ok[:, None], total / np.where(ok, length, 1.0)[:, None], 0.0).astype(np.float32)
+
+
+@torch.no_grad()
+def weld_mesh(tris, normals=False):
+    """A triangle soup [n,3,3] on the GPU -> (vertices [V,3] fp32, faces [n,3] int32[, normals [V,3] fp32]), GPU tensors on
+    the soup's device, enqueued on the current stream: zs_mesh_weld + zs_mesh_weld_vertices (csrc/mesh_weld.hip).  The
+    semantics of SimpleMesh's numpy weld, bit for bit - np.unique's row order of the (x + 0, y + 0, z + 0) bit patterns, the
+    first occurrence's own bits as the stored vertex - and the normals of vertex_normals_host.  One 4-byte device-to-host
+    copy: the vertex count, which sizes the outputs."""
+    from .. import _lib
+    lib = _lib.load()
+    if not (isinstance(tris, torch.Tensor) and tris.is_cuda):
+        raise ValueError("weld_mesh: tris must be a GPU tensor (SimpleMesh welds an array on the host)")
+    soup = tris.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
+    n, dev = soup.shape[0], soup.device
+    faces = torch.empty(n, 3, dtype=torch.int32, device=dev)
+    n_verts = 0
+    if n:
+        scratch = torch.empty(lib.zs_mesh_weld_scratch_bytes(n) // 8, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        stream = _lib.current_stream_ptr(dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_weld(_lib.ptr(soup), n, _lib.ptr(faces), _lib.ptr(count), _lib.ptr(scratch), stream),
+                       "zs_mesh_weld")
+            n_verts = int(count.item())                      # 4-byte D2H: sizes the outputs
+    vertices = torch.empty(n_verts, 3, dtype=torch.float32, device=dev)
+    vnormals = torch.empty(n_verts, 3, dtype=torch.float32, device=dev) if normals else None
+    if n:
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_weld_vertices(_lib.ptr(soup), n, _lib.ptr(scratch), n_verts, _lib.ptr(vertices),
+                                                 _lib.ptr(vnormals), stream), "zs_mesh_weld_vertices")
+    return (vertices, faces, vnormals) if normals else (vertices, faces)
 
 
 _MC_TABLES = {}
@@ -752,7 +834,7 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
         range_min, range_max = opt.eval.range
         tris, pts = extract_surface(vol, isoval, range_min, range_max,
                                     opt.eval.num_points if to_pointcloud else 0, seed + i)
-        meshes.append(SimpleMesh(tris.cpu().numpy()))
+        meshes.append(SimpleMesh(tris))                  # stays in HBM until a dump reads it
         if to_pointcloud:
             clouds.append(pts.cpu().numpy().astype(np.float64))
     if to_pointcloud:

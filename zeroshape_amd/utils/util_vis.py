@@ -64,17 +64,25 @@ def dump_depths(opt, idx, name, depths, masks=None, rescale=False, folder="dump"
         Image.fromarray((x.clip(0, 1) * 65535 + 0.5).astype(np.uint16)).save(_path(opt, folder, i, name, "png"))
 
 
-def dump_meshes(opt, idx, name, meshes, folder="dump", **_):
+def dump_meshes(opt, idx, name, meshes, folder="dump", normals=False, **_):
     """meshes: eval_3D.SimpleMesh objects -> OBJ with shared vertices (the indexed form mcubes.marching_cubes returns in
-    the reference; the marching-cubes kernel emits bit-identical coordinates for shared vertices)."""
+    the reference; the marching-cubes kernel emits bit-identical coordinates for shared vertices): a comment line, one
+    ``v %.6f %.6f %.6f`` per vertex, one ``f %d %d %d`` per face.  With ``normals`` also one ``vn %.6f %.6f %.6f`` per vertex
+    (mesh.vertex_normals) after the vertices, and the faces as ``f a//a b//b c//c``, so that a viewer shades smoothly.
+    Formatted in bulk, one % per block and one write per file: the same bytes as a write per line, which took 64 ms for the
+    vox-128 mesh."""
     for i, mesh in zip(idx, meshes):
+        vn = mesh.vertex_normals if normals else None             # (first: a GPU-built mesh then welds once)
         verts, faces = mesh.vertices, mesh.faces + 1              # the indexed form (eval_3D.SimpleMesh welds the soup)
+        text = ["# zeroshape_amd mesh: %d vertices, %d faces\n" % (len(verts), len(faces)),
+                ("v %.6f %.6f %.6f\n" * len(verts)) % tuple(verts.astype(np.float64).ravel().tolist())]
+        if normals:
+            text += [("vn %.6f %.6f %.6f\n" * len(vn)) % tuple(vn.astype(np.float64).ravel().tolist()),
+                     ("f %d//%d %d//%d %d//%d\n" * len(faces)) % tuple(np.repeat(faces, 2, axis=1).ravel().tolist())]
+        else:
+            text.append(("f %d %d %d\n" * len(faces)) % tuple(faces.ravel().tolist()))
         with open(_path(opt, folder, i, name, "obj"), "w") as f:
-            f.write("# zeroshape_amd mesh: %d vertices, %d faces\n" % (len(verts), len(faces)))
-            for v in verts:
-                f.write("v %.6f %.6f %.6f\n" % tuple(v))
-            for t in faces:
-                f.write("f %d %d %d\n" % tuple(t))
+            f.write("".join(text))
 
 
 def dump_attentions(opt, idx, name, attn, folder="dump", **_):
@@ -219,6 +227,13 @@ def render_mesh_frames(triangles, positions, rotations, resolution, return_depth
     return out[0] if len(out) == 1 else out
 
 
+def _soup(mesh):
+    """The triangle soup of ``mesh``: a SimpleMesh's GPU tensor when it was built from one (no host copy, no second upload),
+    else its host array; anything else is taken to be the soup itself."""
+    soup = getattr(mesh, "device_triangles", None)
+    return soup if soup is not None else getattr(mesh, "triangles", mesh)
+
+
 def visualize_mesh(mesh, output_path, resolution=(200, 200), write_gif=True, write_frames=True, time_per_frame=80,
                    n_frames=180, pose_normalize=False, device="cuda"):
     """utils/util_vis.py:348-405.  ``mesh``: an eval_3D.SimpleMesh, or a triangle soup [n,3,3] as tensor or array (a host
@@ -227,7 +242,7 @@ def visualize_mesh(mesh, output_path, resolution=(200, 200), write_gif=True, wri
     ``write_frames``, ``<output_path>/0000.jpg ...``.  Returns the frames, uint8 [n_frames,H,W,3]."""
     import torch
     from PIL import Image
-    soup = getattr(mesh, "triangles", mesh)
+    soup = _soup(mesh)
     if not isinstance(soup, torch.Tensor):
         soup = torch.from_numpy(np.ascontiguousarray(soup, np.float32)).to(device)
     soup = soup.to(torch.float32).reshape(-1, 3, 3)
@@ -248,7 +263,7 @@ def dump_meshes_viz(opt, idx, name, meshes, save_frames=True, folder="dump"):
     turned, centred and scaled to the unit cube.  An empty mesh writes nothing and raises nothing (the reference's
     ``try/except`` around scale_to_unit_cube)."""
     for i, mesh in zip(idx, meshes):
-        if len(getattr(mesh, "triangles", mesh)) == 0:
+        if len(_soup(mesh)) == 0:                    # (a tensor's length is its shape: no copy to the host)
             continue
         fname = _path(opt, folder, i, name, "gif")[:-4]
         visualize_mesh(mesh, fname, write_frames=save_frames, pose_normalize=True, device=getattr(opt, "device", "cuda"))
