@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 44
+#define ZS_ABI_VERSION 45
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -247,6 +247,18 @@ int zs_sdf_query_grid_split(const void *split_programs, size_t program_stride_by
  *   zs_sdf_block0_tables      that kernel alone: tables[batch][4096] floats = [b_proj 256][c 768][T 3,072] of each split
  *                             program, in the kernel's register order (zeroshape_amd/program.py: block0_window) */
 int zs_sdf_block0_tables(const void *split_programs, size_t program_stride_bytes, int batch, float *tables, void *stream);
+
+/* Block 0 from a compact stream of its own (ABI 45).  With the table, a head's q, k, v and its 224 point-to-latent logits are
+ * rank-5 maps of u = (rstd x, rstd y, rstd z, rstd, 1): one v_mfma_f32_32x32x16_f16 per 32 x 32 tile on packed operands
+ * instead of K-blocks of three.  While tables and streams fit the head of `workspace` (175 images per launch) every split
+ * launch also writes, behind the tables, 544 KiB per image: block 0's 8 x 34 K-block slots in consumption order (packed
+ * operands, and copies of the program's V and proj K-blocks), and the decode kernel streams block 0 from there before it
+ * continues in the program at K-block 736 (4,464 slots and 13,352 MFMAs per wave tile instead of 4,544 and 13,632).
+ * ZS_SPLIT_BLOCK0_STREAM=program in the environment (read per launch), or a larger batch, selects the table path above.
+ *   zs_sdf_block0_streams     that kernel alone: streams[batch][557,056] bytes from the split programs and their tables
+ *                             (zs_sdf_block0_tables; zeroshape_amd/program.py: block0_stream) */
+int zs_sdf_block0_streams(const void *split_programs, size_t program_stride_bytes, int batch, const float *tables,
+                          void *streams, void *stream);
 
 /* As zs_sdf_query_grid / zs_sdf_query_grid_split, for the points [point_begin, point_end) of
  * the grid in its memory order (x slowest, z fastest): out[batch][point_end - point_begin].

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Block 0's q/k/v from the rank-4 table (default) vs from its GEMMs (ZS_SPLIT_BLOCK0_GEMM=1) in ONE process on ONE box.
+"""Block 0's three arms in ONE process on ONE box: from its compact stream (default), q/k/v from the rank-4 table with the
+program's stream (ZS_SPLIT_BLOCK0_STREAM=program), from its GEMMs (ZS_SPLIT_BLOCK0_GEMM=1).
 
-The variable is read per launch, so the arms alternate block by block (blocks of `--block` launches, event-timed on the launch
-stream), in the style of tools/ab_tile_order.py: the whole 129^3 grid through zs_sdf_query_grid_range_split on a prepared
-state (launch only: table kernel + decode kernel + the empty fp32 re-evaluation).
+The variables are read per launch, so the arms alternate block by block (blocks of `--block` launches, event-timed on the
+launch stream; the order of the arms rotates from round to round), in the style of tools/ab_tile_order.py: the whole 129^3
+grid through zs_sdf_query_grid_range_split on a prepared state (launch only: table / stream kernels + decode kernel + the
+empty fp32 re-evaluation).
 
-    python tools/ab_block0_tables.py [--launches 40] [--block 4] > profiles/block0_tables_ab.txt
+    python tools/ab_block0_tables.py [--launches 40] [--block 4] > profiles/block0_stream_ab.txt
 """
 import argparse
 import os
@@ -21,11 +23,16 @@ from zeroshape_amd.model.shape.implicit import Implicit        # noqa: E402
 from zeroshape_amd.utils.pos_embed import get_2d_sincos_pos_embed   # noqa: E402
 
 
+ARMS = ("gemm", "table", "stream")
+
+
 def set_arm(arm):
+    os.environ.pop("ZS_SPLIT_BLOCK0_GEMM", None)
+    os.environ.pop("ZS_SPLIT_BLOCK0_STREAM", None)
     if arm == "gemm":
         os.environ["ZS_SPLIT_BLOCK0_GEMM"] = "1"
-    else:
-        os.environ.pop("ZS_SPLIT_BLOCK0_GEMM", None)
+    elif arm == "table":
+        os.environ["ZS_SPLIT_BLOCK0_STREAM"] = "program"
 
 
 def main():
@@ -57,30 +64,32 @@ def main():
         e1.record(stream)
         return e0, e1, out
     outs = {}
-    for arm in ("gemm", "table"):
+    for arm in ARMS:
         for _ in range(3):
-            outs[arm] = one(arm)[2]
+            outs[arm] = one(arm)[2].clone()
     torch.cuda.synchronize()
-    diff = float((outs["table"] - outs["gemm"]).abs().max())
     evs = []
     for blk in range(a.launches // a.block):
-        for arm in (("gemm", "table") if blk % 2 == 0 else ("table", "gemm")):
+        for arm in ARMS[blk % 3:] + ARMS[:blk % 3]:
             for _ in range(a.block):
                 evs.append((arm,) + one(arm)[:2])
     torch.cuda.synchronize()
-    set_arm("table")
-    times = {"gemm": [], "table": []}
+    set_arm("stream")
+    times = {arm: [] for arm in ARMS}
     for arm, e0, e1 in evs:
         times[arm].append(e0.elapsed_time(e1))
-    print("# block 0 q/k/v: table (default) vs GEMMs (ZS_SPLIT_BLOCK0_GEMM=1), one process, alternating blocks of %d launches, "
-          "%d launches per arm, vox %d" % (a.block, len(times["table"]), a.vox_res))
-    print("# max |occupancy(table) - occupancy(gemm)| over the grid: %.3g" % diff)
+    print("# block 0: GEMMs (ZS_SPLIT_BLOCK0_GEMM=1) vs table (ZS_SPLIT_BLOCK0_STREAM=program) vs compact stream (default), one "
+          "process, alternating blocks of %d launches, %d launches per arm, vox %d" % (a.block, len(times["stream"]), a.vox_res))
+    for x, y in (("table", "gemm"), ("stream", "gemm"), ("stream", "table")):
+        print("# max |occupancy(%s) - occupancy(%s)| over the grid: %.3g" % (x, y, float((outs[x] - outs[y]).abs().max())))
     print("%-6s %9s %9s %9s %9s" % ("arm", "mean ms", "median", "min", "max"))
-    for arm in ("gemm", "table"):
+    med, mean = {}, {}
+    for arm in ARMS:
         t = sorted(times[arm])
-        print("%-6s %9.3f %9.3f %9.3f %9.3f" % (arm, sum(t) / len(t), t[len(t) // 2], t[0], t[-1]))
-    g, t = sorted(times["gemm"]), sorted(times["table"])
-    print("# table / gemm (median): %.4f   (mean): %.4f" % (t[len(t) // 2] / g[len(g) // 2], sum(t) / len(t) / (sum(g) / len(g))))
+        med[arm], mean[arm] = t[len(t) // 2], sum(t) / len(t)
+        print("%-6s %9.3f %9.3f %9.3f %9.3f" % (arm, mean[arm], med[arm], t[0], t[-1]))
+    for x, y in (("table", "gemm"), ("stream", "gemm"), ("stream", "table")):
+        print("# %s / %s (median): %.4f   (mean): %.4f" % (x, y, med[x] / med[y], mean[x] / mean[y]))
 
 
 if __name__ == "__main__":

@@ -59,6 +59,7 @@ SIGNATURES = {
                                 _c_void_p, _c_void_p]),
     "zs_sdf_split_programs": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "zs_sdf_block0_tables": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p]),
+    "zs_sdf_block0_streams": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "zs_sdf_query_points_split": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int,
                                            _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_sdf_query_grid_split": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int, _c_int,
@@ -224,7 +225,7 @@ SIGNATURES = {
     "zs_readout_concat_bwd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
 }
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 _lib = None
 
 

@@ -41,6 +41,7 @@
 //  * The attention map (implicit.py:277) is only produced by the fp32 kernel.
 #include "zs_common.h"
 #include <stdlib.h>
+#include <string.h>
 #include "sdf_layout.h"
 #include "sdf_math.h"
 #include "zs_split16.h"
@@ -236,6 +237,9 @@ struct AStream {
     // Block 0 so consumes program K-blocks 92 h + 48 .. 92 h + 91 for h = 0..7, then 736 on (program.split_consumed_kblocks;
     // tests/test_block0_tables.py replays this schedule wave by wave).
     DEV void skip(int bytes) { gsrc += bytes; }
+    // The NEXT staged chunk comes from `base` (chunk-aligned in its own stream): block 0's compact stream hands over to the
+    // program (BLOCK 0 STREAM below).  Like skip(), only gsrc moves.
+    DEV void seek(const char *base, int wave, int lane) { gsrc = base + wave * (KPW * KB_U4 * 16) + lane * 16; }
     DEV void drain() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 };
 
@@ -498,10 +502,11 @@ DEV void mfma3_cacc(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4
 }
 // one input tile (2 K-blocks) starting at chunk position pos0 (even); side sees K-blocks kb0, kb0 + 1.
 // YACC: acc is a tile of the residual stream (AGPR-resident, see mfma3_cacc)
-template <bool YACC = false, typename SIDE = NoSide>
+// NKB = 1: only the tile's first K-block (registers 0..7 of the input tile)
+template <bool YACC = false, typename SIDE = NoSide, int NKB = 2>
 DEV void gemm_one(AStream &s, const PT &X, f32x16 &acc, int pos0, int kb0 = 0, SIDE side = SIDE()) {
 #pragma unroll
-    for (int j = 0; j < 2; j++) {
+    for (int j = 0; j < NKB; j++) {
         u32x4 ahi, alo;
         s.step((pos0 + j) & (CK - 1), ahi, alo);
         pin(ahi, alo);
@@ -654,6 +659,55 @@ DEV f32x16 block0_qkv(const float *prm, int tile, int hi, float xr, float yr, fl
     }
     return v;
 }
+// BLOCK 0 STREAM.  With the table, q_h = rstd (T_q p~) + c_q is affine in u = (rstd x, rstd y, rstd z, rstd, 1), so the
+// 224 latent logits of a head are S_h = U_h u, U_h = c K_h [T_q,h | c_q,h] (224 x 5; c = 32^-1/2 log2 e folded in: S comes
+// out in the log2 domain), and q, k, v are [T | c] u.  A rank-5 contraction with both operands split is 15 products per
+// output - the K = 16 of ONE MFMA on packed operands (lane l holds k = 8 (l >> 5) + e; xh = fp16(x), xl = fp16(s (x - xh)),
+// xd = fp16(xh / s), s = B0S_LO_SCALE: remainders scaled out of fp16's subnormals, the power of two taken back by the hi
+// copy they meet - zeroshape_amd/program.py has the numbers):
+//     A, 32 rows x 16 (1 KiB)    lanes  0-31: [Uh0 Uh1 Uh2 Uh3 | Ud0 Ud1 Ud2 Ud3]   lanes 32-63: [Ul0 Ul1 Ul2 Ul3 | Uh4 Ud4 Ul4 0]
+//     B, 16 x 32 points           lanes  0-31: [uh0 uh1 uh2 uh3 | ul0 ul1 ul2 ul3]   lanes 32-63: [ud0 ud1 ud2 ud3 | uh4 ul4 ud4 0]
+// B is the same for every operand of a wave tile (rank5_b, once per tile).  block0_stream_kernel writes, per image and in
+// front of every launch, a stream of block 0's own: per head 34 K-block slots in consumption order -
+//     [q|k] [v|U0] V0 V0 [U1|U2] V1 V1 V2 V2 [U3|U4] V3 V3 V4 V4 [U5|U6] V5 V5 V6 proj x 16
+// ([a|b]: packed operand a in the slot's hi half, b in its lo half, one MFMA each; V / proj: copies of the program's
+// K-blocks; latent tile 6 has one V K-block: its second multiplies rows 208-223, all masked) - 97 MFMAs per head instead of
+// 132, 8 x 34 = 272 slots = 34 whole chunks.  A head starts at chunk position 0, 2, 4, 6 in turn (34 = 4 chunks + 2).  Head
+// 7's proj K-blocks are the stream's last two chunks; in front of them every wave's source moves to the program's K-block
+// 736 (AStream::seek), where block 0's MLP section starts.  4,464 slots, 13,352 MFMAs per wave tile; the program itself is
+// untouched (tests/test_block0_stream.py replays the schedule).
+constexpr float B0S_LO_SCALE = 64.0f;             // program.py: B0S_LO_SCALE
+constexpr int B0S_KB_HEAD = 34;
+static_assert(B0_STREAM_KB == HEADS * B0S_KB_HEAD && B0_STREAM_KB % CK == 0 && B0_STREAM_BYTES == (size_t)B0_STREAM_KB * KB_U4 * 16,
+              "the compact stream is whole chunks");
+static_assert(B0S_KB_HEAD == 5 + (2 * LT - 1) + 2 * NT && L - 32 * (LT - 1) <= 16, "latent tile 6: rows 16-31 are padding");
+// x - fp16 half of h: one v_fma_mix_f32, exact (as in zs::s16::split2)
+DEV void rem2(unsigned h, float a, float b, float &ra, float &rb) {
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(ra) : "v"(h), "v"(a));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb) : "v"(h), "v"(b));
+}
+// the B operand of a wave tile's rank-5 MFMAs from u = (u0, u1, u2, u3, 1); bad: a component beyond the fp16 range (or not
+// finite) - the tile is flagged for the fp32 re-evaluation like one outside the envelope (integer test: NaN-proof)
+DEV u32x4 rank5_b(float u0, float u1, float u2, float u3, int hi, bool &bad) {
+    using zs::s16::pk_f16;
+    const unsigned lim = 0x477fe000u;  // 65504.0f
+    bad = (__builtin_bit_cast(unsigned, u0) & 0x7fffffffu) > lim || (__builtin_bit_cast(unsigned, u1) & 0x7fffffffu) > lim ||
+          (__builtin_bit_cast(unsigned, u2) & 0x7fffffffu) > lim || (__builtin_bit_cast(unsigned, u3) & 0x7fffffffu) > lim;
+    const unsigned h01 = pk_f16(u0, u1), h23 = pk_f16(u2, u3);
+    float r0, r1, r2, r3;
+    rem2(h01, u0, u1, r0, r1);
+    rem2(h23, u2, u3, r2, r3);
+    const float s = B0S_LO_SCALE, is = 1.0f / B0S_LO_SCALE;
+    const unsigned l01 = pk_f16(r0 * s, r1 * s), l23 = pk_f16(r2 * s, r3 * s);
+    const unsigned d01 = pk_f16((u0 - r0) * is, (u1 - r1) * is), d23 = pk_f16((u2 - r2) * is, (u3 - r3) * is);   // u - r = uh exactly
+    // u4 = 1: uh4 = 1 (0x3c00), ul4 = 0, ud4 = 2^-6 (0x2400)
+    static_assert(B0S_LO_SCALE == 64.0f, "ud4's bit pattern");
+    return hi ? u32x4{d01, d23, 0x00003c00u, 0x00002400u} : u32x4{h01, h23, l01, l23};
+}
+DEV f32x16 mfma_rank5(const u32x4 &a, const u32x4 &ub) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(zs::s16::as_h(a), zs::s16::as_h(ub), zero16(), 0, 0, 0);
+}
+
 // w.w + w.x*x + w.y*y + w.z*z for the 16 registers of (tile, hi): [tile][hi][r][4] table
 DEV f32x16 xyz_affine(const float *prm, int off, int tile, int hi, float x, float y, float z) {
     const f32x4 *q = reinterpret_cast<const f32x4 *>(prm + off + tile * 128 + hi * 64);
@@ -743,14 +797,13 @@ DEV void load_params(float *prm, const float *prog_params, int start, int count)
     __syncthreads();
 }
 
-// One latent tile of the point->latent attention of one head: S = K_tile q (2 K-blocks), online
+// One latent tile of the point->latent attention of one head (attn_tile): S = K_tile q (2 K-blocks), online
 // softmax update in the log2 domain, o += V_tile^T P (2 K-blocks).  MASK: last tile, rows >= 197
 // are padding.
-template <bool MASK>
-DEV void attn_tile(AStream &s, const PT &q, f32x16 &o, float &m_run, float &z_run, float c, int hi,
-                   int pos0) {
-    f32x16 S = zero16();
-    gemm_one(s, q, S, pos0);
+// softmax_pv is the part behind the logits S (c S is the log2-domain logit), V_tile's K-blocks from chunk position pos0.
+// NKB = 1: the tile's second V K-block is not in the stream (its 16 rows are all masked: P = 0 exactly).
+template <bool MASK, int NKB = 2>
+DEV void softmax_pv(AStream &s, f32x16 &S, f32x16 &o, float &m_run, float &z_run, float c, int hi, int pos0) {
     float mt = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -785,7 +838,14 @@ DEV void attn_tile(AStream &s, const PT &q, f32x16 &o, float &m_run, float &z_ru
         zs_ += p;
     }
     z_run += zs_;
-    gemm_one(s, pack_tile(S), o, pos0 + 2);
+    gemm_one<false, NoSide, NKB>(s, pack_tile(S), o, pos0);
+}
+template <bool MASK>
+DEV void attn_tile(AStream &s, const PT &q, f32x16 &o, float &m_run, float &z_run, float c, int hi,
+                   int pos0) {
+    f32x16 S = zero16();
+    gemm_one(s, q, S, pos0);
+    softmax_pv<MASK>(s, S, o, m_run, z_run, c, hi, pos0 + 2);
 }
 
 #ifdef ZS_EXP_TIMING  // tools/phase_timing_split.py: cycle stamps of (block 0, wave 0, first tile) -> workspace tail
@@ -795,15 +855,16 @@ DEV void attn_tile(AStream &s, const PT &q, f32x16 &o, float &m_run, float &z_ru
 #endif
 // One wave: 32 points (lane & 31; both lane halves carry the same point).
 // tbl: this image's block-0 table (BLOCK 0 TABLE above; wave-uniform), or null: block 0 runs its q/k/v GEMMs like block 1
+// b0s: this image's compact block-0 stream (BLOCK 0 STREAM above; wave-uniform; tbl is null then), or null
 DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage_addr, u32x4 *slab,
-                      const float *tbl, float px, float py, float pz, int wave, int lane, float &guard,
+                      const float *tbl, const char *b0s, float px, float py, float pz, int wave, int lane, float &guard,
                       unsigned long long *dbg) {
     const int hi = lane >> 5;
     const float *prog_params = reinterpret_cast<const float *>(prog) + REC_FLOATS;
     constexpr int QKV_BYTES = 3 * NT * 2 / CK * CHUNK_BYTES;   // q/k/v K-blocks of a head: 6 whole chunks
     static_assert(3 * NT * 2 % CK == 0, "AStream::skip passes whole chunks");
     AStream s;
-    s.init(prog, stage, stage_addr, wave, lane, tbl ? QKV_BYTES : 0);   // head 0's q/k/v are the first six chunks
+    s.init(b0s ? b0s : prog, stage, stage_addr, wave, lane, tbl ? QKV_BYTES : 0);   // table: head 0's q/k/v are the first six chunks
     Slab sl;
     sl.fl = slab;
     ZS_STAMP(0);
@@ -821,8 +882,17 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
 #pragma unroll 1
     for (int blk = 0; blk < BLOCKS; blk++) {
         const bool tab = blk == 0 && tbl != nullptr;   // wave-uniform
+        const bool strm = blk == 0 && b0s != nullptr;  // wave-uniform
         float rstd0 = 0.f, xr = 0.f, yr = 0.f, zr = 0.f;
-        if (tab) {
+        u32x4 ub = {0u, 0u, 0u, 0u};
+        bool u_bad = false;
+        if (strm) {
+            // the block window stays for the whole block; LN1's output is not needed, only rstd: u, split and packed once
+            load_params(prm, prog_params, W_BLK, P_BLK_STRIDE);
+            float mean;
+            ln_stats(y, mean, rstd0);
+            ub = rank5_b(px * rstd0, py * rstd0, pz * rstd0, rstd0, hi, u_bad);
+        } else if (tab) {
             // the table window instead of the block window (which returns behind the heads): LN1's output is not needed
             load_params(prm, tbl, 0, PRM_WINDOW);
             float mean;
@@ -902,11 +972,78 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                 gemm_one(s, op, y[nt], (P + 4 + 2 * nt) & (CK - 1));
             }
         };
+        // one head of block 0 from the compact stream (BLOCK 0 STREAM): 34 slots from chunk position P
+        auto head_b0s = [&](int hd, auto Ptag) {
+            constexpr int P = decltype(Ptag)::value;
+            u32x4 a0, a1;
+            s.step(P & (CK - 1), a0, a1);                       // [q | k]
+            pin(a0, a1);
+            const f32x16 q = mfma_rank5(a0, ub), k = mfma_rank5(a1, ub);
+            s.step((P + 1) & (CK - 1), a0, a1);                 // [v | U0]
+            pin(a0, a1);
+            const f32x16 v = mfma_rank5(a0, ub);
+            f32x16 S = mfma_rank5(a1, ub);
+            float s_self = 0.f, qq = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                s_self = fmaf(q[r], k[r], s_self);
+                qq = fmaf(q[r], q[r], qq);
+            }
+            s_self = half_sum(s_self) * (scale * 1.44269504088896340736f);
+            {
+                const float km = prog_params[P_KMAX + hd] * scale;  // scalar load
+                guard = fmaxf(guard, half_sum(qq) * (km * km));
+            }
+            float m_run = -INFINITY, z_run = 0.f;
+            f32x16 o = zero16();
+            softmax_pv<false>(s, S, o, m_run, z_run, 1.0f, hi, P + 2);
+#pragma unroll
+            for (int i = 0; i < (LT - 1) / 2; i++) {
+                s.step((P + 4 + 5 * i) & (CK - 1), a0, a1);     // [U(2i+1) | U(2i+2)]: the second operand waits in a1
+                pin(a0, a1);
+                S = mfma_rank5(a0, ub);
+                softmax_pv<false>(s, S, o, m_run, z_run, 1.0f, hi, P + 5 + 5 * i);
+                S = mfma_rank5(a1, ub);
+                if (2 * i + 2 < LT - 1)
+                    softmax_pv<false>(s, S, o, m_run, z_run, 1.0f, hi, P + 7 + 5 * i);
+                else
+                    softmax_pv<true, 1>(s, S, o, m_run, z_run, 1.0f, hi, P + 7 + 5 * i);
+            }
+            {
+                const float m_new = fmaxf(m_run, s_self);
+                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+                const float p_self = __builtin_amdgcn_exp2f(s_self - m_new);
+                const float z = fmaf(half_sum(z_run), alpha, p_self);
+                const float inv = 1.0f / z;
+                const float a_i = alpha * inv, p_i = p_self * inv;
+#pragma unroll
+                for (int r = 0; r < 16; r++) o[r] = fmaf(p_i, v[r], o[r] * a_i);
+            }
+            const PT op = pack_tile(o);
+            // head 7's proj K-blocks are the compact stream's last two chunks: their pos-7 steps stage the program's
+            if (P == 6 && hd == HEADS - 1) s.seek(prog + HEADS * (G_HEAD / 2) * (KB_U4 * 16), wave, lane);
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) gemm_one(s, op, y[nt], (P + 18 + 2 * nt) & (CK - 1));
+        };
         static_assert((LT - 1) % 2 == 0 && (3 * NT * 2 + LT * 4 + NT * 2) % CK == 4, "head = 11.5 chunks");
+        static_assert(B0S_KB_HEAD % CK == 2 && HEADS % 4 == 0 && (HEADS * (G_HEAD / 2)) % CK == 0,
+                      "compact heads start at chunk positions 0, 2, 4, 6; the program resumes on a chunk boundary");
+        if (strm) {
 #pragma unroll 1
-        for (int hd = 0; hd < HEADS; hd += 2) {
-            head(hd, std::integral_constant<int, 0>());
-            head(hd + 1, std::integral_constant<int, 4>());
+            for (int hd = 0; hd < HEADS; hd += 4) {
+                head_b0s(hd, std::integral_constant<int, 0>());
+                head_b0s(hd + 1, std::integral_constant<int, 2>());
+                head_b0s(hd + 2, std::integral_constant<int, 4>());
+                head_b0s(hd + 3, std::integral_constant<int, 6>());
+            }
+            // a component of u beyond the fp16 range: the tile goes to the exact kernel (guard = +inf)
+            guard = __builtin_bit_cast(float, u_bad ? 0x7f800000u : __builtin_bit_cast(unsigned, guard));
+        } else {
+#pragma unroll 1
+            for (int hd = 0; hd < HEADS; hd += 2) {
+                head(hd, std::integral_constant<int, 0>());
+                head(hd + 1, std::integral_constant<int, 4>());
+            }
         }
 
         ZS_STAMP(3 + blk * 4);
@@ -1133,7 +1270,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
     float *__restrict__ out, int apply_sigmoid, f32x4 *__restrict__ workspace,
     int *__restrict__ tile_flags,    // [tiles] zeroed by the caller, or null
     int static_order,                // 1: tile += gridDim.x, no counter (ZS_SPLIT_STATIC_TILES=1: the A/B arm of tools/ab_tile_order.py)
-    const float *__restrict__ block0_tables) {   // [batch][PRM_WINDOW] (block0_window_kernel), or null: block 0 runs its q/k/v GEMMs
+    const float *__restrict__ block0_tables,    // [batch][PRM_WINDOW] (block0_window_kernel), or null: block 0 runs its q/k/v GEMMs
+    const char *__restrict__ block0_streams) {  // [batch][B0_STREAM_BYTES] (block0_stream_kernel; the tables are null then), or null
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     float *prm = lds;
     const int lane = threadIdx.x & 63;
@@ -1193,7 +1331,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
 #endif
         float guard = 0.f;
         const float *tbl = block0_tables ? block0_tables + (size_t)img * PRM_WINDOW : nullptr;
-        float logit = decode_tile(prog, prm, stage, stage_addr, fl, tbl, px, py, pz, wave, lane, guard, dbg);
+        const char *b0s = block0_streams ? block0_streams + (size_t)img * B0_STREAM_BYTES : nullptr;
+        float logit = decode_tile(prog, prm, stage, stage_addr, fl, tbl, b0s, px, py, pz, wave, lane, guard, dbg);
         if (apply_sigmoid) logit = 1.0f / (1.0f + expf(-logit));
         // ENVELOPE (zeroshape_amd/program.py, S_GUARD): outside it the tile is flagged for the
         // exact-fp32 kernel, and a program with non-finite / out-of-range operands yields NaN like
@@ -1401,23 +1540,110 @@ __global__ __launch_bounds__(B0_THREADS) void block0_window_kernel(const char *_
     if (tile < C / 32 && t < 32) out[B0_BPROJ + tile * 32 + t] = par[P_BLK0 + PB_BPROJ + tile * 32 + t];
 }
 
+// BLOCK 0 STREAM of every image, from its split program and its table (block0_window_kernel, earlier on the stream): one
+// workgroup per (image, head).  The rows of the ten rank-5 operands meet in LDS in A-row order: q, k, v = [T | c] of the
+// table; U_lt = c K_lt [T_q | c_q] summed in double over the head's 32 features in order, from hi + lo of the K records,
+// rounded once to float.  Then the 10 packed half-slots and the 29 copied K-blocks go to their slots (host mirror:
+// program.block0_stream).
+DEV unsigned short f16_bits(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
+DEV float f16_val(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
+constexpr int B0S_OPERANDS = 3 + LT;
+__global__ __launch_bounds__(B0_THREADS) void block0_stream_kernel(const char *__restrict__ programs, size_t program_stride_bytes,
+                                                                   const float *__restrict__ tables, char *__restrict__ streams) {
+    __shared__ float rows[B0S_OPERANDS][32][5];
+    const int head = blockIdx.x, img = blockIdx.y, t = threadIdx.x;
+    const char *prog = programs + (size_t)img * program_stride_bytes;
+    const float *tbl = tables + (size_t)img * PRM_WINDOW;
+    u32x4 *out = reinterpret_cast<u32x4 *>(streams + (size_t)img * B0_STREAM_BYTES) + (size_t)head * B0S_KB_HEAD * KB_U4;
+    constexpr int KB_HEAD = G_HEAD / 2, KB_QKV = G_QKV_HEAD / 2;
+    if (t < 96) {
+        // row `row` of the tile sits at (hh, r) of the row-param order, row(r, hh) = row
+        const int part = t >> 5, row = t & 31, hh = (row >> 2) & 1, r = (row & 3) + 4 * (row >> 3);
+        const int o = (head * 3 + part) * 32 + hh * 16 + r;
+#pragma unroll
+        for (int d = 0; d < 4; d++) rows[part][row][d] = tbl[B0_T + o * 4 + d];
+        rows[part][row][4] = tbl[B0_C + o];
+    }
+    __syncthreads();
+    if (t < LT * 32) {
+        const int lt = t >> 5, row = t & 31;
+        double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int f = 0; f < HD; f++) {
+            const int hh = (f >> 2) & 1, r = (f & 3) + 4 * (f >> 3), j = r >> 3, e = r & 7;
+            const unsigned short *rec = reinterpret_cast<const unsigned short *>(
+                prog + (size_t)(head * KB_HEAD + KB_QKV + 4 * lt + j) * (KB_U4 * 16) + (row + 32 * hh) * 16);
+            const double kv = (double)f16_val(rec[e]) + (double)f16_val(rec[512 + e]);     // lo half: 1 KiB further on
+#pragma unroll
+            for (int d = 0; d < 5; d++) acc[d] += kv * (double)rows[0][f][d];
+        }
+        const double c = 0.17677669529663688110 * 1.44269504088896340736;   // 32^-1/2 log2 e
+#pragma unroll
+        for (int d = 0; d < 5; d++) rows[3 + lt][row][d] = (float)(acc[d] * c);
+    }
+    __syncthreads();
+    for (int i = t; i < B0S_OPERANDS * 64; i += B0_THREADS) {
+        const int op = i >> 6, lane = i & 63, row = lane & 31, pair = op >> 1;
+        unsigned short h[5], d[5], l[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const float x = rows[op][row][k];
+            h[k] = f16_bits(x);
+            const float hf = f16_val(h[k]);
+            l[k] = f16_bits((x - hf) * B0S_LO_SCALE);
+            d[k] = f16_bits(hf * (1.0f / B0S_LO_SCALE));
+        }
+        auto pk = [](unsigned short a, unsigned short b) { return (unsigned)a | ((unsigned)b << 16); };
+        const u32x4 w = lane < 32 ? u32x4{pk(h[0], h[1]), pk(h[2], h[3]), pk(d[0], d[1]), pk(d[2], d[3])}
+                                  : u32x4{pk(l[0], l[1]), pk(l[2], l[3]), pk(h[4], d[4]), pk(l[4], 0)};
+        const int slot = pair < 2 ? pair : 5 * pair - 6;         // [q|k] 0, [v|U0] 1, [U1|U2] 4, [U3|U4] 9, [U5|U6] 14
+        out[slot * KB_U4 + (op & 1) * 64 + lane] = w;
+    }
+    constexpr int NV = 2 * LT - 1, NCOPY = NV + 2 * NT;          // 13 V K-blocks, 16 proj K-blocks
+    for (int i = t; i < NCOPY * KB_U4; i += B0_THREADS) {
+        const int cb = i / KB_U4, w = i - cb * KB_U4;
+        int src, dst;
+        if (cb < NV) {
+            const int lt = cb >> 1, j = cb & 1;
+            src = KB_QKV + 4 * lt + 2 + j;
+            dst = lt == 0 ? 2 + j : 4 + 5 * ((lt - 1) >> 1) + 1 + 2 * ((lt - 1) & 1) + j;
+        } else {
+            src = KB_HEAD - 2 * NT + (cb - NV);
+            dst = B0S_KB_HEAD - 2 * NT + (cb - NV);
+        }
+        out[dst * KB_U4 + w] = reinterpret_cast<const u32x4 *>(prog)[(size_t)(head * KB_HEAD + src) * KB_U4 + w];
+    }
+}
+
 // in front of every split launch: the block-0 tables of the launch's images -> the head of `workspace`, img * 16 KiB.  That
 // region (96 MiB) is the exact-fp32 kernel's per-wave slabs, which the split kernel never touches; the fp32 re-evaluation
 // that may follow on the stream overwrites it, and the next split launch writes it again.  The tables depend on the weights
 // only and could be computed once per weight version, but the program's bytes are pinned (tests compare them with the host
 // mirror word for word) and the entry points keep their signatures, so there is nowhere to keep them: 24 small workgroups per image
 // per launch (microseconds) against ~8 % of the decode launch.  A plain kernel launch: capturable.
-// -> the kernel's block0_tables argument; null (block 0 runs its q/k/v GEMMs) when the tables do not fit the slab region or
-// ZS_SPLIT_BLOCK0_GEMM=1 (read per launch: the A/B arm of tools/ab_block0_tables.py)
-const float *launch_block0_tables(const void *split_programs, size_t program_stride_bytes, int batch, void *workspace,
-                                  hipStream_t st) {
+// Behind the tables of all images, while both fit (block0_stream_fit: 175 images), the compact block-0 streams, 544 KiB per
+// image from 8 more small workgroups: the default arm.  The arms, read per launch (tools/ab_block0_tables.py alternates them):
+//   ZS_SPLIT_BLOCK0_GEMM=1            block 0 runs its q/k/v GEMMs (also: the tables do not fit)            -> {null, null}
+//   ZS_SPLIT_BLOCK0_STREAM=program    q/k/v from the table, the weight stream is the program's (AStream::skip; also: the
+//                                     streams do not fit): the arm program.split_consumed_kblocks describes  -> {tables, null}
+//   default                           block 0 from its compact stream                                        -> {null, streams}
+struct Block0Arm {
+    const float *tables;
+    const char *streams;
+};
+Block0Arm launch_block0_arm(const void *split_programs, size_t program_stride_bytes, int batch, void *workspace,
+                            hipStream_t st) {
     const char *e = getenv("ZS_SPLIT_BLOCK0_GEMM");
-    if (e && atoi(e) != 0) return nullptr;
-    if (!block0_tables_fit(batch)) return nullptr;
+    if (e && atoi(e) != 0) return {nullptr, nullptr};
+    if (!block0_tables_fit(batch)) return {nullptr, nullptr};
     float *tables = static_cast<float *>(workspace);
     hipLaunchKernelGGL(block0_window_kernel, dim3(HEADS * 3, batch), dim3(B0_THREADS), 0, st,
                        static_cast<const char *>(split_programs), program_stride_bytes, tables);
-    return tables;
+    const char *a = getenv("ZS_SPLIT_BLOCK0_STREAM");
+    if ((a && strcmp(a, "program") == 0) || !block0_stream_fit(batch)) return {tables, nullptr};
+    char *streams = block0_streams(workspace, batch);
+    hipLaunchKernelGGL(block0_stream_kernel, dim3(HEADS, batch), dim3(B0_THREADS), 0, st,
+                       static_cast<const char *>(split_programs), program_stride_bytes, tables, streams);
+    return {nullptr, streams};
 }
 
 // in front of every split launch: the dynamic tile order's counter (in the workspace tail) starts at zero whatever
@@ -1435,12 +1661,12 @@ int launch_decode_split(const char *who, const void *split_programs, size_t prog
     if (q.m == 0) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int static_order = launch_counter_reset(workspace, st);
-    const float *b0_tables = launch_block0_tables(split_programs, program_stride_bytes, batch, workspace, st);
+    const Block0Arm b0 = launch_block0_arm(split_programs, program_stride_bytes, batch, workspace, st);
     hipLaunchKernelGGL(q.points ? sdf_decode_split_kernel<false> : sdf_decode_split_kernel<true>,
                        dim3(decode_grid_size(batch, q.m)), dim3(WAVES * 64), 0, st,
                        static_cast<const char *>(split_programs), program_stride_bytes, batch, q.points, q.axis, q.G,
                        q.first_point, q.m, out, q.apply_sigmoid, static_cast<f32x4 *>(workspace), tile_flags, static_order,
-                       b0_tables);
+                       b0.tables, b0.streams);
     return zs::check_launch(who) ? 1 : 0;
 }
 
@@ -1488,6 +1714,23 @@ extern "C" int zs_sdf_block0_tables(const void *split_programs, size_t program_s
     hipLaunchKernelGGL(block0_window_kernel, dim3(HEADS * 3, batch), dim3(B0_THREADS), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char *>(split_programs), program_stride_bytes, tables);
     return zs::check_launch("zs_sdf_block0_tables") ? 1 : 0;
+}
+
+extern "C" int zs_sdf_block0_streams(const void *split_programs, size_t program_stride_bytes, int batch, const float *tables,
+                                     void *streams, void *stream) {
+    if (batch < 0 || batch > 65535) {
+        zs::set_err("zs_sdf_block0_streams: bad batch %d", batch);
+        return 0;
+    }
+    if (batch == 0) return 1;
+    if (!tables || !streams) {
+        zs::set_err("zs_sdf_block0_streams: null pointer");
+        return 0;
+    }
+    if (!check_programs("zs_sdf_block0_streams", split_programs, program_stride_bytes)) return 0;
+    hipLaunchKernelGGL(block0_stream_kernel, dim3(HEADS, batch), dim3(B0_THREADS), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const char *>(split_programs), program_stride_bytes, tables, static_cast<char *>(streams));
+    return zs::check_launch("zs_sdf_block0_streams") ? 1 : 0;
 }
 
 extern "C" int zs_sdf_query_points_split(const void *split_programs, size_t program_stride_bytes,

@@ -24,7 +24,8 @@ inline int decode_grid_size(int batch, int m) {
 // ---- workspace (zs_sdf_workspace_bytes) ------------------------------------------------------------------------- //
 // [slab region: MAX_WGS x WAVES x ZSLAB_F4 float4, 96 MiB][tail: 4 KiB]
 //  * slab region: the fp32 kernel's per-wave slabs.  The split kernel never touches them; its launches keep the block-0
-//    tables of their images at the head of the region, B0_TABLE_FLOATS per image.
+//    tables of their images at the head of the region, B0_TABLE_FLOATS per image, and behind the tables of all `batch`
+//    images their compact block-0 streams, B0_STREAM_BYTES per image.
 //  * tail + 0: timing stamps (ZS_EXP_TIMING builds); tail + 1 KiB: the split kernel's tile counter, then 16 ints further
 //    one slot per workgroup.
 //  * the fp32 kernel's attention dump (zs_sdf_attn_scratch_bytes) lies behind WORKSPACE_BYTES.
@@ -41,7 +42,16 @@ __host__ __device__ inline unsigned long long *timing_stamps(void *workspace) {
 __host__ __device__ inline int *tile_counter(void *workspace) {
     return reinterpret_cast<int *>(workspace_tail(workspace) + TAIL_TILE_COUNTER);
 }
+constexpr int B0_STREAM_KB = 8 * 34;                        // K-block slots of a compact block-0 stream: 34 per head
+constexpr size_t B0_STREAM_BYTES = (size_t)B0_STREAM_KB * 2048;   // 544 KiB = 34 whole chunks
 inline bool block0_tables_fit(int batch) { return (size_t)batch * B0_TABLE_FLOATS * sizeof(float) <= SLAB_REGION_BYTES; }
+// tables AND streams (175 images); beyond it a launch runs block 0 from the tables alone, beyond block0_tables_fit its GEMMs
+inline bool block0_stream_fit(int batch) {
+    return (size_t)batch * (B0_TABLE_FLOATS * sizeof(float) + B0_STREAM_BYTES) <= SLAB_REGION_BYTES;
+}
+inline char *block0_streams(void *workspace, int batch) {
+    return static_cast<char *>(workspace) + (size_t)batch * B0_TABLE_FLOATS * sizeof(float);
+}
 
 // ---- a query: what one decode launch evaluates per image --------------------------------------------------------- //
 struct Query {

@@ -559,3 +559,129 @@ def split_consumed_kblocks():
     each of block 0's eight heads - head h keeps 92 h + 48 .. 92 h + 91, the MLP section follows from 736 on (4,544 in all)."""
     keep = [kb for kb in range(KB_TOTAL) if not (kb < HEADS * KB_HEAD and kb % KB_HEAD < KB_QKV_HEAD)]
     return np.array(keep)
+
+
+# ----------------------------------------------------------------------------- #
+# block 0 from a compact stream of its own (csrc/sdf_decoder_split.hip: block0_stream_kernel, BLOCK 0 STREAM)
+# ----------------------------------------------------------------------------- #
+# With the table, q_h = rstd (T_q p~) + c_q is affine in u = (rstd x, rstd y, rstd z, rstd, 1), so the 224 latent logits of a
+# head are S_h = U_h u with U_h = c K_h [T_q,h | c_q,h] (224 x 5; K_h the image's K rows, c = 32^-1/2 log2 e folded in), and
+# q, k, v themselves are [T | c] u.  A rank-5 contraction with both operands split needs 15 products per output
+# (U_hi u_hi + U_hi u_lo + U_lo u_hi): the K = 16 of ONE v_mfma_f32_32x32x16_f16.  Lane l of an operand holds k = 8 (l >> 5) + e:
+#     A (32 rows x 16, one 1 KiB half of a K-block slot)   lanes  0-31: [Uh0 Uh1 Uh2 Uh3 | Ud0 Ud1 Ud2 Ud3]
+#                                                            lanes 32-63: [Ul0 Ul1 Ul2 Ul3 | Uh4 Ud4 Ul4 0]
+#     B (16 x 32 points, the same for every A of a tile)     lanes  0-31: [uh0 uh1 uh2 uh3 | ul0 ul1 ul2 ul3]
+#                                                            lanes 32-63: [ud0 ud1 ud2 ud3 | uh4 ul4 ud4 0]
+# with xh = fp16(x), xl = fp16(s (x - xh)), xd = fp16(xh / s), s = B0S_LO_SCALE: the remainders of values of order 0.1 .. 1 are
+# of order 1e-5 .. 1e-4, where fp16 is subnormal (spacing 6e-8, an ABSOLUTE error that the other operand multiplies by up to
+# ~10); scaled by s = 64 before the rounding they keep their 11 bits, and the power of two is taken back exactly by the hi
+# copy that meets them (xd is inexact only where xh / s is itself subnormal - an error the small remainder multiplies).
+# Block 0 then needs, per head, 10 packed operands (q, k, v, U_0..U_6) = 5 K-block slots [a | b] (a in the hi half, b in the
+# lo half), the 13 V K-blocks whose probabilities can be non-zero (the second K-block of latent tile 6 multiplies rows
+# 208-223, which are masked) and the 16 proj K-blocks: 34 slots, 97 MFMAs.  They are written per image in consumption order
+# into a stream of 8 x 34 = 272 slots = 34 whole chunks; behind it the kernel continues in the program at K-block 736.
+B0S_KB_HEAD = 34
+B0S_KB = HEADS * B0S_KB_HEAD                     # 272 K-block slots
+B0S_WORDS = B0S_KB * KB_WORDS                    # 544 KiB per image
+B0S_OPERANDS = 3 + LT                            # q, k, v, U_0 .. U_6
+SPLIT_MFMAS_B0_STREAM = HEADS * (B0S_OPERANDS + 3 * (2 * LT - 1 + 2 * NT)) + 3 * (KB_TOTAL - HEADS * KB_HEAD)   # 13,352
+SLAB_REGION_BYTES = 256 * 4 * (3 * NT * 4 * 64) * 16   # csrc/sdf_query.h: the workspace's slab region (96 MiB)
+LOG2E = 1.44269504088896340736
+B0S_LO_SCALE = 64.0
+
+
+def block0_stream_slots():
+    """The 34 slots of one head in consumption order: ("pack", a, b) = packed operands a | b (0 q, 1 k, 2 v, 3 + lt: U_lt),
+    ("copy", kb) = K-block kb of the head's 92 in the split program (V of latent tile lt: 48 + 4 lt + 2 + j; proj: 76 + i)."""
+    v = lambda lt, n=2: [("copy", KB_QKV_HEAD + 4 * lt + 2 + j) for j in range(n)]
+    slots = [("pack", 0, 1), ("pack", 2, 3)] + v(0)
+    for lt in (1, 3, 5):
+        slots += [("pack", 3 + lt, 4 + lt)] + v(lt) + v(lt + 1, 2 if lt + 1 < LT - 1 else 1)
+    slots += [("copy", KB_HEAD - 2 * NT + i) for i in range(2 * NT)]
+    assert len(slots) == B0S_KB_HEAD
+    return slots
+
+
+def block0_stream_fit(batch):
+    """Do the tables AND the compact streams of `batch` images fit the head of the workspace (csrc/sdf_query.h)?  Beyond it a
+    launch takes the table arm (block0_window alone), beyond that the GEMMs."""
+    return batch * (B0_WINDOW_FLOATS * 4 + B0S_WORDS * 4) <= SLAB_REGION_BYTES
+
+
+def block0_rank5_rows(split_prog, window=None):
+    """[HEADS][10][32][5] float32: the rows (in A-row order: feature of the head / latent of the tile) of the ten rank-5
+    operands of every head.  q, k, v: [T | c] straight from the table window; U_lt = c K_lt [T_q | c_q], summed in float64
+    over the head's 32 features in order, from hi + lo of the split program's K records, rounded once to float32."""
+    words = np.ascontiguousarray(split_prog).view(np.uint32)
+    window = block0_window(words) if window is None else np.asarray(window, np.float32)
+    out = np.zeros((HEADS, B0S_OPERANDS, 32, 5), np.float32)
+    inv = np.empty(32, np.int64)
+    inv[ROW_TABLE.reshape(-1)] = np.arange(32)                  # feature t sits at row-param position inv[t] = hh * 16 + r
+    for h in range(HEADS):
+        for part in range(3):
+            tile = 3 * h + part
+            out[h, part, :, :4] = window[B0_T + tile * 128:B0_T + (tile + 1) * 128].reshape(32, 4)[inv]
+            out[h, part, :, 4] = window[B0_C + tile * 32:B0_C + (tile + 1) * 32][inv]
+        uq = out[h, 0].astype(np.float64)                       # [32 features][5]
+        for lt in range(LT):
+            K = np.zeros((32, HD), np.float64)
+            for j in range(2):
+                v = _kblock_values(words, h * KB_HEAD + KB_QKV_HEAD + 4 * lt + j)     # [lane][e]: K[row][row(8 j + e, hi)]
+                K[LANE_I[:, None], ROW_TABLE[LANE_HI][:, 8 * j:8 * j + 8]] = v
+            acc = np.zeros((32, 5), np.float64)
+            for f in range(HD):
+                acc += K[:, f:f + 1] * uq[f][None, :]
+            out[h, 3 + lt] = (acc * (HD ** -0.5 * LOG2E)).astype(np.float32)
+    return out
+
+
+def _split_scaled(x):
+    """x float32 -> fp16 bit patterns of (hi, hi / s, s lo): hi = fp16(x), lo = x - hi scaled by s = B0S_LO_SCALE BEFORE it is
+    rounded to fp16 (so that it stays out of fp16's subnormals), and the copy of hi that meets a scaled lo divided by s."""
+    x = np.ascontiguousarray(x, np.float32)
+    hb, hf = f16_round(x)
+    with np.errstate(invalid="ignore"):
+        lb, _ = f16_round((x - hf) * np.float32(B0S_LO_SCALE))
+    db, _ = f16_round(hf * np.float32(1.0 / B0S_LO_SCALE))
+    return hb, db, lb
+
+
+def pack_rank5_a(rows):
+    """[32][5] float32 -> the A operand [64 lanes][8] as fp16 bit patterns (uint16), layout above."""
+    h, d, l = _split_scaled(rows)
+    z = np.zeros(32, np.uint16)
+    lo_lanes = np.stack([h[:, 0], h[:, 1], h[:, 2], h[:, 3], d[:, 0], d[:, 1], d[:, 2], d[:, 3]], axis=1)
+    hi_lanes = np.stack([l[:, 0], l[:, 1], l[:, 2], l[:, 3], h[:, 4], d[:, 4], l[:, 4], z], axis=1)
+    return np.concatenate([lo_lanes, hi_lanes], axis=0)
+
+
+def pack_rank5_b(u):
+    """u [32 points][5] float32 -> the B operand [64 lanes][8] as fp16 bit patterns (uint16), layout above."""
+    h, d, l = _split_scaled(u)
+    z = np.zeros(h.shape[0], np.uint16)
+    lo_lanes = np.stack([h[:, 0], h[:, 1], h[:, 2], h[:, 3], l[:, 0], l[:, 1], l[:, 2], l[:, 3]], axis=1)
+    hi_lanes = np.stack([d[:, 0], d[:, 1], d[:, 2], d[:, 3], h[:, 4], l[:, 4], d[:, 4], z], axis=1)
+    return np.concatenate([lo_lanes, hi_lanes], axis=0)
+
+
+def block0_stream(split_prog, window=None):
+    """The compact block-0 stream of one SPLIT program as uint32 words [B0S_WORDS] - host mirror of zs_sdf_block0_streams."""
+    words = np.ascontiguousarray(split_prog).view(np.uint32)
+    rows = block0_rank5_rows(words, window)
+    out = np.zeros((B0S_KB, KB_WORDS), np.uint32)
+    for h in range(HEADS):
+        for i, slot in enumerate(block0_stream_slots()):
+            dst = out[h * B0S_KB_HEAD + i]
+            if slot[0] == "copy":
+                kb = h * KB_HEAD + slot[1]
+                dst[:] = words[kb * KB_WORDS:(kb + 1) * KB_WORDS]
+            else:
+                for half, op in enumerate(slot[1:]):
+                    dst[half * 256:(half + 1) * 256] = np.ascontiguousarray(pack_rank5_a(rows[h, op])).reshape(-1).view(np.uint32)
+    return out.reshape(-1)
+
+
+def split_consumed_slots_b0_stream():
+    """What the weight stream delivers when block 0 runs from its compact stream: ("b0", i) for i = 0..271, then ("prog", kb)
+    for the split program's K-blocks 736 on - 4,464 slots per wave tile."""
+    return [("b0", i) for i in range(B0S_KB)] + [("prog", kb) for kb in range(HEADS * KB_HEAD, KB_TOTAL)]
