@@ -239,11 +239,10 @@ int zs_sdf_query_grid_split(const void *split_programs, size_t program_stride_by
 
 /* Block 0's point-side q/k/v as a rank-4 table (ABI 41).  Block 0's point row is point_proj(xyz), affine in (x, y, z, 1), so
  * after LN1 all 768 q/k/v rows are rstd * (T (x, y, z, 1)) + c with T [768][4] and c [768] functions of the weights alone.
- * Every split launch writes the tables of its images to the head of `workspace` (16 KiB per image, inside the region of the
- * exact-fp32 kernel's slabs) with one small kernel in front of the decode kernel, which then evaluates block 0's q/k/v from
- * them and steps over the 8 x 48 q/k/v K-blocks of block 0 in the weight stream (384 of 4,928 per wave tile).
- * ZS_SPLIT_BLOCK0_GEMM=1 in the environment (read per launch), or a batch whose tables exceed that region (> 6,144
- * images), selects the GEMM path for block 0 as well.
+ * A split launch of up to 175 images writes the tables of its images to the head of `workspace` (16 KiB per image, inside
+ * the region of the exact-fp32 kernel's slabs) with one small kernel in front of the decode kernel; the compact streams
+ * below are built from them.  The decode kernel itself no longer reads a table (it once evaluated block 0's q/k/v from it
+ * and stepped over their K-blocks in the weight stream).
  *   zs_sdf_block0_tables      that kernel alone: tables[batch][4096] floats = [b_proj 256][c 768][T 3,072] of each split
  *                             program, in the kernel's register order (zeroshape_amd/program.py: block0_window) */
 int zs_sdf_block0_tables(const void *split_programs, size_t program_stride_bytes, int batch, float *tables, void *stream);
@@ -253,8 +252,10 @@ int zs_sdf_block0_tables(const void *split_programs, size_t program_stride_bytes
  * instead of K-blocks of three.  While tables and streams fit the head of `workspace` (175 images per launch) every split
  * launch also writes, behind the tables, 544 KiB per image: block 0's 8 x 34 K-block slots in consumption order (packed
  * operands, and copies of the program's V and proj K-blocks), and the decode kernel streams block 0 from there before it
- * continues in the program at K-block 736 (4,464 slots and 13,352 MFMAs per wave tile instead of 4,544 and 13,632).
- * ZS_SPLIT_BLOCK0_STREAM=program in the environment (read per launch), or a larger batch, selects the table path above.
+ * continues in the program at K-block 736 (4,464 slots and 13,352 MFMAs per wave tile instead of 4,928 and 14,784).
+ * ZS_SPLIT_BLOCK0_GEMM=1 in the environment (read per launch), or more than 175 images per launch, selects the GEMM path:
+ * block 0 runs its q/k/v GEMMs from the program like block 1, and neither tables nor streams are written.  (Launches of
+ * 176 to 6,144 images used to evaluate q/k/v from the tables alone; they now take this fallback, which is <= 8e-7 from it.)
  *   zs_sdf_block0_streams     that kernel alone: streams[batch][557,056] bytes from the split programs and their tables
  *                             (zs_sdf_block0_tables; zeroshape_amd/program.py: block0_stream) */
 int zs_sdf_block0_streams(const void *split_programs, size_t program_stride_bytes, int batch, const float *tables,

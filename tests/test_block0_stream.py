@@ -233,8 +233,7 @@ def test_schedule_model_consumes_compact_stream_then_program():
     assert len(want) == 4464 and want[:272] == [("b0", i) for i in range(272)]
     assert want[272:] == [("prog", kb) for kb in range(736, 4928)]
     assert got == want
-    # the program K-blocks behind block 0's heads are the table arm's too (split_consumed_kblocks from 736 on)
-    assert [kb for _, kb in want[272:]] == [kb for kb in P.split_consumed_kblocks() if kb >= 736]
+    assert [kb for _, kb in want[272:]] == list(range(736, P.KB_TOTAL))
     assert P.SPLIT_MFMAS_B0_STREAM == 13352 == 8 * 97 + 3 * (4928 - 736)
 
 

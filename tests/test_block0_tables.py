@@ -1,9 +1,10 @@
-"""Block 0's point-side q/k/v as a rank-4 table (zeroshape_amd/program.py: block0_window, split_consumed_kblocks;
-csrc/sdf_decoder_split.hip: BLOCK 0 TABLE, AStream::skip) - the parts that need no GPU.
+"""Block 0's point-side q/k/v as a rank-4 table (zeroshape_amd/program.py: block0_window; csrc/sdf_decoder_split.hip:
+BLOCK 0 TABLE, which the compact block-0 stream is built from) - the parts that need no GPU.
 
-  * the identity: the table, evaluated in fp32 the way the kernel does, gives LN1 + qkv Linear of point_proj(xyz);
-  * the weight stream's schedule: a wave-by-wave model of the staging (per-wave source pointer, the pos-7 step staging
-    chunk n + 2, the bumps where AStream::skip's comment puts them) consumes exactly split_consumed_kblocks()."""
+  * the identity: the table, evaluated in fp32 with five fmas per value, gives LN1 + qkv Linear of point_proj(xyz);
+  * the weight stream's schedule when every block runs its q/k/v GEMMs (block 1 always, block 0 as the fallback): a
+    wave-by-wave model of the staging (per-wave source pointer, the pos-7 step staging chunk n + 2) consumes the program's
+    K-blocks in order."""
 import numpy as np
 import pytest
 
@@ -20,11 +21,11 @@ def _points():
 
 
 def _kernel_qkv(window, sd, pts):
-    """q/k/v rows [n, 768] (attn.qkv.weight row order) from the window, op for op as the split kernel evaluates them:
-    fp32 point_proj (xyz_affine), fp32 ln_stats, five fmas per value (block0_qkv).  float64 products of float32 operands
-    rounded to float32 ARE the fused multiply-adds for these magnitudes (the 24 x 24-bit product is exact in 53 bits;
-    the one rounding of the sum to float32 after an exact-product double add differs from fmaf only by double rounding, far
-    below the tolerance)."""
+    """q/k/v rows [n, 768] (attn.qkv.weight row order) from the window, in the split kernel's fp32: point_proj op for op
+    (xyz_affine), ln_stats op for op, then five fmas per value - the fp32 evaluation of rstd (T p~) + c.  float64 products
+    of float32 operands rounded to float32 ARE the fused multiply-adds for these magnitudes (the 24 x 24-bit product is
+    exact in 53 bits; the one rounding of the sum to float32 after an exact-product double add differs from fmaf only by
+    double rounding, far below the tolerance)."""
     def fma(a, b, c):
         return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
     Wp = sd["point_proj.proj.weight"].astype(F)
@@ -113,26 +114,12 @@ def test_table_reproduces_ln1_and_qkv(seeded_sd, gain):
     assert float(e_tab.max()) <= float(e_gemm.max()) and float(e_tab.mean()) <= float(e_gemm.mean())
 
 
-def test_consumption_list():
-    got = P.split_consumed_kblocks()
-    want = []
-    for h in range(8):
-        want += list(range(92 * h + 48, 92 * h + 92))
-    want += list(range(736, 4928))
-    assert len(want) == 4544 and list(got) == want
-    # every K-block left out is a q/k/v K-block of block 0 in the program's own order: the program keeps all of them
-    left = sorted(set(range(P.KB_TOTAL)) - set(want))
-    assert len(left) == 384 and all(kb % 92 < 48 and kb < 736 for kb in left)
-    assert np.array_equal(P.split_source_kblocks(P.KB_TOTAL)[left], left)
-
-
-def _stream_model(table):
+def _stream_model():
     """The K-blocks the four waves multiply, in order, from a model of AStream: two buffers of one chunk (8 K-blocks), wave w
     stages K-blocks 2 w, 2 w + 1 of a chunk from ITS pointer gsrc[w]; init stages two chunks; the step at chunk position 7
     stages the chunk after next into the buffer just consumed.  All sizes in K-blocks."""
-    CK, QKV = 8, 48
-    start = QKV if table else 0
-    gsrc = [start + 2 * w for w in range(4)]
+    CK = 8
+    gsrc = [2 * w for w in range(4)]
     bufs = [[None] * CK, [None] * CK]
 
     def stage(buf):
@@ -151,28 +138,17 @@ def _stream_model(table):
             bufs[0], bufs[1] = bufs[1], bufs[0]
         pos[0] = (pos[0] + 1) % CK
 
-    def skip(w):
-        gsrc[w] += QKV
     for blk in range(P.BLOCKS):
-        tab = table and blk == 0
         for hd in range(P.HEADS):
             Ppos = 0 if hd % 2 == 0 else 4
-            if not tab:
-                for _ in range(3):
-                    for kb in range(16):
-                        step((Ppos + kb) % CK)
+            for _ in range(3):
+                for kb in range(16):
+                    step((Ppos + kb) % CK)
             for lt in range(P.LT):                        # attn_tile: S at pos0, o at pos0 + 2; tiles alternate P, P + 4
                 p0 = Ppos if lt % 2 == 0 else (Ppos + 4) % CK
                 for j in range(4):
                     step((p0 + j) % CK)
-            bump = tab and hd + 1 < P.HEADS
-            for w in range(4):
-                if bump and (Ppos == 4 or w >= 2):
-                    skip(w)
             for nt in range(P.NT):
-                if Ppos == 0 and nt == 2 and bump:
-                    skip(0)
-                    skip(1)
                 for j in range(2):
                     step((Ppos + 4 + 2 * nt + j) % CK)
         for _ in range(P.HT * 32):                        # the MLP section: chunk-aligned, sequential
@@ -185,6 +161,5 @@ def _stream_model(table):
 
 
 def test_schedule_model_consumes_the_list():
-    assert _stream_model(False) == list(range(P.KB_TOTAL))
-    assert _stream_model(True) == list(P.split_consumed_kblocks())
+    assert _stream_model() == list(range(P.KB_TOTAL))
 

@@ -1,7 +1,7 @@
 """Block 0 from its compact stream on the GPU (csrc/sdf_decoder_split.hip: BLOCK 0 STREAM): the stream kernel against its
-host mirror, and the split decoder's three block-0 arms - compact stream (default), table with the program's stream
-(ZS_SPLIT_BLOCK0_STREAM=program), GEMMs (ZS_SPLIT_BLOCK0_GEMM=1), all read per launch - against the exact-fp32 kernel and
-against each other, at the bars of tests/test_gpu_block0_tables.py."""
+host mirror, and the split decoder's two block-0 arms - compact stream (default) and GEMMs (ZS_SPLIT_BLOCK0_GEMM=1, read per
+launch, and every launch of more than 175 images) - against the exact-fp32 kernel and against each other, at the bars of
+tests/test_gpu_block0_tables.py."""
 import numpy as np
 import pytest
 import torch
@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 ATOL = 1.5e-5   # tests/test_gpu_block0_tables.py, tests/test_gpu_decoder_split.py: split arithmetic vs the exact-fp32 kernel
 BAND = 1e-5     # |logit| below which an occupancy flip is inside the arithmetic's error
-ARMS = (("stream", {}), ("program", {"ZS_SPLIT_BLOCK0_STREAM": "program"}), ("gemm", {"ZS_SPLIT_BLOCK0_GEMM": "1"}))
+ARMS = (("stream", {}), ("gemm", {"ZS_SPLIT_BLOCK0_GEMM": "1"}))
 
 
 def _net(sd):
@@ -26,8 +26,7 @@ def _net(sd):
 
 
 def _arm(monkeypatch, env):
-    for k in ("ZS_SPLIT_BLOCK0_GEMM", "ZS_SPLIT_BLOCK0_STREAM"):
-        monkeypatch.delenv(k, raising=False)
+    monkeypatch.delenv("ZS_SPLIT_BLOCK0_GEMM", raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
 
@@ -94,7 +93,7 @@ def test_stream_kernel_matches_the_mirror(ctx):
 
 
 @pytest.mark.parametrize("m", [1, 33, 128, 129, 300])
-def test_point_lists_three_arms_vs_fp32_kernel(ctx, monkeypatch, m):
+def test_point_lists_both_arms_vs_fp32_kernel(ctx, monkeypatch, m):
     net = ctx["net"]
     pts = torch.from_numpy(syn.seeded_cloud(200 + m, 2, m, -1.5, 1.5)).cuda()
     exact = net.query_points(ctx["exact"], pts)
@@ -104,15 +103,15 @@ def test_point_lists_three_arms_vs_fp32_kernel(ctx, monkeypatch, m):
         got[name] = net.query_points(ctx["split"], pts)
         assert got[name].shape == (2, m) and int(net.last_tile_flags.sum()) == 0
     err = {name: float((got[name] - exact).abs().max()) for name in got}
-    d = {a + "-" + b: float((got[a] - got[b]).abs().max()) for a, b in (("stream", "program"), ("stream", "gemm"), ("program", "gemm"))}
-    print("m = %d: max |split - fp32| = %s, between arms %s, max |logit| = %.3g" % (m, err, d, float(exact.abs().max())))
-    assert all(e < ATOL for e in err.values()) and all(v < ATOL for v in d.values())
+    d = float((got["stream"] - got["gemm"]).abs().max())
+    print("m = %d: max |split - fp32| = %s, between arms %.3g, max |logit| = %.3g" % (m, err, d, float(exact.abs().max())))
+    assert all(e < ATOL for e in err.values()) and d < ATOL
     if m >= 128:
-        assert not torch.equal(got["stream"], got["program"])               # another arithmetic: the variable selects something
+        assert not torch.equal(got["stream"], got["gemm"])                  # another arithmetic: the variable selects something
     assert not torch.equal(got["stream"][0], got["stream"][1])                # per-image latents are honoured
 
 
-def test_grid33_and_point_range_three_arms(ctx, monkeypatch):
+def test_grid33_and_point_range_both_arms(ctx, monkeypatch):
     """35,937 points = 281 tiles on at most 256 workgroups: some workgroups re-enter the compact stream for a second tile.  A
     point range that starts and ends inside a tile equals the grid's values bit for bit."""
     net, latent, axis, st = ctx["net"], ctx["latent"][:1], ctx["axis"], ctx["split1"]
@@ -129,10 +128,9 @@ def test_grid33_and_point_range_three_arms(ctx, monkeypatch):
         assert bool(torch.all(ctx["exact_lg"][flips].abs() < BAND))
         part = net.query_grid_range(latent, axis, b, e, apply_sigmoid=True, state=st)
         assert torch.equal(part, occ[name].reshape(1, -1)[:, b:e])
-    for a_, b_ in (("stream", "program"), ("stream", "gemm")):
-        d = float((occ[a_] - occ[b_]).abs().max())
-        print("grid 33: max |%s - %s| = %.3g" % (a_, b_, d))
-        assert d < ATOL
+    d = float((occ["stream"] - occ["gemm"]).abs().max())
+    print("grid 33: max |stream - gemm| = %.3g" % d)
+    assert d < ATOL
 
 
 def test_identical_launches_are_bit_equal(ctx, monkeypatch):
@@ -168,3 +166,54 @@ def test_u_beyond_fp16_flags_the_tile_for_the_fp32_kernel(seeded_sd, monkeypatch
     assert flags.tolist() == [[0, 1, 0], [0, 0, 0]]
     assert bool(torch.isfinite(got).all()) and torch.equal(got[0, 128:256], exact[0, 128:256])
     assert float((got - exact).abs().cpu()[other].max()) < ATOL
+
+
+@pytest.fixture(scope="module")
+def many(seeded_sd):
+    """176 images - one more than block0_stream_fit allows - prepared once: the split state, and its fp32 programs as an
+    exact state (2 x 176 x 10.16 MB)."""
+    from zeroshape_amd.model.shape.implicit import DecoderState
+    n = 176
+    assert P.block0_stream_fit(n - 1) and not P.block0_stream_fit(n)
+    net = _net(seeded_sd)
+    latent = torch.from_numpy(syn.seeded_latent(seed=5, batch=n)).cuda()
+    split = net.prepare(latent, "f16x3", calibrate=False)
+    assert split.precision == "f16x3"
+    return dict(net=net, n=n, split=split, exact=DecoderState(split.exact, n, "f32"))
+
+
+def _images(state, idx):
+    """The split state of the images `idx` (a list) of `state`, or of its first `idx` images (an int)."""
+    from zeroshape_amd.model.shape.implicit import DecoderState
+    if isinstance(idx, int):
+        return DecoderState(state.programs[:idx], idx, "f16x3", exact=state.exact[:idx])
+    return DecoderState(state.programs[idx].contiguous(), len(idx), "f16x3", exact=state.exact[idx].contiguous())
+
+
+@pytest.mark.parametrize("m", [1, 129])
+def test_more_images_than_streams_fit_take_the_gemm_arm(many, monkeypatch, m):
+    """176 images in one launch: the tables and streams no longer fit the workspace's head, and block 0 runs its q/k/v GEMMs.
+    A point's value does not depend on the batch it rode in (same tile position, same wave, same lane), so images 0 and 175 of
+    that launch are bit-equal to a 2-image launch of their programs under ZS_SPLIT_BLOCK0_GEMM=1 - and, at 129 points, not to
+    the 2-image launch of the stream arm.  175 images still take the stream: images 0 and 174 are bit-equal to the stream
+    arm's 2-image launch (and, at 129 points, not to the GEMM arm's)."""
+    net, n, st = many["net"], many["n"], many["split"]
+    pts = torch.from_numpy(syn.seeded_cloud(400 + m, n, m, -1.5, 1.5)).cuda()
+    _arm(monkeypatch, {})
+    got = net.query_points(st, pts)
+    assert got.shape == (n, m) and int(net.last_tile_flags.sum()) == 0
+    err = float((got - net.query_points(many["exact"], pts)).abs().max())
+    print("m = %d, %d images: max |split - fp32| = %.3g" % (m, n, err))
+    assert err < ATOL
+    got175 = net.query_points(_images(st, n - 1), pts[:n - 1])
+    assert int(net.last_tile_flags.sum()) == 0
+    pair = {}
+    for ends in ([0, n - 1], [0, n - 2]):
+        for name, env in ARMS:
+            _arm(monkeypatch, env)
+            pair[name, ends[1]] = net.query_points(_images(st, ends), pts[ends].contiguous())
+    assert torch.equal(got[[0, n - 1]], pair["gemm", n - 1])
+    assert torch.equal(got175[[0, n - 2]], pair["stream", n - 2])
+    if m == 129:
+        assert not torch.equal(got[[0, n - 1]], pair["stream", n - 1])
+        assert not torch.equal(got175[[0, n - 2]], pair["gemm", n - 2])

@@ -1,7 +1,7 @@
 """Block 0's point-side q/k/v from the rank-4 table on the GPU (csrc/sdf_decoder_split.hip: BLOCK 0 TABLE): the table
-kernel against its host mirror, and the split decoder with the table (default) and with block 0's q/k/v GEMMs
-(ZS_SPLIT_BLOCK0_GEMM=1, read per launch) against the exact-fp32 kernel and against each other, at the bar of
-tests/test_gpu_decoder_split.py."""
+kernel against its host mirror, and the split decoder with block 0 from the compact stream built from that table (default)
+and with block 0's q/k/v GEMMs (ZS_SPLIT_BLOCK0_GEMM=1, read per launch) against the exact-fp32 kernel and against each
+other, at the bar of tests/test_gpu_decoder_split.py."""
 import numpy as np
 import pytest
 import torch
@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 ATOL = 1.5e-5   # tests/test_gpu_decoder_split.py: the split arithmetic against the exact-fp32 kernel (contract 1e-4)
 BAND = 1e-5     # |logit| below which an occupancy flip is inside the arithmetic's error
-ARMS = (("table", None), ("gemm", "1"))
+ARMS = (("stream", None), ("gemm", "1"))
 
 
 def _net(sd):
@@ -71,13 +71,13 @@ def test_point_lists_both_arms_vs_fp32_kernel(ctx, monkeypatch, m):
         got[name] = net.query_points(ctx["split"], pts)
         assert got[name].shape == (2, m) and int(net.last_tile_flags.sum()) == 0
     err = {name: float((got[name] - exact).abs().max()) for name in got}
-    d = float((got["table"] - got["gemm"]).abs().max())
-    print("m = %d: max |split - fp32| = %.3g (table) %.3g (gemm), max |table - gemm| = %.3g at max |logit| = %.3g" %
-          (m, err["table"], err["gemm"], d, float(exact.abs().max())))
-    assert err["table"] < ATOL and err["gemm"] < ATOL and d < ATOL
+    d = float((got["stream"] - got["gemm"]).abs().max())
+    print("m = %d: max |split - fp32| = %.3g (stream) %.3g (gemm), max |stream - gemm| = %.3g at max |logit| = %.3g" %
+          (m, err["stream"], err["gemm"], d, float(exact.abs().max())))
+    assert err["stream"] < ATOL and err["gemm"] < ATOL and d < ATOL
     if m == 129:
-        assert not torch.equal(got["table"], got["gemm"])                 # two arithmetics: the variable selects something
-    assert not torch.equal(got["table"][0], got["table"][1])               # per-image latents are honoured
+        assert not torch.equal(got["stream"], got["gemm"])                 # two arithmetics: the variable selects something
+    assert not torch.equal(got["stream"][0], got["stream"][1])               # per-image latents are honoured
 
 
 def test_grid33_and_point_range_both_arms(ctx, monkeypatch):
@@ -105,15 +105,15 @@ def test_grid33_and_point_range_both_arms(ctx, monkeypatch):
         assert bool(torch.all(exact_lg[flips].abs() < BAND))
         part = net.query_grid_range(latent, axis, b, e, apply_sigmoid=True, state=split_st)
         assert torch.equal(part, occ[name].reshape(1, -1)[:, b:e])
-    d = float((occ["table"] - occ["gemm"]).abs().max())
-    print("grid 33: max |table - gemm| = %.3g" % d)
+    d = float((occ["stream"] - occ["gemm"]).abs().max())
+    print("grid 33: max |stream - gemm| = %.3g" % d)
     assert d < ATOL
 
 
 def test_guard_fires_and_fp32_reevaluation_both_arms(monkeypatch):
     """(seed 3, gain 10, tol 1e-3) of test_other_weights_and_scales_vs_fp32_kernel with the envelope guard ON: q and k now come
-    from the table, the guard flags the tiles beyond the envelope and the exact kernel rewrites them.  Outputs are compared,
-    not flag sets: a q that moved by 1e-7 may move a tile across the threshold."""
+    from the table (through the compact stream's rank-5 operands), the guard flags the tiles beyond the envelope and the exact
+    kernel rewrites them.  Outputs are compared, not flag sets: a q that moved by 1e-7 may move a tile across the threshold."""
     from zeroshape_amd.utils.pos_embed import get_2d_sincos_pos_embed
     seed, gain, tol = 3, 10.0, 1e-3
     pe = get_2d_sincos_pos_embed(256, 14, cls_token=True).astype(np.float32)

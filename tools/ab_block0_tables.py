@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""Block 0's three arms in ONE process on ONE box: from its compact stream (default), q/k/v from the rank-4 table with the
-program's stream (ZS_SPLIT_BLOCK0_STREAM=program), from its GEMMs (ZS_SPLIT_BLOCK0_GEMM=1).
+"""Block 0's two arms in ONE process on ONE box: from its compact stream (default), from its q/k/v GEMMs
+(ZS_SPLIT_BLOCK0_GEMM=1; also what a launch of more than 175 images runs).
 
-The variables are read per launch, so the arms alternate block by block (blocks of `--block` launches, event-timed on the
+The variable is read per launch, so the arms alternate block by block (blocks of `--block` launches, event-timed on the
 launch stream; the order of the arms rotates from round to round), in the style of tools/ab_tile_order.py: the whole 129^3
 grid through zs_sdf_query_grid_range_split on a prepared state (launch only: table / stream kernels + decode kernel + the
 empty fp32 re-evaluation).
 
-    python tools/ab_block0_tables.py [--launches 40] [--block 4] > profiles/block0_stream_ab.txt
+    python tools/ab_block0_tables.py [--launches 40] [--block 4] > profiles/block0_two_arms_ab.txt
 """
 import argparse
 import os
@@ -23,16 +23,13 @@ from zeroshape_amd.model.shape.implicit import Implicit        # noqa: E402
 from zeroshape_amd.utils.pos_embed import get_2d_sincos_pos_embed   # noqa: E402
 
 
-ARMS = ("gemm", "table", "stream")
+ARMS = ("gemm", "stream")
 
 
 def set_arm(arm):
     os.environ.pop("ZS_SPLIT_BLOCK0_GEMM", None)
-    os.environ.pop("ZS_SPLIT_BLOCK0_STREAM", None)
     if arm == "gemm":
         os.environ["ZS_SPLIT_BLOCK0_GEMM"] = "1"
-    elif arm == "table":
-        os.environ["ZS_SPLIT_BLOCK0_STREAM"] = "program"
 
 
 def main():
@@ -70,7 +67,7 @@ def main():
     torch.cuda.synchronize()
     evs = []
     for blk in range(a.launches // a.block):
-        for arm in ARMS[blk % 3:] + ARMS[:blk % 3]:
+        for arm in ARMS[blk % 2:] + ARMS[:blk % 2]:
             for _ in range(a.block):
                 evs.append((arm,) + one(arm)[:2])
     torch.cuda.synchronize()
@@ -78,18 +75,16 @@ def main():
     times = {arm: [] for arm in ARMS}
     for arm, e0, e1 in evs:
         times[arm].append(e0.elapsed_time(e1))
-    print("# block 0: GEMMs (ZS_SPLIT_BLOCK0_GEMM=1) vs table (ZS_SPLIT_BLOCK0_STREAM=program) vs compact stream (default), one "
-          "process, alternating blocks of %d launches, %d launches per arm, vox %d" % (a.block, len(times["stream"]), a.vox_res))
-    for x, y in (("table", "gemm"), ("stream", "gemm"), ("stream", "table")):
-        print("# max |occupancy(%s) - occupancy(%s)| over the grid: %.3g" % (x, y, float((outs[x] - outs[y]).abs().max())))
+    print("# block 0: GEMMs (ZS_SPLIT_BLOCK0_GEMM=1) vs compact stream (default), one process, alternating blocks of %d "
+          "launches, %d launches per arm, vox %d" % (a.block, len(times["stream"]), a.vox_res))
+    print("# max |occupancy(stream) - occupancy(gemm)| over the grid: %.3g" % float((outs["stream"] - outs["gemm"]).abs().max()))
     print("%-6s %9s %9s %9s %9s" % ("arm", "mean ms", "median", "min", "max"))
     med, mean = {}, {}
     for arm in ARMS:
         t = sorted(times[arm])
         med[arm], mean[arm] = t[len(t) // 2], sum(t) / len(t)
         print("%-6s %9.3f %9.3f %9.3f %9.3f" % (arm, mean[arm], med[arm], t[0], t[-1]))
-    for x, y in (("table", "gemm"), ("stream", "gemm"), ("stream", "table")):
-        print("# %s / %s (median): %.4f   (mean): %.4f" % (x, y, med[x] / med[y], mean[x] / mean[y]))
+    print("# stream / gemm (median): %.4f   (mean): %.4f" % (med["stream"] / med["gemm"], mean["stream"] / mean["gemm"]))
 
 
 if __name__ == "__main__":

@@ -6,9 +6,8 @@ The kernel's LDS-DMA statements write M0 without saving it and count their own v
   * no scratch traffic / no private segment (a spill would also upset the counted waits);
   * every MFMA is a v_mfma_f32_32x32x16_f16 accumulating in place (the VGPR form where the
     registers allow, -mllvm -amdgpu-mfma-vgpr-form); the dynamic count (13,352 per wave tile since block 0
-    runs from its compact stream; 13,632 = 4,544 K-blocks with ZS_SPLIT_BLOCK0_STREAM=program, block 0's q/k/v
-    from the table; 14,784 = 4,928 with ZS_SPLIT_BLOCK0_GEMM=1 and in the instruction counters of profiles/
-    up to round 6);
+    runs from its compact stream; 14,784 = 4,928 K-blocks with ZS_SPLIT_BLOCK0_GEMM=1 and in the instruction
+    counters of profiles/ up to round 6);
   * each decode kernel carries LDS-DMAs and raw barriers, and allocates all 160 KiB of LDS;
   * hipcc does not see the MFMAs inside the asm K-blocks, so it pads no wait states behind them: no VALU instruction (in
     or outside asm) may read a register whose last writer is such an MFMA fewer than 12 issue slots behind it (8-pass

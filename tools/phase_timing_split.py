@@ -5,6 +5,7 @@ run with ZS_LIB_PATH pointing at it."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
+from zeroshape_amd import program as P
 from zeroshape_amd import synthetic as syn
 from zeroshape_amd.model.shape.implicit import Implicit
 from zeroshape_amd.utils.pos_embed import get_2d_sincos_pos_embed
@@ -23,8 +24,12 @@ ws = net.workspace(dev)
 tail = ws[-1024:].view(torch.int64).cpu().numpy()[:16]
 names = ["init", "point_proj", "b0 LN1", "b0 heads", "b0 LN2", "b0 MLP", "b1 LN1", "b1 heads", "b1 LN2", "b1 MLP",
          "final LN", "impl L0", "impl Z", "impl L1", "impl pairs", "drain"]
-kb = {3: 8 * 44, 5: 1024, 7: 8 * 92, 9: 1024, 11: 128, 12: 384, 13: 128, 14: 768}   # K-blocks (x 96 cycles); block 0's heads: 44 each, q/k/v come from the table
+# MFMAs (x 32 cycles); a K-block is three; block 0's heads run from the compact stream: 97 MFMAs each
+mfma = {3: P.HEADS * 97, 5: 3 * 1024, 7: 3 * P.HEADS * P.KB_HEAD, 9: 3 * 1024,
+        11: 3 * 128, 12: 3 * 384, 13: 3 * 128, 14: 3 * 768}
 for i in range(1, 16):
     d = int(tail[i] - tail[i - 1])
-    print("%-12s %9d ticks   MFMA cycles %s" % (names[i], d, kb[i] * 96 if i in kb else ""))
-print("total", int(tail[15] - tail[0]), " MFMA", 4544 * 96)   # 13,632 MFMAs per wave tile (4,928 K-blocks with ZS_SPLIT_BLOCK0_GEMM=1)
+    print("%-12s %9d ticks   MFMA cycles %s" % (names[i], d, mfma[i] * 32 if i in mfma else ""))
+assert sum(mfma.values()) == P.SPLIT_MFMAS_B0_STREAM
+# 13,352 MFMAs per wave tile (14,784 with ZS_SPLIT_BLOCK0_GEMM=1)
+print("total", int(tail[15] - tail[0]), " MFMA", P.SPLIT_MFMAS_B0_STREAM * 32)

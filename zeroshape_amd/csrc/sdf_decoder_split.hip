@@ -41,7 +41,6 @@
 //  * The attention map (implicit.py:277) is only produced by the fp32 kernel.
 #include "zs_common.h"
 #include <stdlib.h>
-#include <string.h>
 #include "sdf_layout.h"
 #include "sdf_math.h"
 #include "zs_split16.h"
@@ -77,7 +76,7 @@ constexpr int SLAB_TILES = NT - 1;                  // tiles of an activation ar
 constexpr int SLAB_U4 = SLAB_TILES * 4 * 64;        // ... as packed (hi, lo) K-blocks: 28 KiB per wave
 constexpr int ZTILES_F4 = NT * 4 * 64;              // one skip layer's fp32 feat partial products (workspace)
 static_assert(ZSLAB_F4 == 3 * ZTILES_F4, "the workspace slab holds three skip layers' feat partial products");
-static_assert(B0_TABLE_FLOATS == PRM_WINDOW, "an image's block-0 tables are loaded as one params window");
+static_assert(B0_TABLE_FLOATS == PRM_WINDOW, "block0_window_kernel / block0_stream_kernel index an image's table by PRM_WINDOW");
 constexpr int LDS_FLOATS = PRM_WINDOW + STAGE_FLOATS + WAVES * SLAB_U4 * 4;
 static_assert(LDS_FLOATS * 4 == 160 * 1024, "the kernel owns the whole LDS of a CU");
 static_assert(KB_TOTAL % CK == 0 && CK % WAVES == 0 && KPW * 2048 <= 4096, "chunking");
@@ -94,13 +93,6 @@ static_assert(P_BLK_STRIDE <= PRM_WINDOW && W_IB - W_IA <= PRM_WINDOW && P_USED 
               "params windows");
 
 #define DEV __device__ __forceinline__
-// fence between the MFMAs of a K-block and the side work placed in their dependency gaps
-// (ZS_FENCE_SCHED: a hard scheduling barrier; default: source order only, which hipcc keeps)
-#ifdef ZS_FENCE_SCHED
-#define ZS_FENCE __builtin_amdgcn_sched_barrier(0)
-#else
-#define ZS_FENCE do { } while (0)
-#endif
 
 // pin(ahi, alo): the prefetch reads issued above stay above (memory clobber) and the MFMAs that
 // consume this K-block's A operand stay below (they read the statement's outputs).  Without it
@@ -141,13 +133,10 @@ DEV void glds_kblocks(const char *gsrc, unsigned lds_dst) {  // this wave's two 
 #ifdef ZS_EXP_NO_DMA   // energy ablation (tools/energy_ablation.sh): results are garbage, the timing is the point
     if (gsrc != nullptr) return;
 #endif
-#ifndef ZS_DMA_MOD      // cache-policy modifiers of the weight stream's loads (experiments: " nt", " sc1", ...)
-#define ZS_DMA_MOD ""
-#endif
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ZS_DMA_MOD
-                 "\n\tglobal_load_lds_dwordx4 %0, off offset:1024" ZS_DMA_MOD
-                 "\n\tglobal_load_lds_dwordx4 %0, off offset:2048" ZS_DMA_MOD
-                 "\n\tglobal_load_lds_dwordx4 %0, off offset:3072" ZS_DMA_MOD
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
+                 "\n\tglobal_load_lds_dwordx4 %0, off offset:1024"
+                 "\n\tglobal_load_lds_dwordx4 %0, off offset:2048"
+                 "\n\tglobal_load_lds_dwordx4 %0, off offset:3072"
                  :
                  : "v"(gsrc), "s"(lds_dst)
                  : "memory");
@@ -175,8 +164,8 @@ struct AStream {
     u32x4 hi, lo;             // A operand of the next K-block (read in flight)
     const char *gsrc;         // this lane's source of this wave's K-blocks of the next chunk to stage
 
-    DEV void init(const char *prog, u32x4 *stage, unsigned stage_addr, int wave, int lane, int first_byte = 0) {
-        const char *g = prog + first_byte + wave * (KPW * KB_U4 * 16) + lane * 16;
+    DEV void init(const char *prog, u32x4 *stage, unsigned stage_addr, int wave, int lane) {
+        const char *g = prog + wave * (KPW * KB_U4 * 16) + lane * 16;
         // the previous tile's reads and DMAs are retired in every wave before the buffers are reused
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
@@ -221,24 +210,9 @@ struct AStream {
 #endif
         }
     }
-    // Step over `bytes` of the program: this wave's NEXT staged chunk comes from that much further on.  Only gsrc moves -
-    // nothing is in flight to it - so the buffers, the barriers and the counted waits are untouched.  Used by block 0 when
-    // its q/k/v come from the table (BLOCK 0 TABLE below) to pass the 48 q/k/v K-blocks = 6 whole chunks in front of every
-    // head; the stream starts 6 chunks in (init) and a head then consumes 44 K-blocks, so heads still alternate between
-    // chunk positions 0 and 4.  The pos-7 step of chunk n stages chunk n + 2, which fixes where head hd (hd < 7) bumps:
-    //  * P = 4 heads: the proj K-blocks fill two whole chunks and the next head starts on a chunk boundary.  Every wave
-    //    bumps BEFORE the proj loop: behind the attention's last pos-7 step, in front of the pos-7 step of proj tile 3, which
-    //    stages the next head's first chunk.
-    //  * P = 0 heads: proj takes pos 4-7 of one chunk, a whole chunk and pos 0-3 of a third, whose pos 4-7 are the next
-    //    head's first K-blocks (a MIXED chunk, staged by the pos-7 step of proj tile 1).  Waves 2 and 3 stage pos 4-7: they
-    //    bump BEFORE the proj loop.  Waves 0 and 1 stage pos 0-3: they bump in front of proj tile 2 - the mixed chunk is
-    //    staged, the next one (pos-7 step of proj tile 5) not yet.
-    //  * head 7 bumps nothing: block 0's MLP section follows it directly.
-    // Block 0 so consumes program K-blocks 92 h + 48 .. 92 h + 91 for h = 0..7, then 736 on (program.split_consumed_kblocks;
-    // tests/test_block0_tables.py replays this schedule wave by wave).
-    DEV void skip(int bytes) { gsrc += bytes; }
-    // The NEXT staged chunk comes from `base` (chunk-aligned in its own stream): block 0's compact stream hands over to the
-    // program (BLOCK 0 STREAM below).  Like skip(), only gsrc moves.
+    // This wave's NEXT staged chunk comes from `base` (chunk-aligned in its own stream): block 0's compact stream hands over
+    // to the program (BLOCK 0 STREAM below).  Only gsrc moves - nothing is in flight to it - so the buffers, the barriers and
+    // the counted waits are untouched.
     DEV void seek(const char *base, int wave, int lane) { gsrc = base + wave * (KPW * KB_U4 * 16) + lane * 16; }
     DEV void drain() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 };
@@ -277,8 +251,9 @@ DEV f32x16 zero16() {
 // 96): 12 plain VALU behind the three MFMAs 126.6, the same 12 as 4 + 4 + 4 in the gaps 101.6;
 // 18: 138.6 vs 113.1; but 24: 157 either way, and a transcendental shares a gap with at most one
 // plain instruction (exp + 1: 99.6; exp + 2: 124.6; exp + 3: 135-156).  Hence: side(kb, g) is
-// called behind the g-th MFMA of K-block kb, fenced by sched_barrier(0) so hipcc cannot regroup
-// it, and the activations are cut into gap-sized stages (GeluStager, SoftplusStager below).
+// called behind the g-th MFMA of K-block kb (source order, which hipcc keeps here; fencing it
+// in with sched_barrier(0) spilled: kblock_gelu below), and the activations are cut into
+// gap-sized stages (GeluStager, SoftplusStager below).
 struct NoSide {
     DEV void operator()(int, int) const {}
 };
@@ -291,17 +266,11 @@ DEV void mfma3_gaps(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4
         return;
     }
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(alo), as_h(bhi), acc, 0, 0, 0);
-    ZS_FENCE;
     side(kb, 0);
-    ZS_FENCE;
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(ahi), as_h(blo), acc, 0, 0, 0);
-    ZS_FENCE;
     side(kb, 1);
-    ZS_FENCE;
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(ahi), as_h(bhi), acc, 0, 0, 0);
-    ZS_FENCE;
     side(kb, 2);
-    ZS_FENCE;
 }
 
 // Collects the split B operands of an activation tile, one value at a time (index 0..15)
@@ -456,17 +425,11 @@ template <typename SIDE>
 DEV void mfma3_breg(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi, const u32x4 &blo, int kb,
                     SIDE &side) {
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(alo), "a"(bhi));
-    ZS_FENCE;
     side(kb, 0);
-    ZS_FENCE;
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(ahi), "a"(blo));
-    ZS_FENCE;
     side(kb, 1);
-    ZS_FENCE;
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(ahi), "a"(bhi));
-    ZS_FENCE;
     side(kb, 2);
-    ZS_FENCE;
 }
 template <int KT, typename SIDE = NoSide>
 DEV void gemm_areg(AStream &s, const PT *X, f32x16 &acc, SIDE side = SIDE()) {  // starts chunk-aligned
@@ -488,17 +451,11 @@ template <typename SIDE>
 DEV void mfma3_cacc(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi, const u32x4 &blo, int kb,
                     SIDE &side) {
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(alo), "v"(bhi));
-    ZS_FENCE;
     side(kb, 0);
-    ZS_FENCE;
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(ahi), "v"(blo));
-    ZS_FENCE;
     side(kb, 1);
-    ZS_FENCE;
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(ahi), "v"(bhi));
-    ZS_FENCE;
     side(kb, 2);
-    ZS_FENCE;
 }
 // one input tile (2 K-blocks) starting at chunk position pos0 (even); side sees K-blocks kb0, kb0 + 1.
 // YACC: acc is a tile of the residual stream (AGPR-resident, see mfma3_cacc)
@@ -644,21 +601,11 @@ DEV f32x16 rp16(const float *prm, int off, int tile, int hi) {
 //     LN1(pf) = rstd g (A - 1 m) p~ + b          (m: column mean of A; rstd: the point's scalar from ln_stats)
 //     qkv     = rstd (T p~) + c,   T = Wqkv diag(g) (A - 1 m)  [768 x 4],   c = Wqkv b + bqkv
 // for all 768 q/k/v rows of block 0.  T and c depend on the weights only (block0_window_kernel writes them in front of every
-// launch), so block 0 needs neither its LN1 -> pack -> slab pass nor its 8 x 48 q/k/v K-blocks (384 of 4,928 per wave tile).
-// Window layout (floats; one load_params): [b_proj 256][c 768, row-param order][T 3,072, [tile][hi][r][4]], tile = 3 head + {q, k, v}.
+// launch).  The decode kernel does not read the table itself: block0_stream_kernel builds the compact stream's operands
+// from it (BLOCK 0 STREAM below).
+// Layout (floats): [b_proj 256][c 768, row-param order][T 3,072, [tile][hi][r][4]], tile = 3 head + {q, k, v}.
 constexpr int B0_BPROJ = 0, B0_C = 256, B0_T = 1024;
 static_assert(B0_T + HEADS * 3 * 128 == PRM_WINDOW, "the block-0 table is exactly one params window");
-// xr, yr, zr = (x, y, z) * rstd
-DEV f32x16 block0_qkv(const float *prm, int tile, int hi, float xr, float yr, float zr, float rstd) {
-    f32x16 v = rp16(prm, B0_C, tile, hi);
-    const f32x4 *q = reinterpret_cast<const f32x4 *>(prm + B0_T + tile * 128 + hi * 64);
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const f32x4 w = q[r];
-        v[r] = fmaf(w.z, zr, fmaf(w.y, yr, fmaf(w.x, xr, fmaf(w.w, rstd, v[r]))));
-    }
-    return v;
-}
 // BLOCK 0 STREAM.  With the table, q_h = rstd (T_q p~) + c_q is affine in u = (rstd x, rstd y, rstd z, rstd, 1), so the
 // 224 latent logits of a head are S_h = U_h u, U_h = c K_h [T_q,h | c_q,h] (224 x 5; c = 32^-1/2 log2 e folded in: S comes
 // out in the log2 domain), and q, k, v are [T | c] u.  A rank-5 contraction with both operands split is 15 products per
@@ -848,23 +795,33 @@ DEV void attn_tile(AStream &s, const PT &q, f32x16 &o, float &m_run, float &z_ru
     softmax_pv<MASK>(s, S, o, m_run, z_run, c, hi, pos0 + 2);
 }
 
+// The self logit joins the running softmax over the latents (reference m_run, lane-half sums z_run) and the head's output
+// is normalised: o = (alpha o + p_self v) / z.
+DEV void merge_self(f32x16 &o, const f32x16 &v, float m_run, float z_run, float s_self) {
+    const float m_new = fmaxf(m_run, s_self);
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    const float p_self = __builtin_amdgcn_exp2f(s_self - m_new);
+    const float z = fmaf(half_sum(z_run), alpha, p_self);
+    const float inv = 1.0f / z;
+    const float a_i = alpha * inv, p_i = p_self * inv;
+#pragma unroll
+    for (int r = 0; r < 16; r++) o[r] = fmaf(p_i, v[r], o[r] * a_i);
+}
+
 #ifdef ZS_EXP_TIMING  // tools/phase_timing_split.py: cycle stamps of (block 0, wave 0, first tile) -> workspace tail
 #define ZS_STAMP(i) do { if (dbg) dbg[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define ZS_STAMP(i) do { } while (0)
 #endif
 // One wave: 32 points (lane & 31; both lane halves carry the same point).
-// tbl: this image's block-0 table (BLOCK 0 TABLE above; wave-uniform), or null: block 0 runs its q/k/v GEMMs like block 1
-// b0s: this image's compact block-0 stream (BLOCK 0 STREAM above; wave-uniform; tbl is null then), or null
+// b0s: this image's compact block-0 stream (BLOCK 0 STREAM above; wave-uniform), or null: block 0 runs its q/k/v GEMMs like block 1
 DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage_addr, u32x4 *slab,
-                      const float *tbl, const char *b0s, float px, float py, float pz, int wave, int lane, float &guard,
+                      const char *b0s, float px, float py, float pz, int wave, int lane, float &guard,
                       unsigned long long *dbg) {
     const int hi = lane >> 5;
     const float *prog_params = reinterpret_cast<const float *>(prog) + REC_FLOATS;
-    constexpr int QKV_BYTES = 3 * NT * 2 / CK * CHUNK_BYTES;   // q/k/v K-blocks of a head: 6 whole chunks
-    static_assert(3 * NT * 2 % CK == 0, "AStream::skip passes whole chunks");
     AStream s;
-    s.init(b0s ? b0s : prog, stage, stage_addr, wave, lane, tbl ? QKV_BYTES : 0);   // table: head 0's q/k/v are the first six chunks
+    s.init(b0s ? b0s : prog, stage, stage_addr, wave, lane);
     Slab sl;
     sl.fl = slab;
     ZS_STAMP(0);
@@ -881,9 +838,8 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
 
 #pragma unroll 1
     for (int blk = 0; blk < BLOCKS; blk++) {
-        const bool tab = blk == 0 && tbl != nullptr;   // wave-uniform
         const bool strm = blk == 0 && b0s != nullptr;  // wave-uniform
-        float rstd0 = 0.f, xr = 0.f, yr = 0.f, zr = 0.f;
+        float rstd0 = 0.f;
         u32x4 ub = {0u, 0u, 0u, 0u};
         bool u_bad = false;
         if (strm) {
@@ -892,14 +848,6 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
             float mean;
             ln_stats(y, mean, rstd0);
             ub = rank5_b(px * rstd0, py * rstd0, pz * rstd0, rstd0, hi, u_bad);
-        } else if (tab) {
-            // the table window instead of the block window (which returns behind the heads): LN1's output is not needed
-            load_params(prm, tbl, 0, PRM_WINDOW);
-            float mean;
-            ln_stats(y, mean, rstd0);
-            xr = px * rstd0;
-            yr = py * rstd0;
-            zr = pz * rstd0;
         } else {
             load_params(prm, prog_params, W_BLK + blk * P_BLK_STRIDE, P_BLK_STRIDE);
             layer_norm_lds(y, sl, prm, PB_LN1G, PB_LN1B, hi);
@@ -907,25 +855,18 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
         ZS_STAMP(2 + blk * 4);
         // y = x + proj_bias + sum_heads Wproj_h o_h
 #pragma unroll
-        for (int nt = 0; nt < NT; nt++) y[nt] += rp16(prm, tab ? B0_BPROJ : PB_BPROJ, nt, hi);
+        for (int nt = 0; nt < NT; nt++) y[nt] += rp16(prm, PB_BPROJ, nt, hi);
 
         // one head: 48 (q, k, v) + 28 (7 latent tiles) + 16 (proj) = 92 K-blocks = 11.5 chunks, so
         // heads alternate between chunk positions 0 and 4 (P); all positions are compile-time
         auto head = [&](int hd, auto Ptag) {
             constexpr int P = decltype(Ptag)::value;
-            f32x16 q, k, v;
-            if (tab) {
-                q = block0_qkv(prm, hd * 3 + 0, hi, xr, yr, zr, rstd0);
-                k = block0_qkv(prm, hd * 3 + 1, hi, xr, yr, zr, rstd0);
-                v = block0_qkv(prm, hd * 3 + 2, hi, xr, yr, zr, rstd0);
-            } else {
-                q = rp16(prm, PB_BQKV, hd * 3 + 0, hi);
-                gemm_lds(s, sl, q, P);
-                k = rp16(prm, PB_BQKV, hd * 3 + 1, hi);
-                gemm_lds(s, sl, k, P);
-                v = rp16(prm, PB_BQKV, hd * 3 + 2, hi);
-                gemm_lds(s, sl, v, P);
-            }
+            f32x16 q = rp16(prm, PB_BQKV, hd * 3 + 0, hi);
+            gemm_lds(s, sl, q, P);
+            f32x16 k = rp16(prm, PB_BQKV, hd * 3 + 1, hi);
+            gemm_lds(s, sl, k, P);
+            f32x16 v = rp16(prm, PB_BQKV, hd * 3 + 2, hi);
+            gemm_lds(s, sl, v, P);
 
             // logits are kept in the log2 domain: c = d^-1/2 * log2(e), softmax = 2^(c s - m)
             const float c = scale * 1.44269504088896340736f;
@@ -945,32 +886,18 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
 
             float m_run = -INFINITY, z_run = 0.f;
             f32x16 o = zero16();
-#pragma unroll 1
+            // unrolled: as a loop (`unroll 1`) this cost short launches 0.2 - 0.4 % once the table arm was gone
+#pragma unroll
             for (int l2 = 0; l2 < (LT - 1) / 2; l2++) {
                 attn_tile<false>(s, qp, o, m_run, z_run, c, hi, P);
                 attn_tile<false>(s, qp, o, m_run, z_run, c, hi, (P + 4) & (CK - 1));
             }
             attn_tile<true>(s, qp, o, m_run, z_run, c, hi, P);
-            {
-                const float m_new = fmaxf(m_run, s_self);
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-                const float p_self = __builtin_amdgcn_exp2f(s_self - m_new);
-                const float z = fmaf(half_sum(z_run), alpha, p_self);
-                const float inv = 1.0f / z;
-                const float a_i = alpha * inv, p_i = p_self * inv;
-#pragma unroll
-                for (int r = 0; r < 16; r++) o[r] = fmaf(p_i, v[r], o[r] * a_i);
-            }
+            merge_self(o, v, m_run, z_run, s_self);
             // y += Wproj[:, head] o_h
             const PT op = pack_tile(o);
-            // the next head's q/k/v K-blocks are not consumed: AStream::skip has the bump points
-            const bool bump = tab && hd + 1 < HEADS;   // wave-uniform
-            if (bump && (P == 4 || wave >= 2)) s.skip(QKV_BYTES);
 #pragma unroll
-            for (int nt = 0; nt < NT; nt++) {
-                if (P == 0 && nt == 2 && bump && wave < 2) s.skip(QKV_BYTES);
-                gemm_one(s, op, y[nt], (P + 4 + 2 * nt) & (CK - 1));
-            }
+            for (int nt = 0; nt < NT; nt++) gemm_one(s, op, y[nt], (P + 4 + 2 * nt) & (CK - 1));
         };
         // one head of block 0 from the compact stream (BLOCK 0 STREAM): 34 slots from chunk position P
         auto head_b0s = [&](int hd, auto Ptag) {
@@ -1009,16 +936,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                 else
                     softmax_pv<true, 1>(s, S, o, m_run, z_run, 1.0f, hi, P + 7 + 5 * i);
             }
-            {
-                const float m_new = fmaxf(m_run, s_self);
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-                const float p_self = __builtin_amdgcn_exp2f(s_self - m_new);
-                const float z = fmaf(half_sum(z_run), alpha, p_self);
-                const float inv = 1.0f / z;
-                const float a_i = alpha * inv, p_i = p_self * inv;
-#pragma unroll
-                for (int r = 0; r < 16; r++) o[r] = fmaf(p_i, v[r], o[r] * a_i);
-            }
+            merge_self(o, v, m_run, z_run, s_self);
             const PT op = pack_tile(o);
             // head 7's proj K-blocks are the compact stream's last two chunks: their pos-7 steps stage the program's
             if (P == 6 && hd == HEADS - 1) s.seek(prog + HEADS * (G_HEAD / 2) * (KB_U4 * 16), wave, lane);
@@ -1047,7 +965,6 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
         }
 
         ZS_STAMP(3 + blk * 4);
-        if (tab) load_params(prm, prog_params, W_BLK, P_BLK_STRIDE);   // block 0's own window, for LN2 and the MLP
         // MLP (timm Mlp): y += b2 + W2 gelu(W1 LN2(y) + b1), one hidden tile at a time
         layer_norm_lds(y, sl, prm, PB_LN2G, PB_LN2B, hi);
 #pragma unroll
@@ -1270,8 +1187,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
     float *__restrict__ out, int apply_sigmoid, f32x4 *__restrict__ workspace,
     int *__restrict__ tile_flags,    // [tiles] zeroed by the caller, or null
     int static_order,                // 1: tile += gridDim.x, no counter (ZS_SPLIT_STATIC_TILES=1: the A/B arm of tools/ab_tile_order.py)
-    const float *__restrict__ block0_tables,    // [batch][PRM_WINDOW] (block0_window_kernel), or null: block 0 runs its q/k/v GEMMs
-    const char *__restrict__ block0_streams) {  // [batch][B0_STREAM_BYTES] (block0_stream_kernel; the tables are null then), or null
+    const char *__restrict__ block0_streams) {  // [batch][B0_STREAM_BYTES] (block0_stream_kernel), or null: block 0's GEMMs
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     float *prm = lds;
     const int lane = threadIdx.x & 63;
@@ -1330,9 +1246,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sdf_decode_split_kernel(
         unsigned long long *dbg = nullptr;
 #endif
         float guard = 0.f;
-        const float *tbl = block0_tables ? block0_tables + (size_t)img * PRM_WINDOW : nullptr;
         const char *b0s = block0_streams ? block0_streams + (size_t)img * B0_STREAM_BYTES : nullptr;
-        float logit = decode_tile(prog, prm, stage, stage_addr, fl, tbl, b0s, px, py, pz, wave, lane, guard, dbg);
+        float logit = decode_tile(prog, prm, stage, stage_addr, fl, b0s, px, py, pz, wave, lane, guard, dbg);
         if (apply_sigmoid) logit = 1.0f / (1.0f + expf(-logit));
         // ENVELOPE (zeroshape_amd/program.py, S_GUARD): outside it the tile is flagged for the
         // exact-fp32 kernel, and a program with non-finite / out-of-range operands yields NaN like
@@ -1620,30 +1535,21 @@ __global__ __launch_bounds__(B0_THREADS) void block0_stream_kernel(const char *_
 // only and could be computed once per weight version, but the program's bytes are pinned (tests compare them with the host
 // mirror word for word) and the entry points keep their signatures, so there is nowhere to keep them: 24 small workgroups per image
 // per launch (microseconds) against ~8 % of the decode launch.  A plain kernel launch: capturable.
-// Behind the tables of all images, while both fit (block0_stream_fit: 175 images), the compact block-0 streams, 544 KiB per
-// image from 8 more small workgroups: the default arm.  The arms, read per launch (tools/ab_block0_tables.py alternates them):
-//   ZS_SPLIT_BLOCK0_GEMM=1            block 0 runs its q/k/v GEMMs (also: the tables do not fit)            -> {null, null}
-//   ZS_SPLIT_BLOCK0_STREAM=program    q/k/v from the table, the weight stream is the program's (AStream::skip; also: the
-//                                     streams do not fit): the arm program.split_consumed_kblocks describes  -> {tables, null}
-//   default                           block 0 from its compact stream                                        -> {null, streams}
-struct Block0Arm {
-    const float *tables;
-    const char *streams;
-};
-Block0Arm launch_block0_arm(const void *split_programs, size_t program_stride_bytes, int batch, void *workspace,
-                            hipStream_t st) {
+// Behind the tables of all images the compact block-0 streams, 544 KiB per image from 8 more small workgroups, which the
+// decode kernel runs block 0 from.  -> the streams, or null: block 0 runs its q/k/v GEMMs from the program, like block 1 -
+// with ZS_SPLIT_BLOCK0_GEMM=1 (read per launch: tools/ab_block0_tables.py alternates the two arms) and when tables and
+// streams do not both fit (block0_stream_fit: more than 175 images per launch); neither kernel is launched then.
+const char *launch_block0_arm(const void *split_programs, size_t program_stride_bytes, int batch, void *workspace,
+                              hipStream_t st) {
     const char *e = getenv("ZS_SPLIT_BLOCK0_GEMM");
-    if (e && atoi(e) != 0) return {nullptr, nullptr};
-    if (!block0_tables_fit(batch)) return {nullptr, nullptr};
+    if ((e && atoi(e) != 0) || !block0_stream_fit(batch)) return nullptr;
     float *tables = static_cast<float *>(workspace);
     hipLaunchKernelGGL(block0_window_kernel, dim3(HEADS * 3, batch), dim3(B0_THREADS), 0, st,
                        static_cast<const char *>(split_programs), program_stride_bytes, tables);
-    const char *a = getenv("ZS_SPLIT_BLOCK0_STREAM");
-    if ((a && strcmp(a, "program") == 0) || !block0_stream_fit(batch)) return {tables, nullptr};
     char *streams = block0_streams(workspace, batch);
     hipLaunchKernelGGL(block0_stream_kernel, dim3(HEADS, batch), dim3(B0_THREADS), 0, st,
                        static_cast<const char *>(split_programs), program_stride_bytes, tables, streams);
-    return {nullptr, streams};
+    return streams;
 }
 
 // in front of every split launch: the dynamic tile order's counter (in the workspace tail) starts at zero whatever
@@ -1655,18 +1561,17 @@ int launch_counter_reset(void *workspace, hipStream_t st) {
     return 0;
 }
 
-// The one launch of sdf_decode_split_kernel over the query q, behind the counter reset and the block-0 tables of its images.
+// The one launch of sdf_decode_split_kernel over the query q, behind the counter reset and the block-0 streams of its images.
 int launch_decode_split(const char *who, const void *split_programs, size_t program_stride_bytes, int batch, const Query &q,
                         float *out, int *tile_flags, void *workspace, void *stream) {
     if (q.m == 0) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int static_order = launch_counter_reset(workspace, st);
-    const Block0Arm b0 = launch_block0_arm(split_programs, program_stride_bytes, batch, workspace, st);
+    const char *b0s = launch_block0_arm(split_programs, program_stride_bytes, batch, workspace, st);
     hipLaunchKernelGGL(q.points ? sdf_decode_split_kernel<false> : sdf_decode_split_kernel<true>,
                        dim3(decode_grid_size(batch, q.m)), dim3(WAVES * 64), 0, st,
                        static_cast<const char *>(split_programs), program_stride_bytes, batch, q.points, q.axis, q.G,
-                       q.first_point, q.m, out, q.apply_sigmoid, static_cast<f32x4 *>(workspace), tile_flags, static_order,
-                       b0.tables, b0.streams);
+                       q.first_point, q.m, out, q.apply_sigmoid, static_cast<f32x4 *>(workspace), tile_flags, static_order, b0s);
     return zs::check_launch(who) ? 1 : 0;
 }
 

@@ -44,8 +44,7 @@ __host__ __device__ inline int *tile_counter(void *workspace) {
 }
 constexpr int B0_STREAM_KB = 8 * 34;                        // K-block slots of a compact block-0 stream: 34 per head
 constexpr size_t B0_STREAM_BYTES = (size_t)B0_STREAM_KB * 2048;   // 544 KiB = 34 whole chunks
-inline bool block0_tables_fit(int batch) { return (size_t)batch * B0_TABLE_FLOATS * sizeof(float) <= SLAB_REGION_BYTES; }
-// tables AND streams (175 images); beyond it a launch runs block 0 from the tables alone, beyond block0_tables_fit its GEMMs
+// tables AND streams (175 images); a launch of more images runs block 0's q/k/v GEMMs from the program and writes neither
 inline bool block0_stream_fit(int batch) {
     return (size_t)batch * (B0_TABLE_FLOATS * sizeof(float) + B0_STREAM_BYTES) <= SLAB_REGION_BYTES;
 }

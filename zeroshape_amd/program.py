@@ -481,8 +481,9 @@ def latent_k_bounds(prog):
 # Block 0's point row is pf = point_proj(xyz) = A p~, p~ = (x, y, z, 1), so LN1(pf) = rstd * g (A - 1 m) p~ + b with m the
 # column mean of A and rstd the per-point scalar, and for the 768 rows of block 0's qkv
 #     qkv = rstd * (T p~) + c,    T = Wqkv diag(g) (A - 1 m)  [768 x 4],    c = Wqkv b + bqkv.
-# The split kernel reads T and c from a 4,096-float window instead of running the three 256 -> 256 GEMMs per head, and
-# steps over their 48 K-blocks per head in the weight stream (which keep their place in the program).
+# T and c go into a 4,096-float window per image.  The split kernel no longer reads it directly: block0_stream_kernel builds
+# the compact block-0 stream (below) from it, and a launch whose streams do not fit runs block 0's three 256 -> 256 GEMMs per
+# head from the program, like block 1 (the program keeps all its K-blocks either way).
 B0_WINDOW_FLOATS = 4096
 B0_BPROJ, B0_C, B0_T = 0, C, C + HEADS * 96      # [b_proj 256][c 768: row-param order][T 3072: [tile][hi][r][4]]
 KB_HEAD = G_HEAD // 2                            # 92 K-blocks per head: 48 q/k/v, 28 latent K/V, 16 proj
@@ -520,9 +521,9 @@ def _from_rowparam(v):
 
 
 def block0_window(split_prog):
-    """The 4,096 floats the split kernel reads for block 0 in place of its LN1 / q, k, v GEMMs, from one SPLIT program
-    (uint32 words, split_program()): [b_proj | c | T] as laid out above, computed in float64 and rounded once to float32 -
-    host mirror of zs_sdf_block0_tables."""
+    """The 4,096 floats that stand for block 0's LN1 / q, k, v GEMMs (the compact stream's q, k, v and U operands are built
+    from them), from one SPLIT program (uint32 words, split_program()): [b_proj | c | T] as laid out above, computed in
+    float64 and rounded once to float32 - host mirror of zs_sdf_block0_tables."""
     words = np.ascontiguousarray(split_prog).view(np.uint32)
     params = words[REC_FLOATS:].view(np.float32).astype(np.float64)
     d = PARAMS.blk[0]
@@ -551,14 +552,6 @@ def _rowparam64(v):
     T = v.shape[0] // 32
     idx = (32 * np.arange(T))[:, None, None] + ROW_TABLE[None, :, :]
     return v[idx].reshape(-1)
-
-
-def split_consumed_kblocks():
-    """K-blocks of the SPLIT program (its own stream order: the positions the weight stream's DMAs read from) in the order
-    the split kernel consumes them when block 0's q/k/v come from the table: everything but the 48 q/k/v K-blocks in front of
-    each of block 0's eight heads - head h keeps 92 h + 48 .. 92 h + 91, the MLP section follows from 736 on (4,544 in all)."""
-    keep = [kb for kb in range(KB_TOTAL) if not (kb < HEADS * KB_HEAD and kb % KB_HEAD < KB_QKV_HEAD)]
-    return np.array(keep)
 
 
 # ----------------------------------------------------------------------------- #
@@ -603,8 +596,8 @@ def block0_stream_slots():
 
 
 def block0_stream_fit(batch):
-    """Do the tables AND the compact streams of `batch` images fit the head of the workspace (csrc/sdf_query.h)?  Beyond it a
-    launch takes the table arm (block0_window alone), beyond that the GEMMs."""
+    """Do the tables AND the compact streams of `batch` images fit the head of the workspace (csrc/sdf_query.h: 175 images)?
+    A launch of more images runs block 0's q/k/v GEMMs from the program, as ZS_SPLIT_BLOCK0_GEMM=1 does."""
     return batch * (B0_WINDOW_FLOATS * 4 + B0S_WORDS * 4) <= SLAB_REGION_BYTES
 
 
