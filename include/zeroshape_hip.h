@@ -18,7 +18,7 @@
  *                           driven by compute_level_grid, utils/eval_3D.py:22-45, and
  *                           get_dense_3D_grid, utils/eval_3D.py:11-20
  *   zs_bf_lower_bounds   <- pruning for brute_force_search, utils/eval_3D.py:140-170
- *   zs_pose_search_batch <- one batch of brute_force_search, utils/eval_3D.py:149-168
+ *   zs_pose_search_batch_sorted <- one batch of brute_force_search, utils/eval_3D.py:149-168
  *   zs_normalize_pc      <- normalize_pc, utils/eval_3D.py:93-102
  *   zs_standardize_pc, zs_icp_step <- standardize_pc, ICP, utils/eval_3D.py:83-91, 271-284
  *   zs_fscore            <- compute_fscore, utils/eval_3D.py:215-231
@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define ZS_ABI_VERSION 45
+#define ZS_ABI_VERSION 46
 
 /* ABI version of the loaded library (== ZS_ABI_VERSION it was built with). */
 int zs_abi_version(void);
@@ -293,8 +293,8 @@ int zs_bf_lower_bounds(const float *pred, int n, const float *gt_normalized, int
  * Fused pose search (brute_force_search, utils/eval_3D.py:140-170) and its helpers
  * normalize_pc (:93-102) and compute_fscore (:215-231).
  *
- * zs_pose_search_batch evaluates `count` (<= zs_pose_max_batch()) rotations exactly - rotate
- * pred[n][3], normalize_pc, nearest neighbours both ways against gt_normalized[m][3] with the
+ * zs_pose_search_batch_sorted - the one search entry - evaluates `count` (<= zs_pose_max_batch()) rotations exactly:
+ * rotate pred[n][3], normalize_pc, nearest neighbours both ways against the normalised ground truth [m][3] with the
  * arithmetic of zs_chamfer_forward, sqrt, means, the six F-score thresholds - and merges the
  * lexicographic (Chamfer-L1, rotation index) minimum into the running record `best`
  * (zs_pose_best_bytes(), device; zs_pose_best_init first): float cd, int32 index, float acc,
@@ -307,49 +307,31 @@ int zs_bf_lower_bounds(const float *pred, int n, const float *gt_normalized, int
  * batch cannot beat `best`, the kernels return at once, so all batches can be enqueued without
  * a host synchronisation.  No rotated cloud, distance or index array is materialised; results
  * are bit-reproducible (fixed reduction order) whatever batch a rotation is evaluated in.
- * scratch: zs_pose_scratch_bytes(n, m, count).
+ *
+ * Both clouds arrive twice: `pred` in the caller's order - the statistics of normalize_pc are summed in it, and it is the
+ * order zs_pose_apply sees - and pred_sorted / gt_sorted in the sort-tile-recursive order of zs_str_sort (x slabs, y strips
+ * inside a slab, z inside a strip; cuts at whole leaves of 64 points, three stable radix sorts, so the permutation is a
+ * pure function of the coordinates; scratch: zs_str_scratch_bytes(n); perm may be NULL), whose leaves of 64 consecutive
+ * points have near-cubic boxes, also after a rotation.  zs_pose_pack writes a sorted cloud as a PACK
+ * (zs_pose_pack_bytes(points)): [sub-tile of 64][x | y | z][64] coordinates, the exact box of every sub-tile and of every
+ * tile of 16 - the form in which a wave reads candidates through the scalar cache.  Three modes, one record:
+ *   mode 0  every pair, candidates staged in LDS (reads gt_sorted; gt_pack unused)   - the tests' independent reference
+ *   mode 1  every pair on packs (the kernel of mode 2 without the skipping)          - the tests' second reference
+ *   mode 2  every (query, 64 candidates) block whose box is farther than the query's current nearest neighbour is
+ *           skipped, tiles nearest first                                             - the default of brute_force_search
+ * All three give the same minima and the same fixed-order sums - the same record, bit for bit; mode 2 from a fraction of
+ * the distance evaluations (utils/eval_3D.py:140-170 evaluates them all).
+ * scratch: zs_pose_sorted_scratch_bytes(n, m, count) (one pack of the prediction per rotation of the batch).
  * zs_pose_apply: out[n][3] = normalize_pc(rotations[index[0]] pred) (index: device int32;
  * scratch: 64 bytes).  zs_normalize_pc: out[b][n][3] = normalize_pc(pc[b][n][3]) (scratch: 64 b
  * bytes).  zs_fscore: out[b][n_thresholds] from UN-squared distances dist1[b][n], dist2[b][m].
+ *
+ * Removed in ABI 46 (DESIGN.md section 4c names them): the unsorted search entry and its scratch size, the three entry
+ * points of the uniform-grid arm and the two of the Z-order sort.
  * ------------------------------------------------------------------------- */
 int zs_pose_max_batch(void);
-size_t zs_pose_scratch_bytes(int n, int m, int count);
 size_t zs_pose_best_bytes(void);
 int zs_pose_best_init(float *best, void *stream);
-int zs_pose_search_batch(const float *pred, int n, const float *gt_normalized, int m,
-                         const float *rotations, const int *order, int count, int index_offset,
-                         const float *lower_bound, const float *thresholds6, float *best,
-                         void *scratch, void *stream);
-/* The same batch through uniform grids (csrc/zs_point_grid.h): the ground truth binned once per search
- * (zs_pose_gt_grid into the first part of `grids`, zs_pose_grid_bytes(n, m, max batch) bytes, 16-byte aligned), the
- * rotated + normalised prediction once per rotation; ~10^2 instead of 10^4 distance evaluations per query and
- * bit-identical records (a skipped candidate provably has a strictly larger distance; sums formed in the same order). */
-size_t zs_pose_grid_bytes(int n, int m, int count);
-int zs_pose_gt_grid(const float *gt_normalized, int m, void *grids, void *stream);
-/* pred_stats (may be NULL = pred): the prediction in the order its mean is summed in (see zs_pose_search_batch_sorted). */
-int zs_pose_search_batch_grid(const float *pred, int n, const float *gt_normalized, int m, const float *rotations,
-                              const int *order, int count, int index_offset, const float *lower_bound,
-                              const float *thresholds6, float *best, void *scratch, void *grids, const float *pred_stats,
-                              void *stream);
-/* Box-culled scan (round 3, the default of brute_force_search).  zs_morton_sort orders a cloud along the Z-order curve
- * of its bounding box (30-bit keys, stable radix sort: the permutation is a pure function of the coordinates); perm
- * (may be NULL) receives sorted[i] = points[perm[i]], tile_boxes (may be NULL) the boxes lo[3], hi[3] of every `tile`
- * consecutive sorted points.  scratch: zs_morton_scratch_bytes(n).
- * zs_pose_pack writes a sorted cloud as a PACK (zs_pose_pack_bytes(points)): [sub-tile of 64][x | y | z][64]
- * coordinates, the exact box of every sub-tile and of every tile of 16 - the form in which a wave reads candidates
- * through the scalar cache.  zs_pose_search_batch_sorted is zs_pose_search_batch on such clouds: statistics from `pred`
- * in the caller's order - the order zs_pose_apply sees - nearest neighbours from the sorted ones.  mode 0: the all-pairs
- * kernel of zs_pose_search_batch (gt_sorted; gt_pack unused); mode 1: all pairs on packs; mode 2: every (query,
- * 64 candidates) block whose box is farther than the query's current nearest neighbour is skipped, tiles nearest first.
- * All three give the same minima and the same fixed-order sums - the same record, bit for bit; mode 2 from a fraction of
- * the distance evaluations (utils/eval_3D.py:140-170 evaluates them all).
- * scratch: zs_pose_sorted_scratch_bytes(n, m, count) (one pack of the prediction per rotation of the batch). */
-size_t zs_morton_scratch_bytes(int n);
-int zs_morton_sort(const float *points, int n, float *sorted, int *perm, float *tile_boxes, int tile, void *scratch,
-                   void *stream);
-/* Sort-tile-recursive order (x slabs, y strips inside a slab, z inside a strip; cuts at whole leaves of 64 points, three
- * stable radix sorts): leaves with near-cubic boxes - the default order of the pose search, which then evaluates about
- * half the pairs it needs with the Z-order.  scratch: zs_str_scratch_bytes(n); perm may be NULL. */
 size_t zs_str_scratch_bytes(int n);
 int zs_str_sort(const float *points, int n, float *sorted, int *perm, void *scratch, void *stream);
 size_t zs_pose_pack_bytes(int points);

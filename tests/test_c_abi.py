@@ -48,6 +48,38 @@ def test_versions_and_sizes(lib):
     assert lib.zs_last_error() in (b"", None) or isinstance(lib.zs_last_error(), bytes)
 
 
+def test_retired_evaluation_geometry_symbols_are_gone(lib):
+    """ABI 46 removed the pose search's unsorted entry and its scratch size, the uniform-grid arm and the Z-order sort:
+    none of them is named in the header (comments included), bound in SIGNATURES or exported by the built library, and
+    the library no longer carries the kernels that only they launched."""
+    from zeroshape_amd import _lib
+    removed = ["zs_pose_search_batch", "zs_pose_search_batch_grid", "zs_pose_gt_grid", "zs_pose_grid_bytes",
+               "zs_morton_sort", "zs_morton_scratch_bytes", "zs_pose_scratch_bytes"]
+    kernels = [b"pose_gt_grid_kernel", b"pose_pred_grid_kernel", b"pose_nn_grid_kernel", b"morton_key_kernel",
+               b"morton_gather_kernel", b"14nn_both_kernel"]        # (the last: its mangled name, length prefix included)
+    hdr = open(os.path.join(ROOT, "include", "zeroshape_hip.h")).read()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    blob = open(_lib.LIB_PATH, "rb").read()
+    for name in removed:
+        assert not re.search(r"\b%s\b" % name, hdr), name
+        assert name not in _lib.SIGNATURES, name
+        assert not hasattr(raw, name), name
+    for name in kernels:
+        assert name not in blob, name
+    assert b"pose_nn_soa_kernel" in blob and b"nn_both_sgpr_kernel" in blob      # (the probe does see kernel names)
+    assert lib.zs_abi_version() == 46
+
+
+def test_pose_search_selector_is_checked_before_any_device_work():
+    """brute_force_search takes nn = "cull", "pairs" or "brute"; anything else - the retired "grid" included - raises
+    ValueError naming the three before a tensor is moved or the library is loaded (so it does here, without a GPU)."""
+    import torch
+    from zeroshape_amd.utils import eval_3D as E
+    for bad in ("grid", "nonsense", "CULL", ""):
+        with pytest.raises(ValueError, match="'cull', 'pairs' or 'brute'"):
+            E.brute_force_search(torch.zeros(5, 3), torch.zeros(3, 3), device="cuda", nn=bad)
+
+
 def test_python_constants_equal_the_header():
     """Every #define ZS_ACT_* / ZS_CONV_* has a Python constant of the same value in nn/ops.py (the one place in nn/ that
     writes them), and the names nn/autograd.py and nn/operands.py hand on are those objects' values."""

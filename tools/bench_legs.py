@@ -51,10 +51,9 @@ def chamfer_leg(dev, cpu=True):
     ms_auto, _ = _events(lambda: ch(a, b), 10)
     pairs = 2.0 * B * n * m
     from zeroshape_amd import chamfer_3D as plugin
-    auto_is_grid = max(n, m) >= plugin.GRID_MIN_POINTS and not os.environ.get("ZS_CHAMFER_BRUTE")
-    # zs_chamfer_forward's scan since round 6: candidates as scalar operands of packed fp32 instructions (ZS_CHAMFER_LDS=1: the
-    # LDS-staged kernel of rounds 1-5)
-    brute_kernel = "nn_both_kernel<2>" if os.environ.get("ZS_CHAMFER_LDS") else "nn_both_sgpr_kernel<2>"
+    auto_is_grid = max(n, m) >= plugin.GRID_MIN_POINTS
+    # zs_chamfer_forward's scan: candidates as scalar operands of packed fp32 instructions
+    brute_kernel = "nn_both_sgpr_kernel<2>"
     out = {"shape": [B, n, m], "ms": round(ms_brute, 4), "ms_min": round(min_brute, 4),
            "tpairs_per_s": round(pairs / (ms_brute * 1e-3) / 1e12, 3),
            "roofline": {"bound": "valu_f32", "achieved": round(pairs * FLOP_PER_PAIR / (ms_brute * 1e-3) / 1e12, 2),

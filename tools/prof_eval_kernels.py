@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Driver for the rocprofv3 passes over the evaluation kernels other than the decoder (profiles/r02_eval_*):
-the Chamfer scan nn_both_kernel<2> on [24,10k]x[24,10k], the grid-accelerated exact kernel, one exhaustive
+the Chamfer scan nn_both_sgpr_kernel<2> on [24,10k]x[24,10k], the grid-accelerated exact kernel, one exhaustive
 6912-rotation pose search (pose_stats / pose_pack / pose_nn_soa / pose_kill / pose_finish), and the iso-surface
 kernels (mc_count, mc_emit, mesh sampling) on a 129^3 level grid of the decoder and on a 257^3 analytic one."""
 import os

@@ -75,17 +75,8 @@ SIGNATURES = {
     "zs_bf_lower_bounds": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
                                     _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_pose_max_batch": (_c_int, []),
-    "zs_pose_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
     "zs_pose_best_bytes": (_c_size_t, []),
     "zs_pose_best_init": (_c_int, [_c_void_p, _c_void_p]),
-    "zs_pose_search_batch": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int,
-                                      _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "zs_pose_grid_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
-    "zs_pose_gt_grid": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p]),
-    "zs_pose_search_batch_grid": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int,
-                                           _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "zs_morton_scratch_bytes": (_c_size_t, [_c_int]),
-    "zs_morton_sort": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p]),
     "zs_str_scratch_bytes": (_c_size_t, [_c_int]),
     "zs_str_sort": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_pose_pack_bytes": (_c_size_t, [_c_int]),
@@ -225,7 +216,7 @@ SIGNATURES = {
     "zs_readout_concat_bwd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
 }
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 _lib = None
 
 

@@ -12,14 +12,12 @@ chamfer3D.cu:142), wrong dtype / device / layout raise instead of corrupting mem
 and the kernels run on torch's CURRENT stream of the tensors' device rather than
 the legacy default stream.
 """
-import os
-
 import torch
 
 from . import _lib
 
 # clouds at least this large take the grid-accelerated kernel (bit-identical results);
-# ZS_CHAMFER_BRUTE=1 forces the brute-force scan (cross-checks, experiments)
+# method="brute" forces the brute-force scan (cross-checks, experiments)
 GRID_MIN_POINTS = 1024
 _WS = {}
 
@@ -63,8 +61,7 @@ def forward(xyz1, xyz2, dist1, dist2, idx1, idx2, method="auto"):
     lib = _lib.load()
     if method not in ("auto", "grid", "brute"):
         raise ValueError("method must be auto, grid or brute")
-    use_grid = min(n, m) > 0 and (method == "grid" or (
-        method == "auto" and max(n, m) >= GRID_MIN_POINTS and not os.environ.get("ZS_CHAMFER_BRUTE")))
+    use_grid = min(n, m) > 0 and (method == "grid" or (method == "auto" and max(n, m) >= GRID_MIN_POINTS))
     with torch.cuda.device(xyz1.device):
         if use_grid:
             nbytes = lib.zs_chamfer_workspace_bytes(b, n, m)

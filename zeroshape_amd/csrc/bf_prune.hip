@@ -205,7 +205,8 @@ extern "C" int zs_bf_lower_bounds(const float *pred, int n, const float *gt_norm
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     int *sc = static_cast<int *>(scratch);
-    const char *env = getenv("ZS_BF_FIELD_BRUTE");                          // A/B switch, read per call: the all-occupied-cells form
+    // kept: the all-occupied-cells form is the reference of test_lower_bound_field_by_sweeps_equals_the_all_cells_form (read per call)
+    const char *env = getenv("ZS_BF_FIELD_BRUTE");
     const bool brute = env && atoi(env) != 0;
     auto field = [&](const float *cloud, int count, float *grid) {
         hipLaunchKernelGGL(lb_build_kernel, dim3(1), dim3(1024), 0, s, cloud, count, grid, sc, brute ? 1 : 0);

@@ -1,25 +1,18 @@
-// Spatial sorts of a point cloud for the culled nearest-neighbour scan of the pose search
+// The spatial sort of a point cloud for the culled nearest-neighbour scan of the pose search
 // (csrc/pose_search.hip: pose_nn_soa_kernel).
 //
 // A cloud whose runs of 64 consecutive points are spatially compact stays so under any rigid rotation - which
 // is what lets the pose search skip every (query, 64 candidates) block whose box is farther away than the
-// nearest neighbour found so far (utils/eval_3D.py:140-170 evaluates every pair).  Two orders:
-//   zs_morton_sort   along the Z-order curve of the bounding box (one sort; runs straddle the curve's jumps)
+// nearest neighbour found so far (utils/eval_3D.py:140-170 evaluates every pair).
 //   zs_str_sort      sort-tile-recursive packing (the R-tree bulk-loading order): sort by x, cut into slabs of
 //                    whole leaves; inside a slab sort by y, cut into strips; inside a strip sort by z.  Three
-//                    sorts, leaves of 64 points with near-cubic boxes: on the benchmark clouds the culled scan
-//                    evaluates 12 % of the pairs with it against 22 % with the Z-order (CPU model of the kernel's
-//                    decisions; a k-d split order reaches 10 % at eight sorts).  The default of the pose search.
-//
-// Morton path:
-//   morton_bbox_kernel    one workgroup: min / max of the finite coordinates
-//   morton_key_kernel     30-bit key (10 bits per axis, x lowest) of every point, value = its index;
-//                         points with a non-finite coordinate sort to the end
-//   rocprim::radix_sort_pairs   stable LSD radix sort -> the permutation is a pure function of the
-//                         coordinates (equal keys keep their input order): summation orders that follow
-//                         it are reproducible from call to call
-//   morton_gather_kernel  sorted[i] = points[perm[i]], and per tile of `tile` consecutive sorted points
-//                         its axis-aligned box (lo[3], hi[3]; non-finite coordinates ignored)
+//                    stable LSD radix sorts (rocprim::radix_sort_pairs: the permutation is a pure function of the
+//                    coordinates, so summation orders that follow it are reproducible from call to call), leaves
+//                    of 64 points with near-cubic boxes: on the benchmark clouds the culled scan evaluates 12 % of
+//                    the pairs with it (CPU model of the kernel's decisions; a k-d split order reaches 10 % at
+//                    eight sorts).
+// The file keeps the name of the order it started with: the sort along the Z-order curve (one sort; runs straddle
+// the curve's jumps, 22 % of the pairs in the same model) is retired, DESIGN.md section 4c.
 #include "zs_common.h"
 #include "../../include/zeroshape_hip.h"
 
@@ -33,113 +26,7 @@ namespace {
 
 constexpr int MS_THREADS = 256;
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// lo[3], hi[3] over the workgroup of the points fetch(i), i in [begin, end) -> out[6]; non-finite coordinates ignored
-template <typename F>
-__device__ __forceinline__ void block_box(F fetch, int begin, int end, float *out, float (*red)[MS_THREADS / 64]) {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = begin + threadIdx.x; i < end; i += MS_THREADS) {
-        float v[3];
-        fetch(i, v);
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-            if (fabsf(v[a]) < INFINITY) {
-                lo[a] = fminf(lo[a], v[a]);
-                hi[a] = fmaxf(hi[a], v[a]);
-            }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        lo[a] = wave_min(lo[a]);
-        hi[a] = wave_max(hi[a]);
-        if (lane == 0) {
-            red[a][wave] = lo[a];
-            red[3 + a][wave] = hi[a];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = red[threadIdx.x][0];
-        for (int w = 1; w < MS_THREADS / 64; w++)
-            v = threadIdx.x < 3 ? fminf(v, red[threadIdx.x][w]) : fmaxf(v, red[threadIdx.x][w]);
-        out[threadIdx.x] = v;
-    }
-}
-
-__global__ __launch_bounds__(MS_THREADS) void morton_bbox_kernel(const float *__restrict__ p, int n, float *bbox) {
-    __shared__ float red[6][MS_THREADS / 64];
-    block_box([&](int i, float *v) {
-        v[0] = p[(size_t)i * 3];
-        v[1] = p[(size_t)i * 3 + 1];
-        v[2] = p[(size_t)i * 3 + 2];
-    }, 0, n, bbox, red);
-}
-
-__device__ __forceinline__ unsigned spread10(unsigned v) {   // 10 bits -> every third bit
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
-__global__ __launch_bounds__(MS_THREADS) void morton_key_kernel(const float *__restrict__ p, int n,
-                                                                const float *__restrict__ bbox, unsigned *keys,
-                                                                unsigned *vals) {
-    const int i = blockIdx.x * MS_THREADS + threadIdx.x;
-    if (i >= n) return;
-    unsigned key = 0;
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float v = p[(size_t)i * 3 + a], lo = bbox[a], ext = bbox[3 + a] - lo;
-        ok = ok && fabsf(v) < INFINITY;
-        const float t = ext > 0.f ? (v - lo) / ext : 0.f;
-        const int c = min(1023, max(0, (int)(t * 1024.f)));
-        key |= spread10((unsigned)c) << a;
-    }
-    keys[i] = ok ? key : 0x7fffffffu;
-    vals[i] = (unsigned)i;
-}
-
-__global__ __launch_bounds__(MS_THREADS) void morton_gather_kernel(const float *__restrict__ p, int n,
-                                                                   const unsigned *__restrict__ perm,
-                                                                   float *__restrict__ sorted, int *__restrict__ perm_out,
-                                                                   float *__restrict__ boxes, int tile) {
-    __shared__ float red[6][MS_THREADS / 64];
-    const int begin = blockIdx.x * tile, end = min(n, begin + tile);
-    float scratch6[6];
-    block_box([&](int i, float *v) {
-        const unsigned s = perm[i];
-        v[0] = p[(size_t)s * 3];
-        v[1] = p[(size_t)s * 3 + 1];
-        v[2] = p[(size_t)s * 3 + 2];
-        sorted[(size_t)i * 3] = v[0];
-        sorted[(size_t)i * 3 + 1] = v[1];
-        sorted[(size_t)i * 3 + 2] = v[2];
-        if (perm_out) perm_out[i] = (int)s;
-    }, begin, end, boxes ? boxes + (size_t)blockIdx.x * 6 : scratch6, red);
-}
-
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t sort_temp_bytes(int n) {
-    size_t bytes = 0;
-    unsigned *none = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, none, none, none, none, (size_t)n, 0u, 31u);
-    return bytes;
-}
 
 // ---- sort-tile-recursive order --------------------------------------------------------------------------- //
 constexpr int STR_LEAF = 64;
@@ -260,47 +147,4 @@ extern "C" int zs_str_sort(const float *points, int n, float *sorted, int *perm,
                            dst[pass], pass == 2 ? perm : pout[pass]);
     }
     return zs::check_launch("zs_str_sort") ? 1 : 0;
-}
-
-namespace {
-}  // namespace
-
-extern "C" size_t zs_morton_scratch_bytes(int n) {
-    if (n <= 0) return 0;
-    return 256 + 4 * align256((size_t)n * 4) + align256(sort_temp_bytes(n));
-}
-
-extern "C" int zs_morton_sort(const float *points, int n, float *sorted, int *perm, float *tile_boxes, int tile,
-                              void *scratch, void *stream) {
-    if (n < 0 || (tile_boxes && tile <= 0)) {
-        zs::set_err("zs_morton_sort: bad size (n=%d tile=%d)", n, tile);
-        return 0;
-    }
-    if (n == 0) return 1;
-    if (!points || !sorted || !scratch || points == sorted) {
-        zs::set_err("zs_morton_sort: null or aliased pointer");
-        return 0;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *base = static_cast<char *>(scratch);
-    float *bbox = reinterpret_cast<float *>(base);
-    const size_t arr = align256((size_t)n * 4);
-    unsigned *keys_in = reinterpret_cast<unsigned *>(base + 256);
-    unsigned *keys_out = reinterpret_cast<unsigned *>(base + 256 + arr);
-    unsigned *vals_in = reinterpret_cast<unsigned *>(base + 256 + 2 * arr);
-    unsigned *vals_out = reinterpret_cast<unsigned *>(base + 256 + 3 * arr);
-    void *temp = base + 256 + 4 * arr;
-    size_t temp_bytes = sort_temp_bytes(n);
-    hipLaunchKernelGGL(morton_bbox_kernel, dim3(1), dim3(MS_THREADS), 0, st, points, n, bbox);
-    hipLaunchKernelGGL(morton_key_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, st, points, n, bbox,
-                       keys_in, vals_in);
-    if (rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, 31u, st) !=
-        hipSuccess) {
-        zs::set_err("zs_morton_sort: rocprim::radix_sort_pairs failed");
-        return 0;
-    }
-    const int t = tile_boxes ? tile : 1024;
-    hipLaunchKernelGGL(morton_gather_kernel, dim3((n + t - 1) / t), dim3(MS_THREADS), 0, st, points, n, vals_out, sorted, perm,
-                       tile_boxes, t);
-    return zs::check_launch("zs_morton_sort") ? 1 : 0;
 }

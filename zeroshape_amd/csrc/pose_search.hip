@@ -16,11 +16,11 @@
 //                       staging candidates into LDS (direction 1) - and an epilogue that reduces
 //                       sqrt(d) and the six F-score counters per workgroup in a FIXED order
 //                       (bit-reproducible: the same rotation gives the same bits in any batch).
-//   pose_nn_cull_kernel the same scan over MORTON-SORTED clouds (csrc/morton_sort.hip) that skips the
-//                       (run of 64 queries, sub-tile of 64 candidates) blocks whose bounding boxes are
+//   pose_nn_soa_kernel  the same scan over SPATIALLY SORTED clouds (zs_str_sort, csrc/morton_sort.hip) that skips
+//                       the (run of 64 queries, sub-tile of 64 candidates) blocks whose bounding boxes are
 //                       farther apart than the worst nearest neighbour the run has found so far, tiles
 //                       visited nearest first: the same minima - a skipped candidate is provably not
-//                       closer - from a fraction of the pairs (round 3; the default).
+//                       closer - from a fraction of the pairs (mode 2; the default).
 //   pose_finish_kernel  per batch: sums the partials in order, acc / comp / cd / F-score per
 //                       rotation, lexicographic (cd, rotation index) winner, merged into the running
 //                       best record on the device.
@@ -28,7 +28,6 @@
 // running best and returns if the batch cannot win: the host enqueues all batches without a
 // single synchronisation and reads the record once at the end.
 #include "zs_common.h"
-#include "zs_point_grid.h"
 #include "../../include/zeroshape_hip.h"
 
 #include <math.h>
@@ -179,9 +178,45 @@ __device__ __forceinline__ bool stage_skips(int stage, int bx, const int *__rest
     return mode == 1 ? (bx >= end && !merged) : merged;
 }
 
+// The epilogue of both scans: the sum of sqrt(d) and the six threshold counters of this workgroup's queries, reduced in a
+// FIXED order (lanes by xor-shuffle, then waves 0..3), written as the workgroup's row of `partial`.  `red`: the kernel's LDS.
+__device__ __forceinline__ void write_partial(const float (&bestd)[PS_Q], int q_base, int nq,
+                                              const float *__restrict__ thresholds, float (&red)[PS_PART][PS_THREADS / 64],
+                                              float *__restrict__ row) {
+    float v[PS_PART];
+#pragma unroll
+    for (int i = 0; i < PS_PART; i++) v[i] = 0.f;
+    float thr[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) thr[i] = thresholds[i];
+#pragma unroll
+    for (int q = 0; q < PS_Q; q++) {
+        const int j = q_base + q * PS_THREADS + threadIdx.x;
+        if (j < nq) {
+            const float s = sqrtf(bestd[q]);
+            v[0] += s;
+#pragma unroll
+            for (int i = 0; i < 6; i++) v[1 + i] += s < thr[i] ? 1.f : 0.f;   // counts <= 512: exact in fp32
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 7; i++) v[i] = wave_sum(v[i]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int i = 0; i < 7; i++) red[i][wave] = v[i];
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        float s = red[threadIdx.x][0];
+        for (int w = 1; w < PS_THREADS / 64; w++) s += red[threadIdx.x][w];
+        row[threadIdx.x] = s;
+    }
+}
+
 // grid (ceil(max(n, m) / (256 Q)), rotations in the batch, 2)
-// The launch covers query blocks x_begin .. x_begin + gridDim.x - 1 of blocks_x; `dead` (nullable): rotations that the
-// probe (block 0, see zs_pose_search_batch) has already shown to lose - they are skipped.
+// The launch covers query blocks x_begin .. x_begin + gridDim.x - 1 of blocks_x; `dead` (nullable): rotations whose first
+// stages (search_batch below) have already shown them to lose - they are skipped.
+// Kept as nn="brute": the GPU tests prove the culled scan against it, and the bench line's all_pairs_kernel_* keys time it.
 __global__ __launch_bounds__(PS_THREADS) void pose_nn_kernel(
     const float *__restrict__ pred, int n, const float *__restrict__ gt, int m,
     const float *__restrict__ stats, const float *__restrict__ thresholds, float *__restrict__ partial,
@@ -258,39 +293,11 @@ __global__ __launch_bounds__(PS_THREADS) void pose_nn_kernel(
             cx = nx; cy = ny; cz = nz;
         }
     }
-    // epilogue: sum of sqrt(d) and the threshold counters of this workgroup's queries, fixed order
-    float v[PS_PART];
-#pragma unroll
-    for (int i = 0; i < PS_PART; i++) v[i] = 0.f;
-    float thr[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) thr[i] = thresholds[i];
-#pragma unroll
-    for (int q = 0; q < PS_Q; q++) {
-        const int j = q_base + q * PS_THREADS + threadIdx.x;
-        if (j < nq) {
-            const float s = sqrtf(bestd[q]);
-            v[0] += s;
-#pragma unroll
-            for (int i = 0; i < 6; i++) v[1 + i] += s < thr[i] ? 1.f : 0.f;   // counts <= 512: exact in fp32
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) v[i] = wave_sum(v[i]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < 7; i++) red[i][wave] = v[i];
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        float s = red[threadIdx.x][0];
-        for (int w = 1; w < PS_THREADS / 64; w++) s += red[threadIdx.x][w];
-        partial[(((size_t)rot * 2 + dir) * blocks_x + bx) * PS_PART + threadIdx.x] = s;
-    }
+    write_partial(bestd, q_base, nq, thresholds, red, partial + (((size_t)rot * 2 + dir) * blocks_x + bx) * PS_PART);
 }
 
 // ---- the same scan with box culling (round 3) --------------------------------------------- //
-// Both clouds arrive Morton-sorted in their own frames (zs_morton_sort): 64 consecutive points ("sub-tile") are a
+// Both clouds arrive spatially sorted in their own frames (zs_str_sort): 64 consecutive points ("sub-tile") are a
 // compact patch, also after the rotation.  pose_pack_kernel writes a cloud - the ground truth once per search, the
 // rotated + normalised prediction once per rotation of the batch - as a PACK:
 //     [sub-tile][x | y | z][64] coordinates (+inf padded)   |   [sub-tile] lo[3], hi[3] exact box   |   [tile of 16] box
@@ -487,14 +494,6 @@ __device__ __forceinline__ void scan_subtile(const float *__restrict__ c, const 
     Chunk8 a, b;
     a.request(c);
     a.arrived();
-#ifdef ZS_POSE_EXP_NOLOAD       // timing experiment (wrong results): the arithmetic of a sub-tile on its first chunk only
-#pragma unroll
-    for (int k = 0; k < PS_SUB; k += 8) {
-        scan_chunk<D0, D1>(a, qx, qy, qz, bestd);
-        asm volatile("" : "+s"(a.x), "+s"(a.y), "+s"(a.z));
-    }
-    return;
-#endif
 #pragma unroll
     for (int k = 0; k < PS_SUB; k += 16) {
         b.request_before(c + k + 8, a);
@@ -507,7 +506,8 @@ __device__ __forceinline__ void scan_subtile(const float *__restrict__ c, const 
 }
 
 // grid and partial layout of pose_nn_kernel.  pred_packs: one pack per rotation of the batch (pose_pack_kernel);
-// gt_pack: the ground truth's.  CULL = false scans every sub-tile in index order (the all-pairs scan on packs).
+// gt_pack: the ground truth's.  CULL = false scans every sub-tile in index order (the all-pairs scan on packs): kept as
+// nn="pairs", the same kernel without the skipping, which the GPU tests prove the culled scan against.
 template <bool CULL>
 __global__ __launch_bounds__(PS_THREADS) void pose_nn_soa_kernel(
     const float *__restrict__ pred_packs, size_t pack_stride, int n, const float *__restrict__ gt_pack, int m,
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_nn_soa_kernel(
     const float *C = dir == 0 ? gt_pack : ppack;
     const int ncs = pack_subs(nc);
     const float *Csub = C + (size_t)ncs * PS_SUB_FLOATS, *Ctile = Csub + (size_t)ncs * 8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     float qx[PS_Q], qy[PS_Q], qz[PS_Q], bestd[PS_Q];
     float rlo[PS_Q][3], rhi[PS_Q][3];       // boxes of this wave's two runs of 64 queries (wave-uniform)
 #pragma unroll
@@ -599,31 +599,18 @@ __global__ __launch_bounds__(PS_THREADS) void pose_nn_soa_kernel(
                 cand = g0 * PS_SKIP <= w0 || g1 * PS_SKIP <= w1;
                 gm = fminf(g0, g1);
             }
-#ifdef ZS_POSE_ITER_MIN   // rounds 3-5 (A/B): one wave-wide minimum per candidate
-            while (__ballot(cand) != 0ull) {
-                int sl;
-                if ((stage >> 30) & 1) {           // measurement (ZS_POSE_LANE_ORDER=1): candidates in index order
-                    sl = __builtin_ctzll(__ballot(cand));
-                } else {
-                    const float near_sub = wave_minf(cand ? gm : INFINITY);
-                    sl = __builtin_ctzll(__ballot(cand && gm == near_sub));
-                }
-                cand = cand && lane != sl;
-#else
             // The order is fixed when the tile is entered, so it is computed once: a candidate's rank among the tile's candidates
             // by (gap, lane) - the lane index rides in the four low mantissa bits of the non-negative gap, whose bit pattern orders
             // like an unsigned integer - from sixteen uniform compares, instead of one wave-wide minimum (~19 VALU instructions)
             // per candidate.  The order only decides how soon the running minima shrink, never a result.
             unsigned key = 0xffffffffu;
-            if (cand) key = ((stage >> 30) & 1) ? (unsigned)lane     // measurement (ZS_POSE_LANE_ORDER=1): index order
-                                                : ((__builtin_bit_cast(unsigned, gm) & ~15u) | (unsigned)lane);
+            if (cand) key = (__builtin_bit_cast(unsigned, gm) & ~15u) | (unsigned)lane;
             int rank = 0;
 #pragma unroll
             for (int j = 0; j < PS_NSUB; j++) rank += (unsigned)__builtin_amdgcn_readlane((int)key, j) < key ? 1 : 0;
             const int ncand = __popcll(__ballot(cand));
             for (int r = 0; r < ncand; r++) {
                 const int sl = __builtin_ctzll(__ballot(cand && rank == r));
-#endif
                 const float lo[3] = {lane_f(slo[0], sl), lane_f(slo[1], sl), lane_f(slo[2], sl)};
                 const float hi[3] = {lane_f(shi[0], sl), lane_f(shi[1], sl), lane_f(shi[2], sl)};
                 // both runs' point-to-box distances in packed form (the same operations per lane as point_gap2)
@@ -650,34 +637,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_nn_soa_kernel(
     }
 #endif
 #undef ZS_COUNT
-    // epilogue: pose_nn_kernel's, statement for statement
-    float v[PS_PART];
-#pragma unroll
-    for (int i = 0; i < PS_PART; i++) v[i] = 0.f;
-    float thr[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) thr[i] = thresholds[i];
-#pragma unroll
-    for (int q = 0; q < PS_Q; q++) {
-        const int j = q_base + q * PS_THREADS + threadIdx.x;
-        if (j < nq) {
-            const float sq = sqrtf(bestd[q]);
-            v[0] += sq;
-#pragma unroll
-            for (int i = 0; i < 6; i++) v[1 + i] += sq < thr[i] ? 1.f : 0.f;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) v[i] = wave_sum(v[i]);
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < 7; i++) red[i][wave] = v[i];
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        float sum = red[threadIdx.x][0];
-        for (int w = 1; w < PS_THREADS / 64; w++) sum += red[threadIdx.x][w];
-        partial[(((size_t)rot * 2 + dir) * blocks_x + bx) * PS_PART + threadIdx.x] = sum;
-    }
+    write_partial(bestd, q_base, nq, thresholds, red, partial + (((size_t)rot * 2 + dir) * blocks_x + bx) * PS_PART);
 }
 
 // A rotation whose first `done` query blocks alone already give (s0 / n + s1 / m) / 2 > best cannot win: acc >= s0 / n and
@@ -710,99 +670,6 @@ __global__ __launch_bounds__(PS_THREADS) void pose_kill_kernel(const float *__re
     }
     __syncthreads();
     if (decide_merge && threadIdx.x == 0) dead[PS_MERGE_SLOT] = 4 * killed <= count ? 1 : 0;
-}
-
-// ---- the same search through uniform grids (csrc/zs_point_grid.h): ~10^2 instead of 10^4 distance evaluations per
-// query, the same minima bit for bit (a skipped candidate provably has a strictly larger d) ------------------------ //
-// The ground truth is binned once per search, normalize_pc(R p) once per rotation; queries and the per-workgroup
-// partial sums are laid out exactly as in pose_nn_kernel, so pose_finish_kernel forms the same sums in the same order.
-__global__ __launch_bounds__(zs::pgrid::BUILD_THREADS) void pose_gt_grid_kernel(const float *__restrict__ gt, int m,
-                                                                                float *__restrict__ slot) {
-    using namespace zs::pgrid;
-    __shared__ int cnt[GRID_MAX_CELLS];
-    __shared__ float red[6][BUILD_THREADS / 64];
-    __shared__ int wsum[BUILD_THREADS / 64];
-    point_grid_build([&](int i, float &x, float &y, float &z) {
-        x = gt[(size_t)i * 3];
-        y = gt[(size_t)i * 3 + 1];
-        z = gt[(size_t)i * 3 + 2];
-    }, m, slot, cnt, red, wsum);
-}
-
-__global__ __launch_bounds__(zs::pgrid::BUILD_THREADS) void pose_pred_grid_kernel(
-    const float *__restrict__ pred, int n, const float *__restrict__ stats, float *__restrict__ slots, size_t slot_words_n,
-    const float *__restrict__ lower_bound, const float *__restrict__ best) {
-    using namespace zs::pgrid;
-    if (batch_pruned(lower_bound, best)) return;
-    __shared__ int cnt[GRID_MAX_CELLS];
-    __shared__ float red[6][BUILD_THREADS / 64];
-    __shared__ int wsum[BUILD_THREADS / 64];
-    const int rot = blockIdx.x;
-    Xform t;
-    t.load(stats + (size_t)rot * PS_STAT);
-    point_grid_build([&](int i, float &x, float &y, float &z) {
-        t.apply(pred[(size_t)i * 3], pred[(size_t)i * 3 + 1], pred[(size_t)i * 3 + 2], x, y, z);
-    }, n, slots + (size_t)rot * slot_words_n, cnt, red, wsum);
-}
-
-// grid (ceil(max(n, m) / (256 Q)), rotations in the batch, 2): pose_nn_kernel with the scan replaced by the grid walk
-__global__ __launch_bounds__(PS_THREADS) void pose_nn_grid_kernel(
-    const float *__restrict__ pred, int n, const float *__restrict__ gt, int m, const float *__restrict__ stats,
-    const float *__restrict__ thresholds, float *__restrict__ partial, const float *__restrict__ gt_slot,
-    const float *__restrict__ pred_slots, size_t slot_words_n, const float *__restrict__ lower_bound,
-    const float *__restrict__ best) {
-    if (batch_pruned(lower_bound, best)) return;
-    __shared__ float red[PS_PART][PS_THREADS / 64];
-    const int dir = blockIdx.z, rot = blockIdx.y;
-    const int nq = dir == 0 ? n : m;      // queries
-    const int q_base = blockIdx.x * (PS_THREADS * PS_Q);
-    if (q_base >= nq) return;
-    Xform t;
-    t.load(stats + (size_t)rot * PS_STAT);
-    const float *slot = dir == 0 ? gt_slot : pred_slots + (size_t)rot * slot_words_n;
-    float bestd[PS_Q];
-#pragma unroll
-    for (int q = 0; q < PS_Q; q++) {
-        int j = q_base + q * PS_THREADS + threadIdx.x;
-        j = j < nq ? j : nq - 1;
-        float qx, qy, qz;
-        if (dir == 0) {
-            t.apply(pred[(size_t)j * 3], pred[(size_t)j * 3 + 1], pred[(size_t)j * 3 + 2], qx, qy, qz);
-        } else {
-            qx = gt[(size_t)j * 3]; qy = gt[(size_t)j * 3 + 1]; qz = gt[(size_t)j * 3 + 2];
-        }
-        int who;
-        zs::pgrid::point_grid_nearest(slot, qx, qy, qz, bestd[q], who);
-    }
-    // epilogue: pose_nn_kernel's, statement for statement
-    float v[PS_PART];
-#pragma unroll
-    for (int i = 0; i < PS_PART; i++) v[i] = 0.f;
-    float thr[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) thr[i] = thresholds[i];
-#pragma unroll
-    for (int q = 0; q < PS_Q; q++) {
-        const int j = q_base + q * PS_THREADS + threadIdx.x;
-        if (j < nq) {
-            const float s = sqrtf(bestd[q]);
-            v[0] += s;
-#pragma unroll
-            for (int i = 0; i < 6; i++) v[1 + i] += s < thr[i] ? 1.f : 0.f;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) v[i] = wave_sum(v[i]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < 7; i++) red[i][wave] = v[i];
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        float s = red[threadIdx.x][0];
-        for (int w = 1; w < PS_THREADS / 64; w++) s += red[threadIdx.x][w];
-        partial[(((size_t)rot * 2 + dir) * gridDim.x + blockIdx.x) * PS_PART + threadIdx.x] = s;
-    }
 }
 
 // F-score of utils/eval_3D.py:215-231 from the two hit fractions
@@ -919,14 +786,14 @@ int blocks_x_of(int n, int m) {
     return (nmax + PS_THREADS * PS_Q - 1) / (PS_THREADS * PS_Q);
 }
 
+// stats | partials | dead flags: the part of the scratch in front of the batch's packs
+size_t scratch_head_bytes(int n, int m, int count) {
+    return ((size_t)count * PS_STAT + (size_t)count * 2 * blocks_x_of(n, m) * PS_PART + (size_t)PS_DEAD_INTS) * sizeof(float);
+}
+
 }  // namespace
 
 extern "C" int zs_pose_max_batch(void) { return PS_THREADS; }
-
-extern "C" size_t zs_pose_scratch_bytes(int n, int m, int count) {
-    if (n <= 0 || m <= 0 || count <= 0) return 0;
-    return ((size_t)count * PS_STAT + (size_t)count * 2 * blocks_x_of(n, m) * PS_PART + (size_t)PS_DEAD_INTS) * sizeof(float);
-}
 
 extern "C" size_t zs_pose_best_bytes(void) { return PS_BEST * sizeof(float); }
 
@@ -951,27 +818,27 @@ extern "C" int zs_pose_best_init(float *best, void *stream) {
 
 namespace {
 // pred: the cloud in its caller's order (statistics: the mean's double sum depends on the order, and zs_pose_apply
-// runs on this order); pred_nn / gt_nn: the clouds the scans read (the same, or Morton-sorted).  mode 0: pose_nn_kernel
+// runs on this order); pred_nn / gt_nn: the clouds the scans read (spatially sorted).  mode 0: pose_nn_kernel
 // (all pairs, candidates staged in LDS); 1 / 2: pose_nn_soa_kernel on packs, all pairs / box-culled.
 int search_batch(const float *pred, const float *pred_nn, int n, const float *gt_nn, const float *gt_pack, int m, int mode,
                  const float *rotations, const int *order, int count, int index_offset, const float *lower_bound,
                  const float *thresholds6, float *best, void *scratch, void *stream) {
     if (n < 0 || m < 0 || count < 0) {
-        zs::set_err("zs_pose_search_batch: negative size (n=%d m=%d count=%d)", n, m, count);
+        zs::set_err("zs_pose_search_batch_sorted: negative size (n=%d m=%d count=%d)", n, m, count);
         return 0;
     }
     if (count == 0) return 1;
     if (n == 0 || m == 0) {
-        zs::set_err("zs_pose_search_batch: empty cloud (n=%d m=%d)", n, m);
+        zs::set_err("zs_pose_search_batch_sorted: empty cloud (n=%d m=%d)", n, m);
         return 0;
     }
     if (count > PS_THREADS) {
-        zs::set_err("zs_pose_search_batch: %d rotations per batch exceed %d", count, PS_THREADS);
+        zs::set_err("zs_pose_search_batch_sorted: %d rotations per batch exceed %d", count, PS_THREADS);
         return 0;
     }
     if (!pred || !pred_nn || !rotations || !thresholds6 || !best || !scratch || (mode == 0 ? !gt_nn : !gt_pack) || mode < 0 ||
         mode > 2) {
-        zs::set_err("zs_pose_search_batch: null pointer or bad mode");
+        zs::set_err("zs_pose_search_batch_sorted: null pointer or bad mode");
         return 0;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -986,7 +853,7 @@ int search_batch(const float *pred, const float *pred_nn, int n, const float *gt
     // after 5-15 % of its queries.
     int *dead = reinterpret_cast<int *>(partial + (size_t)count * 2 * bx * PS_PART);
     if (hipMemsetAsync(dead, 0, (size_t)PS_DEAD_INTS * sizeof(int), st) != hipSuccess) {
-        zs::set_err("zs_pose_search_batch: hipMemsetAsync failed");
+        zs::set_err("zs_pose_search_batch_sorted: hipMemsetAsync failed");
         return 0;
     }
     float *packs = reinterpret_cast<float *>(dead + PS_DEAD_INTS);
@@ -994,11 +861,10 @@ int search_batch(const float *pred, const float *pred_nn, int n, const float *gt
     if (mode != 0)
         hipLaunchKernelGGL(pose_pack_kernel, dim3(pack_subs(n) / PS_NSUB, count), dim3(PS_TILE), 0, st, pred_nn, n,
                            static_cast<const float *>(stats), packs, pstride, lower_bound, static_cast<const float *>(best));
-    // ZS_POSE_STAGES="a,b,c" moves the stage boundaries (measurement; "0,0,0" = one stage: no staged drop); ZS_POSE_MERGE=0
-    // keeps every stage to its own blocks.  Defaults from tools/pose_stages.py (6,912 rotations, 10k x 10k points, batch 256):
+    // ZS_POSE_STAGES="a,b,c" moves the stage boundaries (measurement, tools/pose_stages.py; "0,0,0" = one stage: no staged
+    // drop).  Defaults from tools/pose_stages.py (6,912 rotations, 10k x 10k points, batch 256):
     // stages 1,3,7: unalignable 41.3 / alignable 2.86 ms; 2,6,6: 39.5 / 2.62; one stage: 35.4 / 3.58.
     static const char *stage_env = getenv("ZS_POSE_STAGES");
-    static const bool merge_on = getenv("ZS_POSE_MERGE") == nullptr || atoi(getenv("ZS_POSE_MERGE")) != 0;
     int stage_end[4] = {2, 6, 6, bx};
     if (stage_env) {
         int a = 1, b = 3, c = 7;
@@ -1009,10 +875,9 @@ int search_batch(const float *pred, const float *pred_nn, int n, const float *gt
         const int hi = stage_end[sidx] < bx ? stage_end[sidx] : bx;
         if (hi <= lo) continue;
         // the second launch spans every remaining block (it scans them all when the first kill merged the stages)
-        const int smode = !merge_on || launched == 0 ? 0 : launched == 1 ? 1 : 2;
+        const int smode = launched == 0 ? 0 : launched == 1 ? 1 : 2;
         const int span = smode == 1 ? bx - lo : hi - lo;
-        static const int lane_order = getenv("ZS_POSE_LANE_ORDER") && atoi(getenv("ZS_POSE_LANE_ORDER")) ? 1 : 0;
-        const int stage = (lane_order << 30) | (smode << 24) | hi;
+        const int stage = (smode << 24) | hi;
         const dim3 grid(span, count, 2);
         if (mode == 2)
             hipLaunchKernelGGL(pose_nn_soa_kernel<true>, grid, dim3(PS_THREADS), 0, st, static_cast<const float *>(packs), pstride,
@@ -1027,23 +892,15 @@ int search_batch(const float *pred, const float *pred_nn, int n, const float *gt
                                lower_bound, best, lo, bx, static_cast<const int *>(dead), stage);
         if (hi < bx)
             hipLaunchKernelGGL(pose_kill_kernel, dim3(1), dim3(PS_THREADS), 0, st, partial, count, n, m, bx, hi, best, dead,
-                               lower_bound, merge_on && launched == 0 ? 1 : 0);
+                               lower_bound, launched == 0 ? 1 : 0);
         lo = hi;
         launched++;
     }
     hipLaunchKernelGGL(pose_finish_kernel, dim3(1), dim3(PS_THREADS), 0, st, partial, count, n, m, bx, order,
                        index_offset, best, lower_bound, static_cast<const int *>(dead));
-    return zs::check_launch("zs_pose_search_batch") ? 1 : 0;
+    return zs::check_launch("zs_pose_search_batch_sorted") ? 1 : 0;
 }
 }  // namespace
-
-extern "C" int zs_pose_search_batch(const float *pred, int n, const float *gt_normalized, int m,
-                                    const float *rotations, const int *order, int count, int index_offset,
-                                    const float *lower_bound, const float *thresholds6, float *best,
-                                    void *scratch, void *stream) {
-    return search_batch(pred, pred, n, gt_normalized, nullptr, m, 0, rotations, order, count, index_offset, lower_bound,
-                        thresholds6, best, scratch, stream);
-}
 
 #ifdef ZS_POSE_COUNT
 extern "C" int zs_pose_debug_counters(unsigned long long *out2, int reset) {
@@ -1060,7 +917,7 @@ extern "C" size_t zs_pose_pack_bytes(int points) { return points > 0 ? pack_floa
 
 extern "C" size_t zs_pose_sorted_scratch_bytes(int n, int m, int count) {
     if (n <= 0 || m <= 0 || count <= 0) return 0;
-    return zs_pose_scratch_bytes(n, m, count) + (size_t)count * zs_pose_pack_bytes(n);
+    return scratch_head_bytes(n, m, count) + (size_t)count * zs_pose_pack_bytes(n);
 }
 
 extern "C" int zs_pose_pack(const float *sorted_points, int points, float *pack, void *stream) {
@@ -1080,57 +937,6 @@ extern "C" int zs_pose_search_batch_sorted(const float *pred, const float *pred_
                                            void *scratch, int mode, void *stream) {
     return search_batch(pred, pred_sorted, n, gt_sorted, gt_pack, m, mode, rotations, order, count, index_offset, lower_bound,
                         thresholds6, best, scratch, stream);
-}
-
-extern "C" size_t zs_pose_grid_bytes(int n, int m, int count) {
-    if (n <= 0 || m <= 0 || count <= 0) return 0;
-    return (zs::pgrid::slot_words(m) + (size_t)count * zs::pgrid::slot_words(n)) * sizeof(float);
-}
-
-extern "C" int zs_pose_gt_grid(const float *gt_normalized, int m, void *grids, void *stream) {
-    if (m <= 0 || !gt_normalized || !grids || (reinterpret_cast<uintptr_t>(grids) & 15)) {
-        zs::set_err("zs_pose_gt_grid: bad arguments (m=%d; 16-byte aligned buffer)", m);
-        return 0;
-    }
-    hipLaunchKernelGGL(pose_gt_grid_kernel, dim3(1), dim3(zs::pgrid::BUILD_THREADS), 0, static_cast<hipStream_t>(stream),
-                       gt_normalized, m, static_cast<float *>(grids));
-    return zs::check_launch("zs_pose_gt_grid") ? 1 : 0;
-}
-
-extern "C" int zs_pose_search_batch_grid(const float *pred, int n, const float *gt_normalized, int m,
-                                         const float *rotations, const int *order, int count, int index_offset,
-                                         const float *lower_bound, const float *thresholds6, float *best,
-                                         void *scratch, void *grids, const float *pred_stats, void *stream) {
-    if (n <= 0 || m <= 0 || count < 0) {
-        zs::set_err("zs_pose_search_batch_grid: bad size (n=%d m=%d count=%d)", n, m, count);
-        return 0;
-    }
-    if (count == 0) return 1;
-    if (count > PS_THREADS) {
-        zs::set_err("zs_pose_search_batch_grid: %d rotations per batch exceed %d", count, PS_THREADS);
-        return 0;
-    }
-    if (!pred || !gt_normalized || !rotations || !thresholds6 || !best || !scratch || !grids ||
-        (reinterpret_cast<uintptr_t>(grids) & 15)) {
-        zs::set_err("zs_pose_search_batch_grid: null or misaligned pointer");
-        return 0;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *stats = static_cast<float *>(scratch);
-    float *partial = stats + (size_t)count * PS_STAT;
-    float *gt_slot = static_cast<float *>(grids);
-    float *pred_slots = gt_slot + zs::pgrid::slot_words(m);
-    const size_t sw = zs::pgrid::slot_words(n);
-    const int bx = blocks_x_of(n, m);
-    hipLaunchKernelGGL(pose_stats_kernel, dim3(count), dim3(PS_THREADS), 0, st, pred_stats ? pred_stats : pred, (size_t)0, n,
-                       rotations, order, stats, lower_bound, best);
-    hipLaunchKernelGGL(pose_pred_grid_kernel, dim3(count), dim3(zs::pgrid::BUILD_THREADS), 0, st, pred, n, stats, pred_slots,
-                       sw, lower_bound, best);
-    hipLaunchKernelGGL(pose_nn_grid_kernel, dim3(bx, count, 2), dim3(PS_THREADS), 0, st, pred, n, gt_normalized, m, stats,
-                       thresholds6, partial, gt_slot, pred_slots, sw, lower_bound, best);
-    hipLaunchKernelGGL(pose_finish_kernel, dim3(1), dim3(PS_THREADS), 0, st, partial, count, n, m, bx, order,
-                       index_offset, best, lower_bound, static_cast<const int *>(nullptr));
-    return zs::check_launch("zs_pose_search_batch_grid") ? 1 : 0;
 }
 
 extern "C" int zs_pose_apply(const float *pred, int n, const float *rotations, const int *index, float *out,

@@ -325,26 +325,19 @@ def _bf_lower_bounds(pc_pred, pc_gt_n, rotations):
 _POSE_MODES = {"brute": 0, "pairs": 1, "cull": 2}     # zs_pose_search_batch_sorted: mode
 
 
-def _spatially_sorted(points, order=None):
-    """points [n,3] (GPU, fp32) -> the same points in an order whose runs of 64 are compact boxes: "str" (default;
-    sort-tile-recursive, zs_str_sort) or "morton" (Z-order curve, zs_morton_sort); ZS_POSE_ORDER overrides."""
+def _spatially_sorted(points):
+    """points [n,3] (GPU, fp32) -> the same points in an order whose runs of 64 are compact boxes (sort-tile-recursive,
+    zs_str_sort)."""
     from .. import _lib
     lib = _lib.load()
-    order = (order or os.environ.get("ZS_POSE_ORDER", "str")).lower()
     pts = points.contiguous()
     n = pts.shape[0]
     out = torch.empty_like(pts)
     st = _lib.current_stream_ptr(pts.device)
     with torch.cuda.device(pts.device):
-        if order == "str":
-            scratch = torch.empty(max(1, lib.zs_str_scratch_bytes(n) // 4), dtype=torch.float32, device=pts.device)
-            rc = lib.zs_str_sort(_lib.ptr(pts), n, _lib.ptr(out), None, _lib.ptr(scratch), st)
-        elif order == "morton":
-            scratch = torch.empty(max(1, lib.zs_morton_scratch_bytes(n) // 4), dtype=torch.float32, device=pts.device)
-            rc = lib.zs_morton_sort(_lib.ptr(pts), n, _lib.ptr(out), None, None, 0, _lib.ptr(scratch), st)
-        else:
-            raise ValueError("point order must be 'str' or 'morton', got %r" % (order,))
-    _lib.check(rc, "zs_%s_sort" % order)
+        scratch = torch.empty(max(1, lib.zs_str_scratch_bytes(n) // 4), dtype=torch.float32, device=pts.device)
+        rc = lib.zs_str_sort(_lib.ptr(pts), n, _lib.ptr(out), None, _lib.ptr(scratch), st)
+    _lib.check(rc, "zs_str_sort")
     return out
 
 
@@ -380,19 +373,14 @@ def brute_force_search(pc_pred, pc_gt, f_thresholds=[0.005, 0.01, 0.02, 0.05, 0.
     falls, so every batch the host skips is one the device would have skipped.  The winner is the lexicographic minimum of
     (cd, rotation index) over the evaluated rotations; pruned ones are strictly worse, so this IS
     the first strict minimum of the full scan.
-    ``nn`` picks the nearest-neighbour kernels of the exact evaluations (ZS_POSE_NN overrides the default).  Both
-    clouds are first put into a spatial order (sort-tile-recursive, zs_str_sort; once per search), so that 64
-    consecutive points fill a compact box - also after the rotation; the statistics of normalize_pc and
-    the returned clouds keep the caller's order.  "cull" (default, round 3) reads candidates 64 at a time
-    through the scalar cache and skips every block whose bounding box is farther from a query than its current
-    nearest neighbour, nearest tiles first; "pairs" is the same kernel without the skipping, "brute" round 2's
-    LDS-staged scan of every pair of the same sorted clouds; "grid" walks uniform grids - the ground
-    truth binned once per search, the rotated prediction once per rotation.  The records are bit-identical
-    (tests/test_gpu_chamfer.py): every query ends with the same minimum and the sums keep their fixed order.  The
-    grid walk wins 3.6x on clouds that already lie on each other (the Chamfer call of the final metrics), but most
-    of the 6,912 rotations do NOT, their queries walk many rings (divergent lanes), and the whole search is
-    slower than the plain scan (round 2: 1,139 vs 154 ms exhaustive) - the culled scan keeps the regular
-    wave-wide inner loop and drops whole blocks instead.
+    ``nn`` picks the nearest-neighbour kernels of the exact evaluations: "cull" (None: the default), "pairs" or "brute";
+    anything else raises ValueError.  Both clouds are first put into a spatial order (sort-tile-recursive, zs_str_sort;
+    once per search), so that 64 consecutive points fill a compact box - also after the rotation; the statistics of
+    normalize_pc and the returned clouds keep the caller's order.  "cull" reads candidates 64 at a time through the
+    scalar cache and skips every block whose bounding box is farther from a query than its current nearest neighbour,
+    nearest tiles first; "pairs" is the same kernel without the skipping, "brute" an LDS-staged scan of every pair of the
+    same sorted clouds - the two references the tests prove "cull" against.  The records are bit-identical
+    (tests/test_gpu_chamfer.py): every query ends with the same minimum and the sums keep their fixed order.
     ``rot_slice=(start, stop)`` restricts the scan to a contiguous index range; ``return_index`` appends the
     winning global rotation index and its cd (one host read of the 64-byte record).
     ``rot_shard=(rank, world)`` is the multi-GPU form (every rank of ``group`` calls with the
@@ -403,6 +391,9 @@ def brute_force_search(pc_pred, pc_gt, f_thresholds=[0.005, 0.01, 0.02, 0.05, 0.
     lexicographic (cd, index) minimum taken on the device - the same record, bit for bit, as the single-rank scan
     (a rotation's record does not depend on the batch it was evaluated in)."""
     from .. import _lib
+    nn = "cull" if nn is None else nn
+    if nn not in _POSE_MODES:
+        raise ValueError("nn must be 'cull', 'pairs' or 'brute', got %r" % (nn,))
     lib = _lib.load()
     if len(f_thresholds) > 6:
         raise ValueError("the fused pose search carries six F-score thresholds (options/shape.yaml:54)")
@@ -435,42 +426,28 @@ def brute_force_search(pc_pred, pc_gt, f_thresholds=[0.005, 0.01, 0.02, 0.05, 0.
         K = int(order.numel())
     thr = _threshold_tensor(f_thresholds, dev, pad_to=6)
     best = torch.empty(lib.zs_pose_best_bytes() // 4, dtype=torch.float32, device=dev)
-    scratch = torch.empty(lib.zs_pose_scratch_bytes(n, m, max(1, min(batch_size, K))) // 4, dtype=torch.float32, device=dev)
-    nn = (nn or os.environ.get("ZS_POSE_NN", "cull")).lower()
-    if nn not in ("grid", "brute", "cull", "pairs"):
-        raise ValueError("nn must be 'cull', 'pairs', 'grid' or 'brute', got %r" % (nn,))
     pred_s, gt_s = _spatially_sorted(pred), _spatially_sorted(pc_gt[0])
-    gt_pack = None
-    if nn != "grid":
-        gt_pack = torch.empty(lib.zs_pose_pack_bytes(m) // 4, dtype=torch.float32, device=dev)
-        scratch = torch.empty(lib.zs_pose_sorted_scratch_bytes(n, m, max(1, min(batch_size, K))) // 4, dtype=torch.float32,
-                              device=dev)
-    grids = None
-    if nn == "grid":
-        grids = torch.empty(lib.zs_pose_grid_bytes(n, m, max(1, min(batch_size, K))) // 4, dtype=torch.float32, device=dev)
+    gt_pack = torch.empty(lib.zs_pose_pack_bytes(m) // 4, dtype=torch.float32, device=dev)
+    scratch = torch.empty(lib.zs_pose_sorted_scratch_bytes(n, m, max(1, min(batch_size, K))) // 4, dtype=torch.float32,
+                          device=dev)
     st = _lib.current_stream_ptr(dev)
     rot_base = rotations.data_ptr() + 36 * start
 
     def launch(rot_ptr, order_ptr, count, offset, lb_ptr):
-        if grids is None:
-            return lib.zs_pose_search_batch_sorted(_lib.ptr(pred), _lib.ptr(pred_s), n, _lib.ptr(gt_s), _lib.ptr(gt_pack), m,
-                                                   rot_ptr, order_ptr, count, offset, lb_ptr, _lib.ptr(thr), _lib.ptr(best),
-                                                   _lib.ptr(scratch), _POSE_MODES[nn], st)
-        return lib.zs_pose_search_batch_grid(_lib.ptr(pred_s), n, _lib.ptr(gt_s), m, rot_ptr, order_ptr, count, offset, lb_ptr,
-                                             _lib.ptr(thr), _lib.ptr(best), _lib.ptr(scratch), _lib.ptr(grids),
-                                             _lib.ptr(pred), st)
+        return lib.zs_pose_search_batch_sorted(_lib.ptr(pred), _lib.ptr(pred_s), n, _lib.ptr(gt_s), _lib.ptr(gt_pack), m,
+                                               rot_ptr, order_ptr, count, offset, lb_ptr, _lib.ptr(thr), _lib.ptr(best),
+                                               _lib.ptr(scratch), _POSE_MODES[nn], st)
 
     with torch.cuda.device(dev):
         _lib.check(lib.zs_pose_best_init(_lib.ptr(best), st), "zs_pose_best_init")
-        if grids is not None:
-            _lib.check(lib.zs_pose_gt_grid(_lib.ptr(gt_s), m, _lib.ptr(grids), st), "zs_pose_gt_grid")
-        else:
-            _lib.check(lib.zs_pose_pack(_lib.ptr(gt_s), m, _lib.ptr(gt_pack), st), "zs_pose_pack")
+        _lib.check(lib.zs_pose_pack(_lib.ptr(gt_s), m, _lib.ptr(gt_pack), st), "zs_pose_pack")
         # a small first batch: its winner lets the staged drop (csrc/pose_search.hip) thin out every later batch
         starts, pos = [], 0
         while pos < K:
             starts.append((pos, min(first_batch if pos == 0 else batch_size, K - pos)))
             pos += starts[-1][1]
+        # kept (argument and ZS_POSE_PEEK): the only way to run the plain host loop, which enqueues every batch and never
+        # reads the record mid-search - what a caller that must not synchronise wants, and the A/B of the peek itself
         peek = (os.environ.get("ZS_POSE_PEEK", "1") != "0") if peek is None else bool(peek)
         lb_host = None
         for bi, (pos, count) in enumerate(starts):
@@ -487,7 +464,7 @@ def brute_force_search(pc_pred, pc_gt, f_thresholds=[0.005, 0.01, 0.02, 0.05, 0.
                             lb_sorted.data_ptr() + 4 * pos if lb_sorted is not None else None)
             else:                      # index order
                 rc = launch(rot_base + 36 * pos, None, count, start + pos, None)
-            _lib.check(rc, "zs_pose_search_batch")
+            _lib.check(rc, "zs_pose_search_batch_sorted")
             if rot_shard is not None and bi == 0:
                 _share_running_best(best, group)
         if rot_shard is not None:
