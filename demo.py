@@ -22,6 +22,9 @@ attention of the decoder's points over the input image as the query sweeps the g
 path with vis_attn=True), and <name>_mesh_viz.gif, 180 frames of the mesh on the reference's camera
 path from the library's rasteriser (geometry and shading formula pinned by tests; pyrender's PBR
 pixels are not reproduced).  Without --viz the files written are exactly the four above.
+
+--eval.field_normals=true (opt-in, shape task) gives <name>_mesh.obj one `vn` line per vertex - minus the normalised
+gradient of the occupancy field at the vertex (eval_3D.field_normals) - and faces of the form a//a.
 """
 import importlib
 import os
@@ -38,7 +41,7 @@ compat.install()
 import utils.options as options                                              # noqa: E402
 from utils.eval_3D import compute_level_grid, convert_to_explicit, get_dense_3D_grid   # noqa: E402
 from utils.util import EasyDict as edict                                     # noqa: E402
-from zeroshape_amd.utils import camera, util_vis                             # noqa: E402
+from zeroshape_amd.utils import camera, eval_3D, util_vis                    # noqa: E402
 
 
 def bbox_from_mask(mask, thr):
@@ -119,6 +122,7 @@ def main():
     os.makedirs(save_folder)
     opt.output_path = opt.datadir
     viz = bool(opt.get("viz", False))
+    field_normals = bool(opt.eval.get("field_normals", False))
     for var, name in zip(data_list, name_list):
         with torch.no_grad():
             var = graph.forward(opt, var, training=False, get_loss=False)
@@ -127,7 +131,10 @@ def main():
             util_vis.dump_depths(opt, [name], "depth_est", var.depth_pred, var.mask_input_map, rescale=True, folder='preds')
             if opt.task == 'shape':
                 var = marching_cubes(opt, var, graph.impl_network, vis_attn=viz)
-                util_vis.dump_meshes(opt, [name], "mesh", var.mesh_pred, folder='preds')
+                if field_normals:      # --eval.field_normals=true: <name>_mesh.obj gets `vn` lines, -grad/|grad| of the field
+                    eval_3D.field_normals(opt, graph.impl_network, var.latent_depth, var.latent_semantic, var.mesh_pred)
+                util_vis.dump_meshes(opt, [name], "mesh", var.mesh_pred, folder='preds',
+                                     normals="field" if field_normals else False)
                 if viz:
                     util_vis.dump_attentions(opt, [name], "attn", var.attn_vis, folder='preds')
                     util_vis.dump_meshes_viz(opt, [name], "mesh_viz", var.mesh_pred, save_frames=False, folder='preds')

@@ -414,6 +414,23 @@ int zs_mesh_weld_vertices(const float *tris, int n_tris, const void *scratch, in
                           float *vertices, float *normals, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
+ * itself is Implicit.field_gradient's, between the two calls).
+ *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G
+ *                     with G samples per axis (utils/eval_3D.py:252-255), but sample u of
+ *                     linspace(min, max, G) lies at min + u (max - min) / (G - 1).  points[i] =
+ *                     min + (vertices[i] - min) G / (G - 1), where the field that made the vertex
+ *                     was evaluated: fp64 as written, rounded to fp32.  n vertices of 3 floats; G >= 2.
+ *   finish          : normals[v] = -grad[v] / |grad[v]| (occupancy rises inwards), length and
+ *                     division in fp64, rounded to fp32.  Where |grad[v]| is zero, infinite or NaN:
+ *                     fallback[v] (or (0, 0, 0) when fallback is NULL), and *n_fallback (device
+ *                     int, zeroed by the caller) is incremented.
+ * ------------------------------------------------------------------------- */
+int zs_mesh_to_field_points(const float *vertices, size_t n, float range_min, int G, float *points, void *stream);
+int zs_field_normals_finish(const float *grad, const float *fallback, size_t n, float *normals, int *n_fallback,
+                            void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Mesh turntable renderer (replaces dump_meshes_viz / scale_to_unit_cube / visualize_mesh,
  * utils/util_vis.py:112-127, 310-405: trimesh + pyrender on OpenGL).  A z-buffer rasteriser
  * over the triangle soup tris[n_tris][3][3] that zs_mc_emit writes; all frames of a camera
@@ -837,6 +854,10 @@ int zs_act_backward(const float *dy, const float *ref, float *dx, size_t n, int 
  * posenc_3D = L > 0, model/shape/implicit.py:139-166): out[i][0:3+6L] = [x | sin(x 2^0) | cos(x 2^0) | ... | sin(x 2^(L-1)) |
  * cos(x 2^(L-1))], each group 3 wide (x, y, z), zero padded to `stride` floats per point (stride >= 3 + 6 L). */
 int zs_posenc3d(const float *points, size_t n, int L, float *out, int stride, void *stream);
+/* Its adjoint: dpoints[i][0:3] from the cotangent denc[i][0:stride] of the encoding, per axis
+ * dx = denc[x] + sum_k 2^k (cos(2^k x) denc[sin_k] - sin(2^k x) denc[cos_k]), with 2^k x rounded to fp32 as the forward rounds it
+ * and the forward's channel order.  Channels from 3 + 6 L on (the padding) are never read. */
+int zs_posenc3d_bwd(const float *points, size_t n, int L, const float *denc, int stride, float *dpoints, void *stream);
 int zs_add_scaled_rows(const float *x, const float *branch, const float *scale, float *y, int batch,
                        size_t per_sample, void *stream);
 size_t zs_column_sum_workspace_bytes(int rows, int C);

@@ -100,6 +100,8 @@ SIGNATURES = {
     "zs_mesh_weld_scratch_bytes": (_c_size_t, [_c_int]),
     "zs_mesh_weld": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_weld_vertices": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_to_field_points": (_c_int, [_c_void_p, _c_size_t, _c_float, _c_int, _c_void_p, _c_void_p]),
+    "zs_field_normals_finish": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_stats_scratch_bytes": (_c_size_t, [_c_int]),
     "zs_mesh_stats": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "zs_render_zbuffer_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
@@ -168,6 +170,7 @@ SIGNATURES = {
     "zs_act_forward": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_float, _c_void_p]),
     "zs_act_backward": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_int, _c_float, _c_void_p]),
     "zs_posenc3d": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int, _c_void_p]),
+    "zs_posenc3d_bwd": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
     "zs_add_scaled_rows": (_c_int, [_c_void_p] * 4 + [_c_int, _c_size_t, _c_void_p]),
     "zs_column_sum_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
     "zs_column_sum": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_float, _c_void_p, _c_void_p]),

@@ -550,12 +550,39 @@ __global__ __launch_bounds__(256) void posenc3d_kernel(const float *__restrict__
     for (int c = 3 + 6 * L; c < stride; c++) o[c] = 0.f;
 }
 
+// Its adjoint: dx = denc[x] + sum_k f_k (cos(f_k x) denc[sin_k] - sin(f_k x) denc[cos_k]), f_k = 2^k and x f_k formed as the
+// forward forms them; the forward's channel order; channels from 3 + 6 L on (the padding) are never read.
+__global__ __launch_bounds__(256) void posenc3d_bwd_kernel(const float *__restrict__ pts, size_t n, int L,
+                                                           const float *__restrict__ denc, int stride, float *__restrict__ dpts) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+    const float *g = denc + i * stride;
+    float dx[3] = {g[0], g[1], g[2]};
+    float freq = 1.0f;
+    for (int k = 0; k < L; k++, freq *= 2.0f)
+        for (int d = 0; d < 3; d++) {
+            const float a = x[d] * freq;
+            dx[d] += freq * (cosf(a) * g[3 + 6 * k + d] - sinf(a) * g[3 + 6 * k + 3 + d]);
+        }
+    for (int d = 0; d < 3; d++) dpts[3 * i + d] = dx[d];
+}
+
 extern "C" int zs_posenc3d(const float *points, size_t n, int L, float *out, int stride, void *stream) {
     ZS_REQUIRE(L >= 0 && L <= 16 && stride >= 3 + 6 * L, "zs_posenc3d: bad sizes (L=%d stride=%d)", L, stride);
     if (n == 0) return 1;
     ZS_REQUIRE(points && out, "zs_posenc3d: null pointer");
     hipLaunchKernelGGL(posenc3d_kernel, dim3(blocks_for(n)), dim3(256), 0, S(stream), points, n, L, out, stride);
     return zs::check_launch("zs_posenc3d") ? 1 : 0;
+}
+
+extern "C" int zs_posenc3d_bwd(const float *points, size_t n, int L, const float *denc, int stride, float *dpoints,
+                               void *stream) {
+    ZS_REQUIRE(L >= 0 && L <= 16 && stride >= 3 + 6 * L, "zs_posenc3d_bwd: bad sizes (L=%d stride=%d)", L, stride);
+    if (n == 0) return 1;
+    ZS_REQUIRE(points && denc && dpoints, "zs_posenc3d_bwd: null pointer");
+    hipLaunchKernelGGL(posenc3d_bwd_kernel, dim3(blocks_for(n)), dim3(256), 0, S(stream), points, n, L, denc, stride, dpoints);
+    return zs::check_launch("zs_posenc3d_bwd") ? 1 : 0;
 }
 
 extern "C" int zs_add_scaled_rows(const float *x, const float *branch, const float *scale, float *y, int batch,

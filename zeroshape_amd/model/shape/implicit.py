@@ -15,7 +15,8 @@ configuration the kernels are not specialised for, this module raises.
 Training (``.train()`` mode or any call under autograd that needs gradients) runs the same
 network layer by layer through zeroshape_amd/nn/autograd.py - HIP kernels for every forward and
 backward op, torch.autograd only as the tape - including timm's per-sample DropPath
-(implicit.py:83-109, drop_path=0.1).
+(implicit.py:83-109, drop_path=0.1).  Gradients reach the latent codes, the weights and, first order, the query points
+(``field_gradient``: the field's spatial gradient at many points, in chunks, with the parameters frozen).
 
 Every OTHER constructor configuration of the reference class with a head dimension of 32 - its own defaults (512 channels,
 16 heads, 6 MLP layers, latent_dim 768), a prediction head instead of the MLP (n_layers_mlp=0), other skips / ratios / block
@@ -35,7 +36,6 @@ import torch.nn as nn
 from ... import _lib
 from ... import program as P
 from ...nn import autograd as A
-from ...nn import ops
 from ...nn.operands import weights_stamp
 from ...utils.pos_embed import get_2d_sincos_pos_embed
 
@@ -100,6 +100,21 @@ class DecoderState(object):
     @property
     def stride_bytes(self):
         return self.programs.stride(0) * 4
+
+
+@contextlib.contextmanager
+def frozen_parameters(module):
+    """Within the block no parameter of ``module`` requires a gradient: the flag is cleared on the Parameter objects themselves
+    (the operand cache keys on id(weight): a detached view would be another weight to it) and set back on exit, also when the
+    block raises.  A backward pass inside the block computes no weight gradient and touches no ``.grad``."""
+    flags = [(p, p.requires_grad) for p in module.parameters()]
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        yield module
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
 
 
 class Implicit(nn.Module):
@@ -676,6 +691,46 @@ class Implicit(nn.Module):
         # so a caller gets the same numbers with and without the map
         return logits, self.query_points(DecoderState(state.exact, state.batch), points_3D, need_attn=True)[1]
 
+    def field_gradient(self, latent_depth, latent_semantic, points_3D, chunk=65536):
+        """The field and its spatial gradient at the query points: (logits [B,M], d logit[b,m] / d points_3D[b,m] [B,M,3]), fp32.
+        A point row attends to the latent rows and to itself only (implicit.py:44-66), so the rows are independent of one another
+        and ONE backward pass with a cotangent of ones yields every point's own gradient.  Forward and backward run layer by
+        layer (_forward_autograd) over ``chunk`` points per image at a time - the [B,chunk,4C] hidden tensors bound the memory
+        whatever M is - in eval arithmetic (no DropPath), with the parameters frozen: no weight-gradient GEMM runs, no parameter
+        gains a ``.grad``, the ``requires_grad`` flags are as before afterwards, and scratch buffers and packed operands are
+        this call's own (A.side_state), so a captured training step stays valid.  First order only."""
+        if self.semantic:
+            if latent_semantic is None:
+                raise ValueError("this Implicit was built with semantic=True: latent_semantic is required")
+            latent_depth = torch.cat([latent_depth.to(torch.float32), latent_semantic.to(torch.float32)], dim=-1)
+        elif latent_semantic is not None:
+            raise ValueError("latent_semantic given to an Implicit built with semantic=False")
+        if not (latent_depth.is_cuda and points_3D.is_cuda):
+            raise ValueError("latent_depth / points_3D must be GPU tensors; zeroshape_amd has no CPU path")
+        if points_3D.dim() != 3 or points_3D.shape[-1] != 3 or points_3D.shape[0] != latent_depth.shape[0]:
+            raise ValueError("points_3D must be [B,M,3] with the latent's B, got %s" % (tuple(points_3D.shape),))
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1, got %d" % chunk)
+        lat = latent_depth.detach().to(torch.float32)
+        pts = points_3D.detach().to(torch.float32)
+        B, M = pts.shape[0], pts.shape[1]
+        logits = torch.empty(B, M, dtype=torch.float32, device=pts.device)
+        grad = torch.empty(B, M, 3, dtype=torch.float32, device=pts.device)
+        was_training, drop_scales = self.training, self.drop_scales
+        self.training, self.drop_scales = False, None
+        try:
+            with frozen_parameters(self), A.side_state(), torch.enable_grad():
+                for begin in range(0, M, chunk):
+                    p = pts[:, begin:begin + chunk].contiguous().requires_grad_()
+                    out = self._forward_autograd(lat, p)[0]
+                    (g,) = torch.autograd.grad(out, p, torch.ones_like(out))
+                    logits[:, begin:begin + chunk].copy_(out.detach())
+                    grad[:, begin:begin + chunk].copy_(g)
+        finally:
+            self.training, self.drop_scales = was_training, drop_scales
+        return logits, grad
+
     # ---- training path (layer by layer, autograd over HIP kernels) -------------------------
     def _drop_scale(self, B, device):
         """timm drop_path (timm==0.6.12 layers/drop.py): bernoulli(keep) / keep per sample; None when
@@ -694,14 +749,16 @@ class Implicit(nn.Module):
         if not (latent_depth.is_cuda and points_3D.is_cuda):
             raise ValueError("latent_depth / points_3D must be GPU tensors; zeroshape_amd has no CPU path")
         lat = latent_depth.to(torch.float32)
-        pts = points_3D.detach().to(torch.float32).contiguous()
+        # Query points that carry a gradient keep it (first order): the point rows' data gradients arrive at pts4 / enc below from
+        # point_proj, layer 0 of impl_mlp and every skip layer, and torch.autograd sums them.
+        pts = A.query_points(points_3D.to(torch.float32).contiguous())
         B, M = pts.shape[0], pts.shape[1]
         H = self.num_heads
         Ll = self.num_patches + 1
         if tuple(lat.shape[1:]) != (Ll, self.latent_proj.in_features):
             raise ValueError("latent codes must be [B,%d,%d], got %s" % (Ll, self.latent_proj.in_features, tuple(lat.shape)))
         attn = torch.empty(B, M, Ll, dtype=torch.float32, device=pts.device) if want_attn else None
-        pts4 = ops.pad_channels(pts, 4)
+        pts4 = A.pad_channels(pts, 4)
         xp = A.linear(pts4, self.point_proj.proj.weight, self.point_proj.proj.bias, cin=3)            # :253
         pos = self.pos_embed.detach().expand(B, -1, -1).contiguous()
         cl = lat.shape[-1]

@@ -171,16 +171,84 @@ def backward_segment(s, params, loss=None):
     return True
 
 
-def posenc3d(points, L):
-    """points [..., 3] (no gradient: the decoder's query points are data) -> NeRF encoding [..., pad4(3 + 6 L)], the
-    reference's get_embedder(L, 3) (utils/layers.py:8-53), channels beyond 3 + 6 L zero (the channel count the GEMM stages)."""
+def _posenc3d_forward(pts, L):
     lib = _lib.load()
-    pts = _f32c(points.detach(), "posenc3d input")
     cpad = (3 + 6 * L + 3) // 4 * 4
     out = torch.empty(*pts.shape[:-1], cpad, dtype=torch.float32, device=pts.device)
     with _lib.on(pts.device):
         _lib.check(lib.zs_posenc3d(_lib.ptr(pts), pts.numel() // 3, int(L), _lib.ptr(out), cpad, _stream(pts)), "zs_posenc3d")
     return out
+
+
+def _first_order_only(what):
+    """Inside a backward: the kernels behind this module's Functions record no graph of their own, so a backward pass that is
+    itself being recorded (create_graph=True) would hand out gradients that look differentiable and are constants."""
+    if torch.is_grad_enabled():
+        raise RuntimeError("%s: first-order gradient only - torch.autograd was asked for a differentiable backward pass "
+                           "(create_graph=True), which the HIP kernels do not provide" % what)
+
+
+class _PosEnc3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, L):
+        pts = _f32c(points, "posenc3d input")
+        ctx.L = L
+        ctx.save_for_backward(pts)
+        return _posenc3d_forward(pts, L)
+
+    @staticmethod
+    def backward(ctx, denc):
+        _first_order_only("posenc3d")
+        (pts,) = ctx.saved_tensors
+        return ops.posenc3d_bwd(pts, ctx.L, _f32c(denc, "posenc3d grad")), None
+
+
+def posenc3d(points, L):
+    """points [..., 3] -> NeRF encoding [..., pad4(3 + 6 L)], the reference's get_embedder(L, 3) (utils/layers.py:8-53), channels
+    beyond 3 + 6 L zero (the channel count the GEMM stages).  Points that carry a gradient get it back through zs_posenc3d_bwd;
+    points that do not (training: the query points are data) cost the one launch and save nothing."""
+    if torch.is_grad_enabled() and points.requires_grad:
+        return _PosEnc3D.apply(points, L)
+    return _posenc3d_forward(_f32c(points.detach(), "posenc3d input"), L)
+
+
+class _QueryPoints(torch.autograd.Function):
+    """The identity on query points that carry a gradient, at the head of Implicit's layer-by-layer path: its backward is where
+    a create_graph=True request for the point gradient fails loudly (whatever the configuration puts behind it)."""
+
+    @staticmethod
+    def forward(ctx, points):
+        return points.view_as(points)
+
+    @staticmethod
+    def backward(ctx, dpoints):
+        _first_order_only("Implicit: the gradient w.r.t. points_3D")
+        return dpoints
+
+
+def query_points(points):
+    return _QueryPoints.apply(points) if torch.is_grad_enabled() and points.requires_grad else points
+
+
+class side_state(object):
+    """Within the block this module's launches use scratch buffers and an operand cache of their own (kept between blocks),
+    and SCRATCH_GENERATION reads afterwards what it read before: a captured training step - which holds the addresses of the
+    main scratch buffers and the launch tables of the main cache - is not invalidated by work that is not a training step
+    (Implicit.field_gradient: other row counts, data gradients training never asks for)."""
+    _scratch, _cache = {}, None
+
+    def __enter__(self):
+        global _SCRATCH, CACHE
+        if side_state._cache is None:
+            side_state._cache = type(CACHE)()
+        self.saved = (_SCRATCH, CACHE, SCRATCH_GENERATION[0])
+        _SCRATCH, CACHE = side_state._scratch, side_state._cache
+        return self
+
+    def __exit__(self, *exc):
+        global _SCRATCH, CACHE
+        _SCRATCH, CACHE, SCRATCH_GENERATION[0] = self.saved
+        return False
 
 
 class _PadChannels(torch.autograd.Function):

@@ -407,6 +407,23 @@ def pad_channels(x, cpad):
     return y
 
 
+def posenc3d_bwd(points, L, denc):
+    """The adjoint of zs_posenc3d: points [..., 3], cotangent of the encoding denc [..., pad4(3 + 6 L)] -> [..., 3].  The padding
+    channels of denc are never read."""
+    lib = _lib.load()
+    _chk(points, "posenc3d_bwd points")
+    _chk(denc, "posenc3d_bwd cotangent")
+    n, stride = points.numel() // 3, denc.shape[-1]
+    if points.shape[-1] != 3 or denc.shape[:-1] != points.shape[:-1] or stride < 3 + 6 * L:
+        raise ValueError("posenc3d_bwd: points %s and cotangent %s do not belong to one encoding (L=%d)"
+                         % (tuple(points.shape), tuple(denc.shape), L))
+    dpoints = torch.empty_like(points)
+    with _lib.on(points.device):
+        _lib.check(lib.zs_posenc3d_bwd(_lib.ptr(points), n, int(L), _lib.ptr(denc), stride, _lib.ptr(dpoints), _stream(points)),
+                   "zs_posenc3d_bwd")
+    return dpoints
+
+
 def window_tokens(emb, mask, invalid_token, cls, pos, win):
     """emb [B,H,W,C], mask [B,H,W] bool -> [B*(H/win)*(W/win), win*win+1, C] (zs_window_tokens)."""
     lib = _lib.load()

@@ -650,6 +650,9 @@ class SimpleMesh(object):
 
     def __init__(self, triangles):
         self.device_triangles = self._triangles = self._indexed = self._normals = None
+        # set by field_normals(): the weld it made (vertices, faces, normals on the device: _weld copies it instead of welding
+        # again), the field's normals [V,3] fp32 on the device, and the device count [1] int32 of vertices that fell back
+        self._device_weld = self.device_field_normals = self.field_normal_fallbacks = self._field_normals = None
         if isinstance(triangles, torch.Tensor) and triangles.is_cuda:
             self.device_triangles = triangles.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
         else:
@@ -664,9 +667,10 @@ class SimpleMesh(object):
     def _weld(self, normals=False):
         if self.device_triangles is not None:
             if self._indexed is None or (normals and self._normals is None):
-                out = [t.cpu().numpy() for t in weld_mesh(self.device_triangles, normals=normals)]
+                welded = self._device_weld or weld_mesh(self.device_triangles, normals=normals)
+                out = [t.cpu().numpy() for t in welded]
                 self._indexed = (out[0], out[1].astype(np.int64))
-                if normals:
+                if len(out) > 2:
                     self._normals = out[2]
             return self._indexed
         if self._indexed is None:
@@ -693,6 +697,67 @@ class SimpleMesh(object):
     def vertex_normals(self):
         self._weld(normals=True)
         return self._normals
+
+    @property
+    def field_normals(self):
+        """[v,3] float32, the rows of ``vertices``: minus the occupancy field's normalised gradient at each vertex, computed
+        by field_normals() (on the device until read here)."""
+        if self.device_field_normals is None:
+            raise ValueError("this mesh has no field normals: eval_3D.field_normals(opt, impl_network, latents, meshes) "
+                             "computes them")
+        if self._field_normals is None:
+            self._field_normals = self.device_field_normals.cpu().numpy()
+        return self._field_normals
+
+
+def mesh_to_field_points_host(vertices, range_min, G):
+    """zs_mesh_to_field_points restated in numpy, operation for operation: marching cubes puts grid index u at
+    v = min + u (max - min) / G (G samples per axis), the grid linspace(min, max, G) has sample u at min + u (max - min) / (G - 1),
+    so the field that made vertex v was evaluated at p = min + (v - min) G / (G - 1) - float64, rounded to float32 (the minimum
+    as the float32 the kernel receives)."""
+    lo = np.float64(np.float32(range_min))
+    v = np.asarray(vertices, np.float32).astype(np.float64)
+    return (lo + (v - lo) * np.float64(G) / np.float64(G - 1)).astype(np.float32)
+
+
+def field_normals(opt, impl_network, latent_depth, latent_semantic, meshes, chunk=65536):
+    """Vertex normals from the field itself: for mesh b of the batch (SimpleMesh objects of convert_to_explicit on
+    ``opt.eval.vox_res`` / ``opt.eval.range``) weld (weld_mesh), map the vertices to where the field that made them was
+    evaluated (zs_mesh_to_field_points), take the gradient of the logit there with image b's latent
+    (``impl_network.field_gradient``, ``chunk`` points at a time) and finish (zs_field_normals_finish): n = -g / |g| - occupancy
+    rises inwards, so minus the gradient points out - with the weld's area-weighted normal wherever |g| is zero or not finite.
+    Stored as ``mesh.field_normals`` ([V,3] float32, on the device until read; [0,3] for an empty mesh);
+    ``mesh.field_normal_fallbacks`` is the device count [1] int32 of vertices that fell back.  GPU meshes only: a mesh built
+    from a host array raises ValueError.  -> meshes."""
+    from .. import _lib
+    lib = _lib.load()
+    range_min = float(opt.eval.range[0])
+    G = int(opt.eval.vox_res) + 1
+    if len(meshes) > latent_depth.shape[0]:
+        raise ValueError("field_normals: %d meshes for %d latents" % (len(meshes), latent_depth.shape[0]))
+    for b, mesh in enumerate(meshes):
+        if getattr(mesh, "device_triangles", None) is None:
+            raise ValueError("field_normals: mesh %d was built from a host array; there is no CPU path" % b)
+    for b, mesh in enumerate(meshes):
+        if mesh._device_weld is None:
+            mesh._device_weld = weld_mesh(mesh.device_triangles, normals=True)
+        vertices, _, fallback = mesh._device_weld
+        V, dev = vertices.shape[0], vertices.device
+        normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        if V:
+            points = torch.empty_like(vertices)
+            with _lib.on(dev):
+                _lib.check(lib.zs_mesh_to_field_points(_lib.ptr(vertices), V, range_min, G, _lib.ptr(points),
+                                                       _lib.current_stream_ptr(dev)), "zs_mesh_to_field_points")
+            sem = None if latent_semantic is None else latent_semantic[b:b + 1]
+            _, grad = impl_network.field_gradient(latent_depth[b:b + 1], sem, points.unsqueeze(0), chunk=chunk)
+            grad = grad.reshape(V, 3)
+            with _lib.on(dev):
+                _lib.check(lib.zs_field_normals_finish(_lib.ptr(grad), _lib.ptr(fallback), V, _lib.ptr(normals), _lib.ptr(count),
+                                                       _lib.current_stream_ptr(dev)), "zs_field_normals_finish")
+        mesh.device_field_normals, mesh.field_normal_fallbacks, mesh._field_normals = normals, count, None
+    return meshes
 
 
 def vertex_normals_host(triangles, faces, n_vertices):
