@@ -25,6 +25,13 @@ pixels are not reproduced).  Without --viz the files written are exactly the fou
 
 --eval.field_normals=true (opt-in, shape task) gives <name>_mesh.obj one `vn` line per vertex - minus the normalised
 gradient of the occupancy field at the vertex (eval_3D.field_normals) - and faces of the form a//a.
+
+--eval.min_component_area=0.05 and --eval.drop_cavities=true (opt-in, shape task) clean the mesh on the GPU before it is
+written (eval_3D.filter_components): connected components whose area is below that fraction of the largest one's - the
+detached blobs of a single-view reconstruction - and closed inner shells of negative volume are dropped.
+--eval.mesh_report=true adds <name>_mesh_report.json next to the .obj: area, volume, Euler number, watertightness and the
+per-component table (faces, vertices, edges, boundary / non-manifold / misoriented edges, area, signed volume) of the mesh
+that was written.
 """
 import importlib
 import os
@@ -123,6 +130,7 @@ def main():
     opt.output_path = opt.datadir
     viz = bool(opt.get("viz", False))
     field_normals = bool(opt.eval.get("field_normals", False))
+    mesh_report = bool(opt.eval.get("mesh_report", False))
     for var, name in zip(data_list, name_list):
         with torch.no_grad():
             var = graph.forward(opt, var, training=False, get_loss=False)
@@ -135,6 +143,8 @@ def main():
                     eval_3D.field_normals(opt, graph.impl_network, var.latent_depth, var.latent_semantic, var.mesh_pred)
                 util_vis.dump_meshes(opt, [name], "mesh", var.mesh_pred, folder='preds',
                                      normals="field" if field_normals else False)
+                if mesh_report:        # --eval.mesh_report=true: <name>_mesh_report.json, the totals and components of that mesh
+                    util_vis.dump_mesh_reports(opt, [name], "mesh_report", var.mesh_pred, folder='preds')
                 if viz:
                     util_vis.dump_attentions(opt, [name], "attn", var.attn_vis, folder='preds')
                     util_vis.dump_meshes_viz(opt, [name], "mesh_viz", var.mesh_pred, save_frames=False, folder='preds')

@@ -414,6 +414,52 @@ int zs_mesh_weld_vertices(const float *tris, int n_tris, const void *scratch, in
                           float *vertices, float *normals, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Connected components of an indexed mesh, their counts and measures, and the removal of
+ * components from the soup (csrc/mesh_components.hip; eval_3D.mesh_components_host restates all
+ * of it in numpy and defines it).  faces [n_tris][3] int32 over n_verts vertices is the weld's
+ * output, tris [n_tris][3][3] the soup it was made from.
+ *   components : two vertices are connected when some face holds both (a shared vertex is
+ *                enough, an edge is not needed).  Label = the rank of the component's smallest
+ *                vertex index.  vertex_labels [n_verts], face_labels [n_tris] (the label of the
+ *                face's first vertex), out[2] (device ints) = the component count and a status
+ *                word: 0, or nonzero when a loop ran into its bound (1) or a face index lies
+ *                outside [0, n_verts) (2) - the labels are then not to be used.
+ *                A lock-free union-find over the faces, a flattening kernel, one scan.
+ *   stats      : after the caller has read the count.  counts [n_comps][8] int32 = faces,
+ *                vertices, degenerate faces (two equal indices), edges (unique vertex pairs of the
+ *                other faces), boundary edges (used once), non-manifold edges (used more than
+ *                twice), misoriented edges (used twice, in the same direction), Euler number
+ *                V - E + (F - degenerate).  measures [n_comps][2] fp64 = area (sum of
+ *                |cross(v1 - v0, v2 - v0)| / 2) and signed volume (sum of v0 . cross(v1, v2) / 6)
+ *                from the soup's fp32 corners, every operation in fp64 as written in the checker;
+ *                a degenerate face adds exactly 0.  The integers by integer atomics; the sums by a
+ *                stable sort of the faces by label and a fixed-shape segmented reduction - no
+ *                floating-point atomics, two runs give the same bits.
+ *   select     : keep[c] = explicit_keep[c] != 0 when explicit_keep (uint8 [n_comps]) is given;
+ *                otherwise area[c] >= min_rel_area * max(area) (fp64; min_rel_area = 0 switches
+ *                the area rule off) and, with drop_cavities, not (closed and signed volume < 0),
+ *                closed = at least one non-degenerate face and no boundary, non-manifold or
+ *                misoriented edge.  keep_pos [n_tris] int32 = the inclusive scan of the faces'
+ *                keep flags, *n_kept (device int) = its last element.
+ *   filter     : after the caller has read n_kept: out_tris[keep_pos[f] - 1] = tris[f] for the
+ *                kept faces - the soup's order is preserved.
+ * scratch: zs_mesh_components_scratch_bytes(n_tris, n_verts) bytes, 8-byte aligned, for any of the
+ * calls (0 for empty and out-of-range sizes); nothing is carried in it from one call to the next.
+ * Limits: n_tris <= 2^29, n_verts <= 3 n_tris, n_comps <= n_verts.  Zero sizes return 1 and touch
+ * nothing.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_components_scratch_bytes(int n_tris, int n_verts);
+int zs_mesh_components(const int *faces, int n_tris, int n_verts, int *vertex_labels, int *face_labels, int *out,
+                       void *scratch, void *stream);
+int zs_mesh_component_stats(const float *tris, const int *faces, const int *vertex_labels, const int *face_labels,
+                            int n_tris, int n_verts, int n_comps, int *counts, double *measures, void *scratch,
+                            void *stream);
+int zs_mesh_components_select(const int *counts, const double *measures, int n_comps, double min_rel_area,
+                              int drop_cavities, const uint8_t *explicit_keep, const int *face_labels, int n_tris,
+                              int n_verts, int *keep_pos, int *n_kept, void *scratch, void *stream);
+int zs_mesh_filter_faces(const float *tris, const int *keep_pos, int n_tris, float *out_tris, int n_kept, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
  * itself is Implicit.field_gradient's, between the two calls).
  *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G

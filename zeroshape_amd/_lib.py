@@ -14,6 +14,7 @@ _c_void_p = ctypes.c_void_p
 _c_int = ctypes.c_int
 _c_size_t = ctypes.c_size_t
 _c_float = ctypes.c_float
+_c_double = ctypes.c_double
 
 class ConvFuse(ctypes.Structure):
     """include/zeroshape_hip.h: zs_conv_fuse."""
@@ -100,6 +101,13 @@ SIGNATURES = {
     "zs_mesh_weld_scratch_bytes": (_c_size_t, [_c_int]),
     "zs_mesh_weld": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_weld_vertices": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_components_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+    "zs_mesh_components": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_component_stats": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p,
+                                         _c_void_p, _c_void_p]),
+    "zs_mesh_components_select": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_double, _c_int, _c_void_p, _c_void_p, _c_int, _c_int,
+                                           _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_filter_faces": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p]),
     "zs_mesh_to_field_points": (_c_int, [_c_void_p, _c_size_t, _c_float, _c_int, _c_void_p, _c_void_p]),
     "zs_field_normals_finish": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_stats_scratch_bytes": (_c_size_t, [_c_int]),

@@ -45,6 +45,8 @@ EXTRA = {
     "mesh_weld.hip": ["-ffp-contract=off"],
     # the fp64 vertex mapping reproducible op for op by the numpy restatement in utils/eval_3D.py (mesh_to_field_points_host)
     "field_normals.hip": ["-ffp-contract=off"],
+    # fp64 area / volume terms equal, term for term, to the numpy restatement in utils/eval_3D.py (mesh_components_host)
+    "mesh_components.hip": ["-ffp-contract=off"],
 }
 
 

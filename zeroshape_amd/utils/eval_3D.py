@@ -525,11 +525,28 @@ def _surface_clouds(opt, level_vox, seed=0):
     reference (utils/eval_3D.py:115-118,181-184)."""
     meshes, clouds = [], []
     range_min, range_max = opt.eval.range
+    cleaning = _component_options(opt)
     for i in range(level_vox.shape[0]):
-        tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
-        meshes.append(SimpleMesh(tris))                  # stays in HBM until a dump reads it
+        if cleaning is None:
+            tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
+            mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
+        else:                                            # eval.min_component_area / eval.drop_cavities: sample the cleaned mesh
+            tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)
+            mesh = filter_components(SimpleMesh(tris), *cleaning)
+            pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i)
+        meshes.append(mesh)
         clouds.append(pts)
     return meshes, torch.stack(clouds, dim=0)
+
+
+def _component_options(opt):
+    """(min_component_area, drop_cavities) when either opt-in is set (``--eval.min_component_area=0.05``,
+    ``--eval.drop_cavities=true``: no yaml file carries them), else None: the pipelines then make today's calls."""
+    min_area = opt.eval.get("min_component_area", None)
+    drop = bool(opt.eval.get("drop_cavities", False))
+    if min_area is None and not drop:
+        return None
+    return (None if min_area is None else float(min_area)), drop
 
 
 def _gt_to_view_frame(opt, var):
@@ -641,6 +658,9 @@ class SimpleMesh(object):
     for bit and welding = unique rows of the soup (``vertices[faces]`` reproduces ``triangles`` exactly).
     ``vertex_normals`` [v,3] float32 (trimesh's name): the area-weighted formula of vertex_normals_host; parity with
     trimesh's own weighting is unpinned (trimesh is not a dependency of this package).
+    ``components`` (a MeshComponents: labels, per-component counts, area and signed volume) and, from it, trimesh's ``area``,
+    ``volume``, ``euler_number`` and ``is_watertight``; filter_components(mesh, ...) is the stand-in for ``mesh.split()`` + a
+    choice among the parts.
 
     Built from a GPU tensor the mesh stays in HBM: ``device_triangles`` is that tensor (the turntable renders from it),
     the weld and the normals come from weld_mesh (csrc/mesh_weld.hip) on first access, and ``triangles`` / ``vertices`` /
@@ -653,6 +673,7 @@ class SimpleMesh(object):
         # set by field_normals(): the weld it made (vertices, faces, normals on the device: _weld copies it instead of welding
         # again), the field's normals [V,3] fp32 on the device, and the device count [1] int32 of vertices that fell back
         self._device_weld = self.device_field_normals = self.field_normal_fallbacks = self._field_normals = None
+        self._components = None                          # mesh_components(self), cached by the ``components`` property
         if isinstance(triangles, torch.Tensor) and triangles.is_cuda:
             self.device_triangles = triangles.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
         else:
@@ -697,6 +718,37 @@ class SimpleMesh(object):
     def vertex_normals(self):
         self._weld(normals=True)
         return self._normals
+
+    @property
+    def components(self):
+        """mesh_components(self), computed once: the connected components with their counts and measures (on the device for
+        a GPU mesh until a column is read)."""
+        if self._components is None:
+            self._components = mesh_components(self)
+        return self._components
+
+    @property
+    def area(self):
+        """trimesh's name: the surface area, the sum over the components (float)."""
+        return float(self.components.area.sum())
+
+    @property
+    def volume(self):
+        """trimesh's name: the signed volume, the sum over the components - positive for a solid wound like marching cubes'
+        meshes, a closed cavity counts negative (float)."""
+        return float(self.components.signed_volume.sum())
+
+    @property
+    def euler_number(self):
+        """trimesh's name: V - E + F over the whole mesh, degenerate faces (two equal indices) left out of E and F (int)."""
+        return int(self.components.euler.sum())
+
+    @property
+    def is_watertight(self):
+        """trimesh's name: at least one component, and every component closed - every edge used by exactly two faces that
+        run through it in opposite directions."""
+        closed = self.components.closed
+        return bool(len(closed) > 0 and closed.all())
 
     @property
     def field_normals(self):
@@ -810,6 +862,267 @@ def weld_mesh(tris, normals=False):
     return (vertices, faces, vnormals) if normals else (vertices, faces)
 
 
+COMPONENT_COLUMNS = ("faces", "vertices", "degenerate_faces", "edges", "boundary_edges", "nonmanifold_edges",
+                     "misoriented_edges", "euler")
+
+
+class MeshComponents(object):
+    """The connected components of a mesh (mesh_components / mesh_components_host), numbered in ascending order of their
+    smallest vertex index:
+
+      n_components                      int
+      vertex_labels [V], face_labels [F] int32 (a face has the label of its first vertex)
+      counts [C,8] int32                the columns of COMPONENT_COLUMNS, also readable by name: ``faces``, ``vertices``,
+                                        ``degenerate_faces``, ``edges``, ``boundary_edges``, ``nonmanifold_edges``,
+                                        ``misoriented_edges``, ``euler``
+      area, signed_volume [C] float64
+      closed [C] bool                   at least one non-degenerate face and no boundary, non-manifold or misoriented edge
+
+    From a GPU mesh the ``device_*`` tensors (vertex_labels, face_labels, counts, measures [C,2] fp64 = area, signed volume)
+    hold the results and the arrays above are host copies made when first read; from a host mesh they are None."""
+
+    def __init__(self, n_components, vertex_labels, face_labels, counts, measures):
+        self.n_components = int(n_components)
+        self.device_vertex_labels = self.device_face_labels = self.device_counts = self.device_measures = None
+        self._host = {}
+        given = dict(vertex_labels=vertex_labels, face_labels=face_labels, counts=counts, measures=measures)
+        if isinstance(counts, torch.Tensor):
+            for key, value in given.items():
+                setattr(self, "device_" + key, value)
+        else:
+            self._host = given
+
+    def _read(self, key):
+        if key not in self._host:
+            self._host[key] = getattr(self, "device_" + key).cpu().numpy()
+        return self._host[key]
+
+    vertex_labels = property(lambda self: self._read("vertex_labels"))
+    face_labels = property(lambda self: self._read("face_labels"))
+    counts = property(lambda self: self._read("counts"))
+    area = property(lambda self: self._read("measures")[:, 0])
+    signed_volume = property(lambda self: self._read("measures")[:, 1])
+
+    @property
+    def closed(self):
+        c = self.counts
+        return (c[:, 0] - c[:, 2] > 0) & (c[:, 4] == 0) & (c[:, 5] == 0) & (c[:, 6] == 0)
+
+    def table(self):
+        """The per-component table as a list of dicts of Python numbers (what demo.py's mesh report stores)."""
+        closed = self.closed
+        return [dict([(name, int(self.counts[c, k])) for k, name in enumerate(COMPONENT_COLUMNS)]
+                     + [("closed", bool(closed[c])), ("area", float(self.area[c])), ("signed_volume", float(self.signed_volume[c]))])
+                for c in range(self.n_components)]
+
+
+for _k, _name in enumerate(COMPONENT_COLUMNS):
+    setattr(MeshComponents, _name, property(lambda self, _k=_k: self.counts[:, _k]))
+
+
+def mesh_face_terms_host(triangles, faces):
+    """The per-face terms of mesh_components_host's sums, float64 [F] each: area |cross(v1 - v0, v2 - v0)| / 2 and signed
+    volume dot(v0, cross(v1, v2)) / 6 from the float32 corners, operation by operation as cs_terms_kernel computes them; a
+    face with two equal indices gives exactly 0 for both."""
+    t = np.asarray(triangles, np.float32).reshape(-1, 3, 3).astype(np.float64)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    degenerate = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2])
+    with np.errstate(over="ignore", invalid="ignore"):
+        x0, y0, z0 = t[:, 0, 0], t[:, 0, 1], t[:, 0, 2]
+        x1, y1, z1 = t[:, 1, 0], t[:, 1, 1], t[:, 1, 2]
+        x2, y2, z2 = t[:, 2, 0], t[:, 2, 1], t[:, 2, 2]
+        ax, ay, az, bx, by, bz = x1 - x0, y1 - y0, z1 - z0, x2 - x0, y2 - y0, z2 - z0
+        nx, ny, nz = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx
+        area = 0.5 * np.sqrt(nx * nx + ny * ny + nz * nz)
+        cx, cy, cz = y1 * z2 - z1 * y2, z1 * x2 - x1 * z2, x1 * y2 - y1 * x2
+        volume = (x0 * cx + y0 * cy + z0 * cz) / 6.0
+    return np.where(degenerate, 0.0, area), np.where(degenerate, 0.0, volume)
+
+
+def mesh_components_host(vertices, faces, triangles):
+    """The definition of the mesh-component quantities and the checker of csrc/mesh_components.hip, in numpy.
+    ``vertices`` [V,3] (only V is used), ``faces`` [F,3] the weld's indices, ``triangles`` [F,3,3] float32 the soup the weld
+    was made from -> MeshComponents.
+
+    Components: two vertices are connected when some face holds both.  Sharing a welded vertex is enough, an edge is not
+    required: trimesh's ``split`` goes by edge adjacency and separates two bodies that touch in a point - this deliberately
+    does not.  Components are numbered in ascending order of their smallest vertex index; a face has the label of its first
+    vertex.  A face is degenerate when two of its three indices are equal (by index, not by area): it belongs to its
+    component, is counted in ``degenerate_faces``, has no edges and is left out of the face term of the Euler number; its
+    area and volume terms are exactly zero.  ``edges`` = unique undirected vertex pairs of the other faces; ``boundary_edges``
+    are used by exactly one face, ``nonmanifold_edges`` by more than two, ``misoriented_edges`` by exactly two whose
+    half-edges run the same way; an edge belongs to the component of its vertices.  euler = vertices - edges + (faces -
+    degenerate_faces).  area = sum of |cross(v1 - v0, v2 - v0)| / 2, signed_volume = sum of dot(v0, cross(v1, v2)) / 6 over the
+    component's faces in ascending face order, from the float32 corners converted to float64, every operation as written
+    below (the kernels do the same operations; only the order of the additions differs).  With the winding of this package's
+    marching cubes a solid body has a positive volume and a closed cavity a negative one."""
+    V = len(vertices)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    F = len(f)
+    assert np.asarray(triangles).size == 9 * F and (F == 0 or (f.min() >= 0 and f.max() < V))
+    # union-find by rounds: hook every face's roots under the smallest of them, then jump every pointer to its root
+    root = np.arange(V, dtype=np.int64)
+    live = f
+    while len(live):
+        r = root[live]
+        low = r.min(axis=1)
+        differ = (r != low[:, None]).any(axis=1)               # faces whose vertices are not under one root yet
+        live, r, low = live[differ], r[differ], low[differ]
+        if not len(live):
+            break
+        np.minimum.at(root, r.reshape(-1), np.repeat(low, 3))
+        while True:
+            jumped = root[root]
+            if np.array_equal(jumped, root):
+                break
+            root = jumped
+    roots = np.flatnonzero(root == np.arange(V))                     # ascending: the smallest vertex of each component
+    C = len(roots)
+    vertex_labels = np.searchsorted(roots, root).astype(np.int32)
+    face_labels = vertex_labels[f[:, 0]].astype(np.int32) if F else np.zeros(0, np.int32)
+    counts = np.zeros((C, len(COMPONENT_COLUMNS)), np.int32)
+    degenerate = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2])
+    counts[:, 0] = np.bincount(face_labels, minlength=C)
+    counts[:, 1] = np.bincount(vertex_labels, minlength=C)
+    counts[:, 2] = np.bincount(face_labels[degenerate], minlength=C)
+    g = f[~degenerate]
+    a, b = g.reshape(-1), g[:, [1, 2, 0]].reshape(-1)                # the half-edges a -> b
+    key = (np.minimum(a, b).astype(np.uint64) << np.uint64(32)) | np.maximum(a, b).astype(np.uint64)
+    edge, inverse, uses = np.unique(key, return_inverse=True, return_counts=True)
+    forward = np.bincount(inverse.reshape(-1), weights=(a < b), minlength=len(edge)).astype(np.int64)
+    edge_label = vertex_labels[(edge >> np.uint64(32)).astype(np.int64)]
+    counts[:, 3] = np.bincount(edge_label, minlength=C)
+    counts[:, 4] = np.bincount(edge_label[uses == 1], minlength=C)
+    counts[:, 5] = np.bincount(edge_label[uses > 2], minlength=C)
+    counts[:, 6] = np.bincount(edge_label[(uses == 2) & (forward != 1)], minlength=C)
+    counts[:, 7] = counts[:, 1] - counts[:, 3] + (counts[:, 0] - counts[:, 2])
+    area, volume = mesh_face_terms_host(triangles, f)
+    measures = np.zeros((C, 2), np.float64)
+    measures[:, 0] = np.bincount(face_labels, weights=area, minlength=C)      # (bincount adds in face order)
+    measures[:, 1] = np.bincount(face_labels, weights=volume, minlength=C)
+    return MeshComponents(C, vertex_labels, face_labels, counts, measures)
+
+
+def _components_device(tris, faces, n_verts):
+    """zs_mesh_components + zs_mesh_component_stats on a welded GPU mesh -> MeshComponents of device tensors.  One 8-byte
+    device-to-host copy: the component count, which sizes the tables, with the kernels' status word beside it."""
+    from .. import _lib
+    lib = _lib.load()
+    n, dev = tris.shape[0], tris.device
+    vertex_labels = torch.empty(n_verts, dtype=torch.int32, device=dev)
+    face_labels = torch.empty(n, dtype=torch.int32, device=dev)
+    n_comps = 0
+    if n and n_verts:
+        scratch = torch.empty(lib.zs_mesh_components_scratch_bytes(n, n_verts) // 8 + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(2, dtype=torch.int32, device=dev)
+        stream = _lib.current_stream_ptr(dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_components(_lib.ptr(faces), n, n_verts, _lib.ptr(vertex_labels), _lib.ptr(face_labels),
+                                              _lib.ptr(out), _lib.ptr(scratch), stream), "zs_mesh_components")
+            n_comps, status = out.tolist()                   # 8-byte D2H: sizes the tables
+        if status:
+            raise _lib.ZeroShapeHipError("zs_mesh_components: status %d (%s)" % (
+                status, "a face index outside the vertices" if status & 2 else "a linking loop ran into its bound"))
+    counts = torch.empty(n_comps, len(COMPONENT_COLUMNS), dtype=torch.int32, device=dev)
+    measures = torch.empty(n_comps, 2, dtype=torch.float64, device=dev)
+    if n_comps:
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_component_stats(_lib.ptr(tris), _lib.ptr(faces), _lib.ptr(vertex_labels), _lib.ptr(face_labels),
+                                                   n, n_verts, n_comps, _lib.ptr(counts), _lib.ptr(measures), _lib.ptr(scratch),
+                                                   stream), "zs_mesh_component_stats")
+    return MeshComponents(n_comps, vertex_labels, face_labels, counts, measures)
+
+
+@torch.no_grad()
+def mesh_components(mesh):
+    """The connected components of a SimpleMesh with their counts and measures -> MeshComponents (the semantics:
+    mesh_components_host).  A GPU mesh is labelled and measured on the device (csrc/mesh_components.hip) from the weld it
+    carries (``_device_weld``, which field_normals leaves too) or, if it has none yet, from one weld_mesh call whose result it
+    then keeps; a mesh built from a host array goes through the host checker.  ``mesh.components`` caches the result."""
+    if getattr(mesh, "device_triangles", None) is not None:
+        if mesh._device_weld is None:
+            mesh._device_weld = weld_mesh(mesh.device_triangles, normals=True)
+        vertices, faces = mesh._device_weld[0], mesh._device_weld[1]
+        return _components_device(mesh.device_triangles, faces, vertices.shape[0])
+    return mesh_components_host(mesh.vertices, mesh.faces, mesh.triangles)
+
+
+def _check_filter_arguments(min_component_area, keep, n_components):
+    if min_component_area is not None and not (0.0 < float(min_component_area) <= 1.0):
+        raise ValueError("filter_components: min_component_area must lie in (0, 1], got %r" % (min_component_area,))
+    if keep is None:
+        return None
+    flags = np.zeros(n_components, np.uint8)
+    ids = np.asarray(list(keep), np.int64).reshape(-1)
+    if len(ids) and (ids.min() < 0 or ids.max() >= n_components):
+        raise ValueError("filter_components: keep names a component outside 0..%d" % (n_components - 1))
+    flags[ids] = 1
+    return flags
+
+
+def select_components_host(components, min_component_area=None, drop_cavities=False, keep=None):
+    """The rule of filter_components in numpy -> bool [C]: the checker of zs_mesh_components_select."""
+    flags = _check_filter_arguments(min_component_area, keep, components.n_components)
+    if flags is not None:
+        return flags.astype(bool)
+    kept = np.ones(components.n_components, bool)
+    if min_component_area is not None and components.n_components:
+        kept &= components.area >= np.float64(min_component_area) * components.area.max()
+    if drop_cavities:
+        kept &= ~(components.closed & (components.signed_volume < 0.0))
+    return kept
+
+
+@torch.no_grad()
+def filter_components(mesh, min_component_area=None, drop_cavities=False, keep=None):
+    """A new SimpleMesh of the components of ``mesh`` that pass - its soup is the kept faces in soup order, on the GPU for a
+    GPU mesh (rule and compaction run on the device: zs_mesh_components_select, one 4-byte read-back of the kept count,
+    zs_mesh_filter_faces), in numpy for a host mesh.  Component c is kept iff
+    ``area[c] >= min_component_area * max(area)`` (``min_component_area`` in (0, 1]; at 1.0 only the largest component and
+    exact ties stay; None: no area rule) and, with ``drop_cavities``, it is not a closed component of negative signed
+    volume; or, with ``keep`` (component labels) given, iff c is in ``keep``.  An empty mesh, or a rule that keeps nothing,
+    gives an empty mesh."""
+    comps = mesh.components
+    flags = _check_filter_arguments(min_component_area, keep, comps.n_components)
+    if getattr(mesh, "device_triangles", None) is None:
+        kept = select_components_host(comps, min_component_area, drop_cavities, keep)
+        return SimpleMesh(mesh.triangles[kept[comps.face_labels]] if len(mesh.triangles) else mesh.triangles.copy())
+    from .. import _lib
+    lib = _lib.load()
+    tris = mesh.device_triangles
+    n, dev = tris.shape[0], tris.device
+    n_verts = comps.device_vertex_labels.shape[0]
+    n_kept = 0
+    if n and n_verts:
+        scratch = torch.empty(lib.zs_mesh_components_scratch_bytes(n, n_verts) // 8 + 1, dtype=torch.int64, device=dev)
+        keep_pos = torch.empty(n, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        explicit = None if flags is None else torch.from_numpy(flags).to(dev)
+        stream = _lib.current_stream_ptr(dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_components_select(
+                _lib.ptr(comps.device_counts), _lib.ptr(comps.device_measures), comps.n_components,
+                0.0 if min_component_area is None else float(min_component_area), int(bool(drop_cavities)), _lib.ptr(explicit),
+                _lib.ptr(comps.device_face_labels), n, n_verts, _lib.ptr(keep_pos), _lib.ptr(count), _lib.ptr(scratch), stream),
+                "zs_mesh_components_select")
+            n_kept = int(count.item())                       # 4-byte D2H: sizes the output
+    out = torch.empty(n_kept, 3, 3, dtype=torch.float32, device=dev)
+    if n_kept:
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_filter_faces(_lib.ptr(tris), _lib.ptr(keep_pos), n, _lib.ptr(out), n_kept, stream),
+                       "zs_mesh_filter_faces")
+    return SimpleMesh(out)
+
+
+def mesh_report(mesh):
+    """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
+    per-component table."""
+    comps = mesh.components
+    return dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
+                area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
+                component_table=comps.table())
+
+
 _MC_TABLES = {}
 
 
@@ -850,13 +1163,27 @@ def extract_surface(level_vox, isoval, range_min, range_max, num_points=0, seed=
         _lib.check(lib.zs_mc_emit(_lib.ptr(vol), G, float(isoval), _lib.ptr(tab), stride, _lib.ptr(cnt),
                                   _lib.ptr(scratch), float(scale), float(range_min), _lib.ptr(tris), n_tris,
                                   stream), "zs_mc_emit")
-        pts = None
-        if num_points:
-            pts = torch.empty(num_points, 3, dtype=torch.float32, device=dev)
-            cum = torch.empty(max(lib.zs_mesh_sample_scratch_doubles(n_tris), 1), dtype=torch.float64, device=dev)
-            _lib.check(lib.zs_mesh_sample(_lib.ptr(tris), n_tris, num_points, int(seed) & ((1 << 64) - 1),
-                                          _lib.ptr(cum), _lib.ptr(pts), stream), "zs_mesh_sample")
+        pts = sample_surface(tris, num_points, seed) if num_points else None
     return tris, pts
+
+
+@torch.no_grad()
+def sample_surface(tris, num_points, seed=0):
+    """``num_points`` area-weighted points [num_points,3] fp32 on a triangle soup [n,3,3] that lives on the GPU
+    (zs_mesh_sample: counter-based random stream seeded by ``seed``; an empty soup gives zeros), enqueued on the current
+    stream.  extract_surface samples through this, and so does the pipeline after filter_components."""
+    from .. import _lib
+    lib = _lib.load()
+    if not (isinstance(tris, torch.Tensor) and tris.is_cuda):
+        raise ValueError("sample_surface: tris must be a GPU tensor")
+    soup = tris.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
+    n_tris, dev = soup.shape[0], soup.device
+    pts = torch.empty(int(num_points), 3, dtype=torch.float32, device=dev)
+    cum = torch.empty(max(lib.zs_mesh_sample_scratch_doubles(n_tris), 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.zs_mesh_sample(_lib.ptr(soup), n_tris, int(num_points), int(seed) & ((1 << 64) - 1),
+                                      _lib.ptr(cum), _lib.ptr(pts), _lib.current_stream_ptr(dev)), "zs_mesh_sample")
+    return pts
 
 
 def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0):
@@ -866,7 +1193,9 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
     the tensor compute_level_grid returned to keep the grid in HBM).  Returns ``meshes``
     (SimpleMesh list) and, with ``to_pointcloud``, ``pointclouds`` float64 [B,num_points,3]
     like the reference (an empty mesh gives zeros, :262).  The random stream is a
-    counter-based generator seeded by ``seed`` + the grid index, not numpy's global RNG."""
+    counter-based generator seeded by ``seed`` + the grid index, not numpy's global RNG.
+    With ``opt.eval.min_component_area`` / ``opt.eval.drop_cavities`` set (opt-in) every mesh goes through
+    filter_components first, and the points are sampled on what is left."""
     device = getattr(opt, "device", "cuda")
     meshes, clouds = [], []
     for i, g in enumerate(level_grids):
@@ -874,9 +1203,16 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
         vol = vol.to(device)
         assert vol.shape[0] == vol.shape[1] == vol.shape[2]
         range_min, range_max = opt.eval.range
-        tris, pts = extract_surface(vol, isoval, range_min, range_max,
-                                    opt.eval.num_points if to_pointcloud else 0, seed + i)
-        meshes.append(SimpleMesh(tris))                  # stays in HBM until a dump reads it
+        cleaning = _component_options(opt)
+        if cleaning is None:
+            tris, pts = extract_surface(vol, isoval, range_min, range_max,
+                                        opt.eval.num_points if to_pointcloud else 0, seed + i)
+            mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
+        else:                                            # marching cubes, filter_components, then sampling with the same seed
+            tris, _ = extract_surface(vol, isoval, range_min, range_max)
+            mesh = filter_components(SimpleMesh(tris), *cleaning)
+            pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i) if to_pointcloud else None
+        meshes.append(mesh)
         if to_pointcloud:
             clouds.append(pts.cpu().numpy().astype(np.float64))
     if to_pointcloud:

@@ -91,7 +91,7 @@ def load_options(fname):
 
 # switches that are off unless the command line gives them: absent from the yaml files on purpose, so that the option
 # files (and the options.yaml a run saves) stay what they are
-COMMAND_LINE_ONLY = ("eval.dump_results",)
+COMMAND_LINE_ONLY = ("eval.dump_results", "eval.min_component_area", "eval.drop_cavities")
 
 
 def override_options(opt, opt_over, key_stack=None, safe_check=False):

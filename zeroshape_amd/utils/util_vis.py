@@ -91,6 +91,17 @@ def dump_meshes(opt, idx, name, meshes, folder="dump", normals=False, **_):
             f.write("".join(text))
 
 
+def dump_mesh_reports(opt, idx, name, meshes, folder="dump", **_):
+    """meshes: eval_3D.SimpleMesh objects -> one JSON file each (eval_3D.mesh_report): the totals under trimesh's names -
+    area, volume, euler_number, is_watertight, the vertex, face and component counts - and the per-component table."""
+    import json
+    from . import eval_3D
+    for i, mesh in zip(idx, meshes):
+        with open(_path(opt, folder, i, name, "json"), "w") as f:
+            json.dump(eval_3D.mesh_report(mesh), f, indent=1)
+            f.write("\n")
+
+
 def dump_attentions(opt, idx, name, attn, folder="dump", **_):
     """Per-sample frame lists (what ``compute_level_grid(vis_attn=True)`` returns: [H,W,3] arrays in [0,1]) -> GIF at 50 ms a
     frame like the reference (utils/util_vis.py:93-97).  A tensor (or a list of tensors) of raw maps -> .npy per sample: the
