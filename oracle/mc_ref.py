@@ -211,7 +211,8 @@ def verify_case_tables(table, count):
 
 
 def _fma32(a, b, c):
-    return (np.float64(a) * np.float64(b) + np.float64(c)).astype(np.float32)
+    # (np.asarray, not np.float64(...): a one-element array - one sample - must stay an array, not become a scalar)
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
 
 
 def marching_cubes(vol, iso, scale, offset):

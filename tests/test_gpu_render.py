@@ -275,6 +275,32 @@ def test_mesh_stats_against_numpy(mc_mesh):
     np.testing.assert_array_equal(one[:6], numpy_stats(mc_mesh[5:6].cpu().numpy())[:6].astype(np.float32))
 
 
+@pytest.mark.parametrize("name,n", [("F257", 65535), ("F257", 65536), ("F257", 65537), ("F257", 131073), ("F257", None),
+                                    ("F129", None)])
+def test_mesh_stats_past_one_triangle_per_thread(name, n):
+    """zs_mesh_stats launches at most 256 blocks of 256 threads: up to 65,536 triangles a thread has one (65,535: the last
+    thread none), from 65,537 on the threads stride over the soup, and the final kernel reduces all 256 partials.  Slices
+    of a production-size marching-cubes soup (open surfaces: their signed terms cancel, hence the second term of the bound)."""
+    from tests.test_gpu_mc_full_size import case
+    soup = case(name)[2]
+    soup = soup if n is None else soup[:n]
+    assert soup.is_contiguous() and soup.shape[0] == (n or soup.shape[0]) and soup.shape[0] > (65536 if n is None else 0)
+    tris = soup.cpu().numpy()
+    got = V.mesh_stats(soup)
+    want = numpy_stats(tris)
+    t64 = tris.astype(np.float64)
+    terms = np.abs(np.einsum("ni,ni->n", t64[:, 0], np.cross(t64[:, 1], t64[:, 2]))).sum() / 6.0
+    # one fp32 rounding of the result (2^-24 = 6e-8) + the fp64 accumulation in whatever order (n * 2^-53 = 1.5e-10 of the
+    # terms' magnitudes at 1.3 M triangles, with margin)
+    bound = 1.2e-7 * abs(want[6]) + 1e-9 * terms
+    print("%s[:%s]: %d triangles, volume %.9g (numpy %.9g), |difference| %.3g, bound %.3g"
+          % (name, n, len(tris), got[6], want[6], abs(got[6] - want[6]), bound))
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got[:6], want[:6].astype(np.float32))
+    assert abs(float(got[6]) - want[6]) <= bound
+    np.testing.assert_array_equal(V.mesh_stats(soup).view(np.uint32), got.view(np.uint32))         # fixed-order reduction
+
+
 def test_mc_mesh_turntable_is_deterministic_and_stays_in_view(mc_frames):
     a, b = mc_frames
     for x, y in zip(a, b):

@@ -92,6 +92,54 @@ def _sphere(G, r, c=None):
     return (1.0 / (1.0 + np.exp((d - r) * 20.0))).astype(np.float32), ax     # >0.5 inside, like occ
 
 
+def _noise(G, seed):
+    return np.random.RandomState(seed).uniform(0, 1, (G, G, G)).astype(np.float32)       # every case, incl. ambiguous ones
+
+
+def _three_valued(G, seed):
+    """Corner values exactly ON the iso level 0.5 (never below it): vertices on grid corners, zero-area triangles."""
+    return np.random.RandomState(seed).choice(np.float32([0.0, 0.5, 1.0]), size=(G, G, G)).astype(np.float32)
+
+
+def _non_finite(G, seed):
+    """Noise with one NaN, one +inf and one -inf, away from each other and from the faces."""
+    vol = _noise(G, seed)
+    vol[2, 3, 4], vol[G - 3, 2, G - 2], vol[G // 2, G - 3, 1] = np.nan, np.inf, -np.inf
+    return vol
+
+
+def _wide_range(G, seed):
+    """Values in [-2, 3]: for an iso level and a world range other than the pipeline's 0.5 and (-1.5, 1.5)."""
+    return np.random.RandomState(seed).uniform(-2, 3, (G, G, G)).astype(np.float32)
+
+
+WIDE_ISO, WIDE_RANGE = 0.3, (-0.7, 2.1)          # 0.3 is not a float32: both sides round it the same way or the cases differ
+
+
+def _field_f(G, slab=6, share=0.5):
+    """A sphere of radius 1.7 in the [-1.5, 1.5] box - it cuts all six faces of the grid - with about `share` of the
+    values in the last `slab` k-columns replaced by uniform noise: surface in the first and last cubes of the k-rows (the
+    row ends the count pass reads apart from the rest) and in the first and last i / j slabs."""
+    vol = _sphere(G, 1.7, c=(0.1, -0.05, 0.2))[0]
+    rs = np.random.RandomState(1000 + G)
+    shape = (G, G, slab)
+    noise = rs.uniform(0, 1, shape).astype(np.float32)
+    vol[:, :, G - slab:] = np.where(rs.uniform(0, 1, shape) < share, noise, vol[:, :, G - slab:])
+    return vol
+
+
+def soup_cube_census(tris, G, lo=-1.5, hi=1.5):
+    """How many triangles of a soup of marching_cubes(vol, iso, (hi - lo) / G, lo) lie, strictly, in the last cube of a
+    k-row and in the first / last slab of cubes along i and j.  A triangle of cube index c along an axis has its
+    coordinates in [plane(c), plane(c + 1)]; counted are those inside the slab with a vertex off its inner plane."""
+    scale = np.float32((hi - lo) / G)
+    plane = lambda c: M._fma32(np.float32(c), scale, np.float32(lo))      # noqa: E731  (monotonic in c, as the vertices are)
+    mn, mx = tris.min(axis=1), tris.max(axis=1)                              # [n,3]
+    first = lambda a: int(((mx[:, a] <= plane(1)) & (mn[:, a] < plane(1))).sum())              # noqa: E731
+    last = lambda a: int(((mn[:, a] >= plane(G - 2)) & (mx[:, a] > plane(G - 2))).sum())       # noqa: E731
+    return dict(row_end=last(2), i_first=first(0), i_last=last(0), j_first=first(1), j_last=last(1))
+
+
 def test_sphere_mesh_is_closed_and_accurate():
     G = 17
     vol, ax = _sphere(G, 0.8)
@@ -163,6 +211,56 @@ def test_vectorised_extraction_and_sampling_equal_the_loops_bit_for_bit():
         p2, i2 = M.sample_surface_loop(b, 300, seed=G)
         assert np.array_equal(i1, i2) and np.array_equal(p1.view(np.uint32), p2.view(np.uint32))
     assert len(M.marching_cubes(np.zeros((4, 4, 4), np.float32), 0.5, np.float32(1.0), 0.0)) == 0
+
+
+def test_vectorised_extraction_equals_the_loop_on_level_values_non_finite_values_and_another_level():
+    """The inputs tests/test_gpu_mc_full_size.py adds, at G = 6: corner values exactly on the level (zero-area triangles),
+    a NaN and both infinities (NaN vertices: compared as NaN, everything else bit for bit), and the iso level 0.3 with the
+    world range (-0.7, 2.1)."""
+    G = 6
+    for vol, iso, (lo, hi) in ((_three_valued(G, G), 0.5, (-1.5, 1.5)), (_non_finite(G, G), 0.5, (-1.5, 1.5)),
+                               (_wide_range(G, G), WIDE_ISO, WIDE_RANGE)):
+        scale = np.float32((hi - lo) / G)
+        with np.errstate(all="ignore"):
+            a = M.marching_cubes(vol, iso, scale, lo)
+            b = M.marching_cubes_loop(vol, iso, scale, lo)
+        assert a.shape == b.shape and len(a) > 50
+        nan = np.isnan(a)
+        assert np.array_equal(a, b, equal_nan=True) and np.array_equal(nan, np.isnan(b))
+        assert np.array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan])
+        assert nan.any() == (not np.isfinite(vol).all())
+    tv = M.marching_cubes(_three_valued(G, G), 0.5, np.float32(3.0 / G), -1.5)
+    assert (M.triangle_areas(tv) == 0).sum() > 5
+
+
+def test_vectorised_sampling_equals_the_loop_past_one_scan_tile_with_zero_area_triangles():
+    """300 samples on a soup of more than 2,048 triangles (what the device scans as one tile) that has zero-area ones:
+    the same ids and the same bits, and no id on a triangle without area."""
+    tris = M.marching_cubes(_three_valued(13, 13), 0.5, np.float32(3.0 / 13), -1.5)
+    area = M.triangle_areas(tris)
+    assert len(tris) > 2048 and (area == 0).sum() > 100
+    for seed in (7, 2 ** 64 - 1):
+        p1, i1 = M.sample_surface(tris, 300, seed)
+        p2, i2 = M.sample_surface_loop(tris, 300, seed)
+        assert np.array_equal(i1, i2) and np.array_equal(p1.view(np.uint32), p2.view(np.uint32))
+        assert (area[i1] > 0).all() and i1.max() >= 2048
+
+
+def test_full_size_field_has_surface_at_the_row_ends_and_on_every_face():
+    """_field_f (the volume of the 129^3 and 253^3 .. 258^3 GPU cases), checked small: triangles in the last cube of the
+    k-rows and in the first and last slabs of cubes along i and j; and soup_cube_census counts cubes, not vertices - a
+    closed sphere away from the faces has none there."""
+    G = 33
+    census = soup_cube_census(M.marching_cubes(_field_f(G), 0.5, np.float32(3.0 / G), -1.5), G)
+    assert census["row_end"] > 1000 and min(census.values()) > 100, census
+    inner = soup_cube_census(M.marching_cubes(_sphere(G, 0.8)[0], 0.5, np.float32(3.0 / G), -1.5), G)
+    assert set(inner.values()) == {0}
+    # one triangle in each place, by hand: cube (0, 3, G - 2) and cube (G - 2, 0, 5)
+    P = lambda *v: M._fma32(np.float32(v), np.float32(3.0 / G), np.float32(-1.5))      # noqa: E731
+    t = np.stack([np.stack([P(0.5, 3, G - 2), P(1, 3.5, G - 2), P(1, 3, G - 1.5)]),
+                  np.stack([P(G - 2, 0.5, 5), P(G - 1.5, 0, 5), P(G - 2, 0, 5.5)])]).astype(np.float32)
+    assert soup_cube_census(t[:1], G) == dict(row_end=1, i_first=1, i_last=0, j_first=0, j_last=0)
+    assert soup_cube_census(t[1:], G) == dict(row_end=0, i_first=0, i_last=1, j_first=1, j_last=0)
 
 
 def test_simple_mesh_is_indexed_like_mcubes():
