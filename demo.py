@@ -32,6 +32,15 @@ detached blobs of a single-view reconstruction - and closed inner shells of nega
 --eval.mesh_report=true adds <name>_mesh_report.json next to the .obj: area, volume, Euler number, watertightness and the
 per-component table (faces, vertices, edges, boundary / non-manifold / misoriented edges, area, signed volume) of the mesh
 that was written.
+
+--eval.vertex_colors=true (opt-in, shape task) colours the mesh from the input photo on the GPU (eval_3D.vertex_colors): a
+vertex the input camera saw takes the photo's bilinear texel, every other vertex the colour of the nearest seen one.
+<name>_mesh.obj then has `v x y z r g b` lines (the vertex-colour extension MeshLab, Blender and Open3D read), with --viz
+<name>_mesh_viz.gif is rendered with those colours, and with --eval.mesh_report=true the report gains seen_area_fraction.
+--eval.color_fade=<mesh units> fades copied colours towards the plain material colour with the distance from the seen
+surface (0, the default: no fade), --eval.color_min_cos (0.1) is the smallest cosine between a vertex normal and the ray to the
+camera that still counts as facing it, --eval.color_supersample (2) the z-buffer's resolution over the photo's.  Applied
+after the component filter and the field normals.
 """
 import importlib
 import os
@@ -131,6 +140,7 @@ def main():
     viz = bool(opt.get("viz", False))
     field_normals = bool(opt.eval.get("field_normals", False))
     mesh_report = bool(opt.eval.get("mesh_report", False))
+    colors = eval_3D.color_options(opt)
     for var, name in zip(data_list, name_list):
         with torch.no_grad():
             var = graph.forward(opt, var, training=False, get_loss=False)
@@ -141,13 +151,16 @@ def main():
                 var = marching_cubes(opt, var, graph.impl_network, vis_attn=viz)
                 if field_normals:      # --eval.field_normals=true: <name>_mesh.obj gets `vn` lines, -grad/|grad| of the field
                     eval_3D.field_normals(opt, graph.impl_network, var.latent_depth, var.latent_semantic, var.mesh_pred)
+                if colors is not None:  # --eval.vertex_colors=true: `v x y z r g b` lines, a coloured turntable, the seen fraction
+                    eval_3D.vertex_colors(opt, var, **colors)
                 util_vis.dump_meshes(opt, [name], "mesh", var.mesh_pred, folder='preds',
-                                     normals="field" if field_normals else False)
+                                     normals="field" if field_normals else False, colors=colors is not None)
                 if mesh_report:        # --eval.mesh_report=true: <name>_mesh_report.json, the totals and components of that mesh
                     util_vis.dump_mesh_reports(opt, [name], "mesh_report", var.mesh_pred, folder='preds')
                 if viz:
                     util_vis.dump_attentions(opt, [name], "attn", var.attn_vis, folder='preds')
-                    util_vis.dump_meshes_viz(opt, [name], "mesh_viz", var.mesh_pred, save_frames=False, folder='preds')
+                    util_vis.dump_meshes_viz(opt, [name], "mesh_viz", var.mesh_pred, save_frames=False, folder='preds',
+                                             colors=colors is not None)
             elif opt.task == 'depth':
                 # demo.py:205-214 of the reference; the mask goes to the kernel in place of its `* mask + (1 - mask) * -1`
                 B, _, H, W = var.depth_pred.shape

@@ -10,6 +10,11 @@ files are written - or, with --eval.shard_image (automatic when there are more G
 a share of EVERY image: point ranges of its occupancy grid, one RCCL all-gather, and a share of the pose
 search's rotations (BASELINE config 5: "SDF grid sharded 8-way with RCCL all-gather").
 
+With --eval.dump_results the per-sample dumps take the demo's opt-in switches: --eval.vertex_colors=true (with
+--eval.color_fade=<mesh units>, --eval.color_min_cos, --eval.color_supersample) colours <idx>_mesh.obj and the turntable from
+the input photo on the GPU (eval_3D.vertex_colors), and --eval.mesh_report=true writes <idx>_mesh_report.json, with the
+seen area fraction of a coloured mesh.
+
 ZS_VIRTUAL_RANKS=N (with ZS_DEVICE_OVERRIDE=0 ZS_DIST_BACKEND=gloo) rehearses the N-rank path on one GPU.
 """
 import importlib

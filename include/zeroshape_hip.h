@@ -519,6 +519,60 @@ int zs_render_frames(const float *tris, int n_tris, const float *xform, const fl
                      int frames, int H, int W, float yfov, float znear, const float *base_rgb,
                      uint8_t *rgb, float *depth, int *tri, void *zbuffer, void *stream);
 
+/* The same frames with a colour per triangle corner instead of one base colour:
+ * corner_rgb [n_tris][3][3] uint8 (corner k of triangle t, then r g b; may be NULL when n_tris == 0).
+ * Clear and scatter are zs_render_frames': depth and tri are the same bits.  The resolve recomputes
+ * the winner's projected corners and w0, w1, w2 at the pixel centre exactly as the scatter did and
+ * interpolates the albedo perspective-correctly in fp64, a = (sum w_k / z_k c_k / 255) / (sum w_k / z_k);
+ * the pixel is floor(255 a (0.3 + 0.7 |n . l|) + 0.5); the background is white. */
+int zs_render_frames_colored(const float *tris, int n_tris, const float *xform, const float *cams,
+                             int frames, int H, int W, float yfov, float znear, const uint8_t *corner_rgb,
+                             uint8_t *rgb, float *depth, int *tri, void *zbuffer, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Vertex colours of a predicted mesh from the input photo (csrc/mesh_colors.hip;
+ * eval_3D.mesh_vertex_colors_host restates all of it in float64 numpy, operation for operation, and
+ * defines it).  The mesh is the weld's: vertices [n_verts][3] fp32, faces [n_tris][3] int32, normals
+ * [n_verts][3] fp32 (area weighted).  It lives in the normalised frame of the input camera: vertex v
+ * sits at X = v scale + mean in the camera and projects through K (device: K[9] row-major, mean[3],
+ * scale[1], fp32).  image [3][H][W] fp32 planar in [0, 1], mask [H][W] fp32; pixel (row i, col j) is
+ * at (u, w) = (j, i).  Geometry in fp64 from the fp32 inputs, only + - * / sqrt floor and comparisons.
+ *   seen    : p = K X, Z = p_z, u = p_x / p_z, w = p_y / p_z.  A z-buffer of ss H x ss W words in that
+ *             camera by the rules of zs_render_frames' scatter (raster coordinates (u + 0.5) ss,
+ *             (w + 0.5) ss; a face with a Z not > 0 or not finite is skipped whole).  A vertex is seen iff
+ *             Z > 0 and finite, 0 <= u <= W - 1, 0 <= w <= H - 1; n . (-X) > min_cos |n| |X| (a zero or
+ *             non-finite n fails); the four mask texels of its bilinear footprint (j0 = min(floor(u),
+ *             max(W - 2, 0)), j1 = min(j0 + 1, W - 1), rows likewise) are > 0.5; and the z-buffer word at
+ *             (min(floor((w + 0.5) ss), ss H - 1), min(floor((u + 0.5) ss), ss W - 1)) is 0, or names a
+ *             face that holds the vertex, or Z <= (double)depth + depth_tol scale.  depth_tol is in
+ *             mesh units.  Writes seen [n_verts] uint8, colors [n_verts][3] uint8 (the bilinear
+ *             texel, floor(255 c + 0.5) clamped; 0 for a hidden vertex until the fill), source
+ *             [n_verts] int32 (the vertex itself, -1 when hidden), *n_seen (device int: the caller reads
+ *             these 4 bytes) and fraction[2] fp64 = the area of the faces whose three vertices are
+ *             seen, and the total area (fixed-order block reduction, no float atomics).
+ *   compact : after the caller has read n_seen, with the SAME workspace untouched in between:
+ *             seen_idx [n_seen] / seen_xyz [n_seen][3] and hidden_idx / hidden_xyz [n_verts - n_seen],
+ *             the vertex indices and positions in ascending vertex order.  The caller then finds the
+ *             nearest seen vertex of every hidden one with zs_chamfer_forward_ws (xyz1 = hidden,
+ *             xyz2 = seen, b = 1: squared distance, the lowest index among equal minima).
+ *   fill    : hidden vertex k of the list takes the colour of seen_idx[nearest[k]], faded towards
+ *             base_rgb [host][3]: t = fade > 0 ? min(sqrt(dist[k]) / fade, 1) : 0, c = (1 - t) c_nn + t 255 base
+ *             on the uint8 c_nn, floor(c + 0.5) clamped; source = that seen vertex.  With n_seen == 0
+ *             (seen_idx, nearest and dist may be NULL) every vertex gets 255 base and source -1.
+ * workspace: zs_mesh_colors_workspace_bytes(n_verts, n_tris, H, W, ss) bytes, 8-byte aligned (0 for an
+ * empty mesh and beyond the limits n_verts, n_tris <= 2^29, ss H and ss W <= 16384).  n_verts == 0
+ * returns 1 and touches nothing.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_colors_workspace_bytes(int n_verts, int n_tris, int H, int W, int ss);
+int zs_mesh_colors_seen(const float *vertices, const int *faces, const float *normals, int n_verts, int n_tris,
+                        const float *image, const float *mask, int H, int W, const float *K, const float *mean,
+                        const float *scale, int ss, double depth_tol, double min_cos, uint8_t *colors, uint8_t *seen,
+                        int *source, int *n_seen, double *fraction, void *workspace, void *stream);
+int zs_mesh_colors_compact(const float *vertices, const uint8_t *seen, int n_verts, int n_seen, const void *workspace,
+                           int *seen_idx, float *seen_xyz, int *hidden_idx, float *hidden_xyz, void *stream);
+int zs_mesh_colors_fill(const int *hidden_idx, const int *seen_idx, const int *nearest, const float *dist, int n_verts,
+                        int n_seen, double fade, const float *base_rgb, uint8_t *colors, int *source, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Seen-surface mesh (replaces create_seen_surface, utils/util_vis.py:137-170): the textured
  * mesh of the surface the camera sees, from a camera-frame point map, in the reference's order.

@@ -115,7 +115,15 @@ SIGNATURES = {
     "zs_render_zbuffer_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
     "zs_render_frames": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_float), _c_void_p, _c_int, _c_int, _c_int, _c_float,
                                   _c_float, ctypes.POINTER(_c_float), _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "zs_seen_mesh_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+    "zs_render_frames_colored": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_float), _c_void_p, _c_int, _c_int, _c_int, _c_float,
+                                          _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_colors_workspace_bytes": (_c_size_t, [_c_int] * 5),
+    "zs_mesh_colors_seen": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int,
+                                     _c_void_p, _c_void_p, _c_void_p, _c_int, _c_double, _c_double] + [_c_void_p] * 7),
+    "zs_mesh_colors_compact": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int] + [_c_void_p] * 6),
+    "zs_mesh_colors_fill": (_c_int, [_c_void_p] * 4 + [_c_int, _c_int, _c_double, ctypes.POINTER(_c_float), _c_void_p, _c_void_p,
+                                                       _c_void_p]),
+    "zs_seen_mesh_workspace_bytes":(_c_size_t, [_c_int, _c_int, _c_int]),
     "zs_seen_mesh": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float] + [_c_void_p] * 7),
     "zs_intr_param2mtx": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "zs_unproj_depth": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),

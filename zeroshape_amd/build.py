@@ -47,6 +47,8 @@ EXTRA = {
     "field_normals.hip": ["-ffp-contract=off"],
     # fp64 area / volume terms equal, term for term, to the numpy restatement in utils/eval_3D.py (mesh_components_host)
     "mesh_components.hip": ["-ffp-contract=off"],
+    # fp64 projection, z-buffer, seen test and colours equal to the numpy restatement in utils/eval_3D.py (mesh_vertex_colors_host)
+    "mesh_colors.hip": ["-ffp-contract=off"],
 }
 
 

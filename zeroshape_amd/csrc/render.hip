@@ -222,6 +222,67 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_resolve_kernel(const fl
     if (tri) tri[q] = t;
 }
 
+// The resolve of zs_render_frames_colored: the same winner, depth, normal and light, but the albedo is interpolated from
+// the winner's three corner colours instead of one base colour.  The projected corners and w0, w1, w2 at the pixel centre are
+// recomputed exactly as the scatter computed them (the same operations on the same inputs: the same bits), and the albedo is
+// perspective correct in fp64: a = (sum w_k / z_k c_k / 255) / (sum w_k / z_k).  A kernel of its own, so that the uncoloured
+// frames cannot change.
+__global__ __launch_bounds__(RENDER_THREADS) void render_resolve_colored_kernel(const float *__restrict__ tris, RenderXform xf,
+                                                                                const float *__restrict__ cams, RenderView vw,
+                                                                                long long pixels,
+                                                                                const uint8_t *__restrict__ corner_rgb,
+                                                                                const unsigned long long *__restrict__ zbuf,
+                                                                                uint8_t *__restrict__ rgb, float *__restrict__ depth,
+                                                                                int *__restrict__ tri) {
+    const long long q = (long long)blockIdx.x * RENDER_THREADS + threadIdx.x;
+    if (q >= pixels) return;
+    const unsigned long long key = zbuf[q];
+    uint8_t out[3] = {255, 255, 255};
+    float d = INFINITY;
+    int t = -1;
+    if (key) {
+        t = (int)~(unsigned)key;
+        d = __uint_as_float(~(unsigned)(key >> 32));
+        const long long hw = (long long)vw.H * vw.W;
+        const int f = (int)(q / hw), rem = (int)(q - (long long)f * hw), i = rem / vw.W, j = rem - i * vw.W;
+        double v[3][3];
+        camera_triangle(tris, t, xf, cams + (size_t)f * 12, v);
+        double z[3], x[3], y[3];
+        for (int k = 0; k < 3; ++k) {
+            z[k] = -v[k][2];
+            x[k] = (v[k][0] / (z[k] * vw.ta) + 1.0) * vw.half_w;
+            y[k] = (1.0 - v[k][1] / (z[k] * vw.tn)) * vw.half_h;
+        }
+        const double area = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0]);
+        const double px = (double)j + 0.5, py = (double)i + 0.5;
+        const double w0 = ((x[2] - x[1]) * (py - y[1]) - (y[2] - y[1]) * (px - x[1])) / area;
+        const double w1 = ((x[0] - x[2]) * (py - y[2]) - (y[0] - y[2]) * (px - x[2])) / area;
+        const double w2 = ((x[1] - x[0]) * (py - y[0]) - (y[1] - y[0]) * (px - x[0])) / area;
+        const double q0 = w0 / z[0], q1 = w1 / z[1], q2 = w2 / z[2];
+        const double den = q0 + q1 + q2;
+        const double e1[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]};
+        const double e2[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
+        const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+        const double dx = (((double)j + 0.5) / vw.half_w - 1.0) * vw.ta, dy = (1.0 - ((double)i + 0.5) / vw.half_h) * vw.tn;
+        const double nn = sqrt(nx * nx + ny * ny + nz * nz), ll = sqrt(dx * dx + dy * dy + 1.0);
+        const double ndl = nn > 0.0 ? fabs(nz - nx * dx - ny * dy) / (nn * ll) : 0.0;
+        const double shade = 0.3 + 0.7 * ndl;
+        const uint8_t *c = corner_rgb + (size_t)t * 9;
+        // (xf.swap exchanges corners 1 and 2 of the triangle: their colours go with them)
+        const int c1 = xf.swap ? 2 : 1, c2 = xf.swap ? 1 : 2;
+        for (int ch = 0; ch < 3; ++ch) {
+            const double a = (q0 * ((double)c[ch] / 255.0) + q1 * ((double)c[c1 * 3 + ch] / 255.0) + q2 * ((double)c[c2 * 3 + ch] / 255.0)) / den;
+            const double p = floor(255.0 * a * shade + 0.5);
+            out[ch] = (uint8_t)(p >= 0.0 ? fmin(p, 255.0) : 0.0);
+        }
+    }
+    rgb[q * 3 + 0] = out[0];
+    rgb[q * 3 + 1] = out[1];
+    rgb[q * 3 + 2] = out[2];
+    if (depth) depth[q] = d;
+    if (tri) tri[q] = t;
+}
+
 constexpr int RENDER_MAX_FRAMES = 65535;   // frames ride on blockIdx.y
 constexpr int RENDER_MAX_SIDE = 16384;
 
@@ -269,29 +330,33 @@ extern "C" size_t zs_render_zbuffer_bytes(int frames, int H, int W) {
     return (size_t)frames * H * W * sizeof(unsigned long long);
 }
 
-extern "C" int zs_render_frames(const float *tris, int n_tris, const float *xform, const float *cams, int frames, int H,
-                                int W, float yfov, float znear, const float *base_rgb, uint8_t *rgb, float *depth, int *tri,
-                                void *zbuffer, void *stream) {
+namespace {
+
+// zs_render_frames (corner_rgb == NULL: one base colour) and zs_render_frames_colored (base_rgb == NULL): the same checks, clear
+// and scatter; only the resolve kernel differs
+int render_frames(const char *who, const float *tris, int n_tris, const float *xform, const float *cams, int frames, int H, int W,
+                  float yfov, float znear, const float *base_rgb, const uint8_t *corner_rgb, uint8_t *rgb, float *depth, int *tri,
+                  void *zbuffer, void *stream) {
     if (n_tris < 0 || !render_dims_ok(frames, H, W)) {
-        zs::set_err("zs_render_frames: bad size (n_tris=%d frames=%d H=%d W=%d)", n_tris, frames, H, W);
+        zs::set_err("%s: bad size (n_tris=%d frames=%d H=%d W=%d)", who, n_tris, frames, H, W);
         return 0;
     }
     if (!(yfov > 0.0f && yfov < 3.14159f) || !(znear > 0.0f)) {
-        zs::set_err("zs_render_frames: bad camera (yfov=%g znear=%g)", (double)yfov, (double)znear);
+        zs::set_err("%s: bad camera (yfov=%g znear=%g)", who, (double)yfov, (double)znear);
         return 0;
     }
     const long long pixels = (long long)frames * H * W;
     if (pixels > 0x7fffffffLL * RENDER_THREADS) {
-        zs::set_err("zs_render_frames: %lld pixels exceed one launch", pixels);
+        zs::set_err("%s: %lld pixels exceed one launch", who, pixels);
         return 0;
     }
     if (frames == 0) return 1;
-    if (!xform || !cams || !base_rgb || !rgb || !zbuffer || (n_tris > 0 && !tris)) {
-        zs::set_err("zs_render_frames: null pointer");
+    if (!xform || !cams || (!base_rgb && !corner_rgb) || !rgb || !zbuffer || (n_tris > 0 && !tris)) {
+        zs::set_err("%s: null pointer", who);
         return 0;
     }
     if (reinterpret_cast<uintptr_t>(zbuffer) & 7) {
-        zs::set_err("zs_render_frames: zbuffer must be 8-byte aligned");
+        zs::set_err("%s: zbuffer must be 8-byte aligned", who);
         return 0;
     }
     RenderXform xf;
@@ -315,7 +380,33 @@ extern "C" int zs_render_frames(const float *tris, int n_tris, const float *xfor
     if (n_tris > 0)
         hipLaunchKernelGGL(render_scatter_kernel, dim3((unsigned)(((long long)n_tris + RENDER_THREADS - 1) / RENDER_THREADS), (unsigned)frames),
                            dim3(RENDER_THREADS), 0, s, tris, n_tris, xf, cams, vw, zbuf);
-    hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((pixels + RENDER_THREADS - 1) / RENDER_THREADS)), dim3(RENDER_THREADS),
-                       0, s, tris, xf, cams, vw, pixels, base_rgb[0], base_rgb[1], base_rgb[2], zbuf, rgb, depth, tri);
-    return zs::check_launch("zs_render_frames") ? 1 : 0;
+    const dim3 pgrid((unsigned)((pixels + RENDER_THREADS - 1) / RENDER_THREADS));
+    if (corner_rgb)
+        hipLaunchKernelGGL(render_resolve_colored_kernel, pgrid, dim3(RENDER_THREADS), 0, s, tris, xf, cams, vw, pixels, corner_rgb,
+                           zbuf, rgb, depth, tri);
+    else
+        hipLaunchKernelGGL(render_resolve_kernel, pgrid, dim3(RENDER_THREADS), 0, s, tris, xf, cams, vw, pixels, base_rgb[0],
+                           base_rgb[1], base_rgb[2], zbuf, rgb, depth, tri);
+    return zs::check_launch(who) ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" int zs_render_frames(const float *tris, int n_tris, const float *xform, const float *cams, int frames, int H,
+                                int W, float yfov, float znear, const float *base_rgb, uint8_t *rgb, float *depth, int *tri,
+                                void *zbuffer, void *stream) {
+    return render_frames("zs_render_frames", tris, n_tris, xform, cams, frames, H, W, yfov, znear, base_rgb, nullptr, rgb, depth, tri,
+                         zbuffer, stream);
+}
+
+extern "C" int zs_render_frames_colored(const float *tris, int n_tris, const float *xform, const float *cams, int frames, int H,
+                                        int W, float yfov, float znear, const uint8_t *corner_rgb, uint8_t *rgb, float *depth,
+                                        int *tri, void *zbuffer, void *stream) {
+    if (!corner_rgb && n_tris > 0 && frames > 0 && render_dims_ok(frames, H, W)) {
+        zs::set_err("zs_render_frames_colored: null pointer");
+        return 0;
+    }
+    static const float white[3] = {1.0f, 1.0f, 1.0f};             // (n_tris == 0: white frames, no corner is read)
+    return render_frames("zs_render_frames_colored", tris, n_tris, xform, cams, frames, H, W, yfov, znear,
+                         corner_rgb ? nullptr : white, corner_rgb, rgb, depth, tri, zbuffer, stream);
 }

@@ -447,8 +447,14 @@ class Runner:
         idx = torch.as_tensor(var.idx).view(-1).tolist()
         util_vis.dump_images(opt, idx, "image_input", var.rgb_input_map, masks=None, from_range=(0, 1), folder=folder)
         util_vis.dump_images(opt, idx, "mask_input", var.mask_input_map, folder=folder)
-        util_vis.dump_meshes(opt, idx, "mesh", var.mesh_pred, folder=folder)
-        util_vis.dump_meshes_viz(opt, idx, "mesh_viz", var.mesh_pred, folder=folder)           # image frames + gif
+        colors = eval_3D.color_options(opt)           # --eval.vertex_colors=true: the photo on the mesh, .obj and turntable alike
+        if colors is not None and 'depth_pred' in var:
+            eval_3D.vertex_colors(opt, var, **colors)
+        colored = colors is not None and 'depth_pred' in var
+        util_vis.dump_meshes(opt, idx, "mesh", var.mesh_pred, folder=folder, colors=colored)
+        util_vis.dump_meshes_viz(opt, idx, "mesh_viz", var.mesh_pred, folder=folder, colors=colored)   # image frames + gif
+        if bool(opt.eval.get("mesh_report", False)):
+            util_vis.dump_mesh_reports(opt, idx, "mesh_report", var.mesh_pred, folder=folder)
         if 'depth_pred' in var:
             util_vis.dump_depths(opt, idx, "depth_est", var.depth_pred, var.mask_input_map, rescale=True, folder=folder)
         if 'depth_input_map' in var:

@@ -30,6 +30,7 @@ import torch
 
 from ..external.chamfer3D.dist_chamfer_3D import chamfer_3DDist
 from .camera import get_rotation_sphere
+from .util_vis import BASE_RGB
 
 
 class _GridInfo(object):
@@ -674,6 +675,10 @@ class SimpleMesh(object):
         # again), the field's normals [V,3] fp32 on the device, and the device count [1] int32 of vertices that fell back
         self._device_weld = self.device_field_normals = self.field_normal_fallbacks = self._field_normals = None
         self._components = None                          # mesh_components(self), cached by the ``components`` property
+        # set by mesh_vertex_colors(): colours uint8 [V,3], seen flags uint8 [V], colour sources int32 [V] and (seen area, total
+        # area) fp64 [2] on the device, and the host copies the properties below make when read
+        self.device_vertex_colors = self.device_vertex_seen = self.device_color_source = self.device_seen_area = None
+        self._vertex_colors = self._vertex_seen = self._seen_area = None
         if isinstance(triangles, torch.Tensor) and triangles.is_cuda:
             self.device_triangles = triangles.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
         else:
@@ -760,6 +765,39 @@ class SimpleMesh(object):
         if self._field_normals is None:
             self._field_normals = self.device_field_normals.cpu().numpy()
         return self._field_normals
+
+
+    def _colored(self, what):
+        if self.device_vertex_colors is None:
+            raise ValueError("this mesh has no %s: eval_3D.vertex_colors(opt, var) or eval_3D.mesh_vertex_colors(mesh, ...) "
+                             "computes them" % what)
+
+    @property
+    def vertex_colors(self):
+        """[v,3] uint8, the rows of ``vertices``: the input photo where the input camera saw the vertex, the colour of the
+        nearest seen vertex elsewhere, computed by mesh_vertex_colors() (on the device until read here)."""
+        self._colored("vertex colours")
+        if self._vertex_colors is None:
+            self._vertex_colors = self.device_vertex_colors.cpu().numpy()
+        return self._vertex_colors
+
+    @property
+    def vertex_seen(self):
+        """[v] bool: whether the input camera saw the vertex (mesh_vertex_colors_host's rule)."""
+        self._colored("seen flags")
+        if self._vertex_seen is None:
+            self._vertex_seen = self.device_vertex_seen.cpu().numpy().astype(bool)
+        return self._vertex_seen
+
+    @property
+    def seen_area_fraction(self):
+        """The area of the faces whose three vertices the input camera saw over the mesh's area (float; 0.0 for a mesh
+        without area)."""
+        self._colored("seen area")
+        if self._seen_area is None:
+            self._seen_area = self.device_seen_area.cpu().numpy()
+        seen, total = self._seen_area
+        return float(seen / total) if total > 0.0 else 0.0
 
 
 def mesh_to_field_points_host(vertices, range_min, G):
@@ -1116,11 +1154,284 @@ def filter_components(mesh, min_component_area=None, drop_cavities=False, keep=N
 
 def mesh_report(mesh):
     """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
-    per-component table."""
+    per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``."""
     comps = mesh.components
-    return dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
-                area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
-                component_table=comps.table())
+    report = dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
+                  area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
+                  component_table=comps.table())
+    if getattr(mesh, "device_vertex_colors", None) is not None:
+        report["seen_area_fraction"] = mesh.seen_area_fraction
+    return report
+
+
+# ---- vertex colours from the input photo (csrc/mesh_colors.hip) ----
+
+# Design choices, not measurements: a vertex counts as facing the camera when the cosine between its normal and the ray to
+# the camera exceeds COLOR_MIN_COS (grazing vertices would smear texels along the silhouette), and as unoccluded when it lies
+# within COLOR_DEPTH_TOL_CELLS marching-cubes cells (mesh units: cells * (range_max - range_min) / vox_res) behind the nearest
+# surface of its z-buffer texel (a face is at most one cell across, so a vertex's own neighbourhood passes).
+COLOR_MIN_COS = 0.1
+COLOR_DEPTH_TOL_CELLS = 1.5
+
+
+def default_color_depth_tol(opt):
+    """The occlusion tolerance of vertex_colors in mesh units: COLOR_DEPTH_TOL_CELLS cells of the evaluation grid."""
+    range_min, range_max = opt.eval.range
+    return COLOR_DEPTH_TOL_CELLS * (float(range_max) - float(range_min)) / float(opt.eval.vox_res)
+
+
+def _round_u8(x):
+    """floor(x + 0.5) clamped to [0, 255] as uint8, NaN -> 0: col_round of csrc/mesh_colors.hip."""
+    with np.errstate(invalid="ignore"):
+        r = np.floor(np.asarray(x, np.float64) + 0.5)
+        return np.where(r >= 0.0, np.minimum(r, 255.0), 0.0).astype(np.uint8)
+
+
+def _fma32(a, b, c):
+    """fmaf(a, b, c) on float32 arrays, correctly rounded: the product is exact in float64, the sum is rounded to odd in
+    float64 (the rounded sum moved, when inexact and even, to its neighbour on the side of the exact value - found with the
+    TwoSum error term), and a round-to-odd value with 53 >= 2 * 24 + 2 bits rounds to float32 like the exact one."""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        move = np.isfinite(s) & np.isfinite(err) & (err != 0.0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(move, np.nextafter(s, np.where(err > 0.0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def nearest_point_host(queries, candidates, block=1 << 22):
+    """For every query [n,3] the nearest candidate [m,3] (m > 0) by zs_chamfer_forward_ws's rule, brute force: float32
+    (dx, dy, dz) = candidate - query, d = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), the lowest index among equal minima ->
+    (squared distance float32 [n], index int32 [n])."""
+    q = np.asarray(queries, np.float32).reshape(-1, 3)
+    c = np.asarray(candidates, np.float32).reshape(-1, 3)
+    dist, index = np.zeros(len(q), np.float32), np.zeros(len(q), np.int32)
+    rows = max(1, block // max(len(c), 1))
+    for lo in range(0, len(q), rows):
+        d3 = c[None, :, :] - q[lo:lo + rows, None, :]
+        d = _fma32(d3[..., 2], d3[..., 2], _fma32(d3[..., 1], d3[..., 1], d3[..., 0] * d3[..., 0]))
+        best = np.argmin(d, axis=1)                               # (the first minimum: the lowest index)
+        index[lo:lo + rows] = best
+        dist[lo:lo + rows] = d[np.arange(len(best)), best]
+    return dist, index
+
+
+def mesh_vertex_colors_host(vertices, faces, normals, image, mask, intr, mean, scale, depth_tol, min_cos=COLOR_MIN_COS,
+                            supersample=2, fade=0.0, base_rgb=BASE_RGB):
+    """The definition of mesh_vertex_colors and the checker of csrc/mesh_colors.hip: float64 numpy from the float32 inputs,
+    operation for operation (the kernels are built without contraction, so the outputs are equal, not close).
+    ``vertices`` [V,3], ``faces`` [F,3], ``normals`` [V,3] (the weld's, area weighted), ``image`` [3,H,W] in [0,1], ``mask``
+    [H,W], ``intr`` [3,3], ``mean`` [3], ``scale`` scalar -> dict: colors uint8 [V,3], seen uint8 [V], source int32 [V],
+    seen_area / total_area (float), u, w, Z float64 [V].
+
+    A. X = v scale + mean, p = K X, Z = p_z, u = p_x / p_z, w = p_y / p_z; pixel (row i, col j) is at (u, w) = (j, i).
+    B. A z-buffer of ss H x ss W in that camera, a plain loop over the faces in index order: raster coordinates (u + 0.5) ss,
+       (w + 0.5) ss, pixel centres (j + 0.5, i + 0.5), coverage inclusive on every edge, faces with a Z not > 0 or not finite
+       or with zero / NaN / overflowing area skipped whole, depth 1 / (sum w_k / Z_k) rounded to float32, the nearest depth
+       wins and at equal depth the lower face index.
+    C. Seen iff Z > 0 and finite, 0 <= u <= W - 1, 0 <= w <= H - 1; n . (-X) > min_cos |n| |X| (a zero or non-finite n fails);
+       the four mask texels of the bilinear footprint are > 0.5; and the z-buffer texel of (u, w) is empty, or holds a face of
+       this vertex, or Z <= depth + depth_tol scale.  Colour: bilinear, floor(255 c + 0.5) clamped.
+    D/E. A hidden vertex takes the colour of the nearest seen vertex in mesh space (nearest_point_host), faded towards
+       ``base_rgb`` by t = min(sqrt(dist) / fade, 1) (fade 0: t = 0): floor((1 - t) c_nn + t 255 base + 0.5) clamped.  When no
+       vertex is seen every vertex gets 255 base and source -1."""
+    f64 = np.float64
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    n = np.asarray(normals, np.float32).reshape(-1, 3).astype(f64)
+    img = np.asarray(image, np.float32).astype(f64)
+    msk = np.asarray(mask, np.float32).reshape(img.shape[1:])
+    K = np.asarray(intr, np.float32).reshape(3, 3).astype(f64)
+    mu = np.asarray(mean, np.float32).reshape(3).astype(f64)
+    s = f64(np.asarray(scale, np.float32).reshape(-1)[0])
+    base = np.asarray(base_rgb, np.float32).reshape(3).astype(f64)
+    depth_tol, min_cos, fade, ss = f64(depth_tol), f64(min_cos), f64(fade), int(supersample)
+    H, W = img.shape[1:]
+    Hz, Wz = H * ss, W * ss
+    V = len(v32)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        X = v32.astype(f64) * s + mu
+        p = [K[r, 0] * X[:, 0] + K[r, 1] * X[:, 1] + K[r, 2] * X[:, 2] for r in range(3)]
+        Z, u, w = p[2], p[0] / p[2], p[1] / p[2]
+        # B
+        zdepth, zface = np.full((Hz, Wz), np.inf, np.float32), np.full((Hz, Wz), -1, np.int64)
+        xr, yr = (u + 0.5) * f64(ss), (w + 0.5) * f64(ss)
+        for t in range(len(f)):
+            idx = f[t]
+            z, x, y = Z[idx], xr[idx], yr[idx]
+            if not np.all((z > 0.0) & (z <= 1.7e308)):
+                continue
+            area = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0])
+            if not abs(area) > 0.0 or not abs(area) <= 1.0e300:
+                continue
+            j0, j1 = int(min(max(np.ceil(x.min() - 0.5), 0.0), Wz)), int(max(min(np.floor(x.max() - 0.5), Wz - 1.0), -1.0))
+            i0, i1 = int(min(max(np.ceil(y.min() - 0.5), 0.0), Hz)), int(max(min(np.floor(y.max() - 0.5), Hz - 1.0), -1.0))
+            if i1 < i0 or j1 < j0:
+                continue
+            py, px = (np.arange(i0, i1 + 1, dtype=f64) + 0.5)[:, None], (np.arange(j0, j1 + 1, dtype=f64) + 0.5)[None, :]
+            w0 = ((x[2] - x[1]) * (py - y[1]) - (y[2] - y[1]) * (px - x[1])) / area
+            w1 = ((x[0] - x[2]) * (py - y[2]) - (y[0] - y[2]) * (px - x[2])) / area
+            w2 = ((x[1] - x[0]) * (py - y[0]) - (y[1] - y[0]) * (px - x[0])) / area
+            d = (1.0 / (w0 / z[0] + w1 / z[1] + w2 / z[2])).astype(np.float32)
+            hit = (w0 >= 0.0) & (w1 >= 0.0) & (w2 >= 0.0) & (d > 0.0) & (d <= np.float32(3.0e38))
+            sub_d, sub_f = zdepth[i0:i1 + 1, j0:j1 + 1], zface[i0:i1 + 1, j0:j1 + 1]
+            hit &= d < sub_d                                      # (ascending faces: a tie keeps the lower index)
+            sub_d[hit], sub_f[hit] = d[hit], t
+        # C
+        ok = (Z > 0.0) & (Z <= 1.7e308) & (u >= 0.0) & (u <= f64(W - 1)) & (w >= 0.0) & (w <= f64(H - 1))
+        dvec = -X
+        nn = np.sqrt(n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2])
+        dd = np.sqrt(dvec[:, 0] * dvec[:, 0] + dvec[:, 1] * dvec[:, 1] + dvec[:, 2] * dvec[:, 2])
+        dot = n[:, 0] * dvec[:, 0] + n[:, 1] * dvec[:, 1] + n[:, 2] * dvec[:, 2]
+        ok &= (nn > 0.0) & (nn <= 1.7e308) & (dot > min_cos * nn * dd)
+        us, ws = np.where(ok, u, 0.0), np.where(ok, w, 0.0)       # (indices only of vertices still in the running)
+        j0 = np.minimum(np.floor(us).astype(np.int64), max(W - 2, 0))
+        i0 = np.minimum(np.floor(ws).astype(np.int64), max(H - 2, 0))
+        j1, i1 = np.minimum(j0 + 1, W - 1), np.minimum(i0 + 1, H - 1)
+        half = np.float32(0.5)
+        ok &= (msk[i0, j0] > half) & (msk[i0, j1] > half) & (msk[i1, j0] > half) & (msk[i1, j1] > half)
+        fu, fv = us - j0.astype(f64), ws - i0.astype(f64)
+        colors = np.zeros((V, 3), np.uint8)
+        for c in range(3):
+            t00, t01, t10, t11 = img[c][i0, j0], img[c][i0, j1], img[c][i1, j0], img[c][i1, j1]
+            val = (1.0 - fv) * ((1.0 - fu) * t00 + fu * t01) + fv * ((1.0 - fu) * t10 + fu * t11)
+            colors[:, c] = _round_u8(255.0 * val)
+        jz = np.minimum(np.floor((us + 0.5) * f64(ss)).astype(np.int64), Wz - 1)
+        iz = np.minimum(np.floor((ws + 0.5) * f64(ss)).astype(np.int64), Hz - 1)
+        win_f, win_d = zface[iz, jz], zdepth[iz, jz].astype(f64)
+        own = (f[np.maximum(win_f, 0)] == np.arange(V)[:, None]).any(axis=1) if len(f) else np.zeros(V, bool)
+        ok &= (win_f < 0) | own | (Z <= win_d + depth_tol * s)
+        colors[~ok] = 0
+        # fraction
+        tri = v32.astype(f64)[f]
+        e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+        nx, ny, nz = (e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                      e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0])
+        area = 0.5 * np.sqrt(nx * nx + ny * ny + nz * nz)
+        seen_area, total_area = float(area[ok[f].all(axis=1)].sum()), float(area.sum())
+        # D, E
+        source = np.where(ok, np.arange(V), -1).astype(np.int32)
+        seen_ids, hidden_ids = np.flatnonzero(ok), np.flatnonzero(~ok)
+        if len(hidden_ids):
+            if len(seen_ids) == 0:
+                colors[:] = _round_u8(255.0 * base)
+            else:
+                dist, near = nearest_point_host(v32[hidden_ids], v32[seen_ids])
+                src = seen_ids[near]
+                t = np.minimum(np.sqrt(dist.astype(f64)) / fade, 1.0) if fade > 0.0 else np.zeros(len(src), f64)
+                t = np.where(t <= 1.0, t, 1.0)
+                colors[hidden_ids] = _round_u8((1.0 - t)[:, None] * colors[src].astype(f64) + t[:, None] * (255.0 * base)[None, :])
+                source[hidden_ids] = src
+    return dict(colors=colors, seen=ok.astype(np.uint8), source=source, seen_area=seen_area, total_area=total_area, u=u, w=w, Z=Z)
+
+
+@torch.no_grad()
+def mesh_vertex_colors(mesh, image, mask, intr, mean, scale, depth_tol, min_cos=COLOR_MIN_COS, supersample=2, fade=0.0,
+                       base_rgb=BASE_RGB):
+    """Colours one GPU SimpleMesh from the photo it was predicted from (the semantics: mesh_vertex_colors_host), on the current
+    stream: ``image`` [3,H,W] fp32 in [0,1], ``mask`` H*W values, ``intr`` [3,3], ``mean`` [3], ``scale`` one value - GPU tensors,
+    one sample of var.rgb_input_map / mask_input_map / intr_pred and of seen_surface's normalisation.  ``depth_tol`` and
+    ``fade`` are in mesh units.  Reuses the weld the mesh carries (``_device_weld``) or welds with normals and keeps it.
+    zs_mesh_colors_seen, the 4-byte read-back of the seen count, zs_mesh_colors_compact, the library's own nearest-neighbour
+    search (zs_chamfer_forward_ws: hidden against seen) and zs_mesh_colors_fill.  Stores ``mesh.device_vertex_colors`` uint8
+    [V,3], ``device_vertex_seen`` uint8 [V], ``device_color_source`` int32 [V] (the vertex itself when seen, the vertex it
+    copied from when hidden, -1 when nothing is seen) and ``device_seen_area`` fp64 [2] (seen area, total area), all on the
+    device until read through ``vertex_colors`` / ``vertex_seen`` / ``seen_area_fraction``.  A host-built mesh or CPU tensors
+    raise ValueError: there is no CPU path.  -> mesh."""
+    import ctypes
+    from .. import _lib
+    if getattr(mesh, "device_triangles", None) is None:
+        raise ValueError("mesh_vertex_colors: the mesh was built from a host array; there is no CPU path")
+    tensors = dict(image=image, mask=mask, intr=intr, mean=mean, scale=scale)
+    for name, t in tensors.items():
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ValueError("mesh_vertex_colors: %s must be a GPU tensor; there is no CPU path" % name)
+    image, mask, intr, mean, scale = [_gpu_f32(tensors[k], k) for k in ("image", "mask", "intr", "mean", "scale")]
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError("mesh_vertex_colors: image must be [3,H,W], got %s" % (tuple(image.shape),))
+    H, W = int(image.shape[1]), int(image.shape[2])
+    if mask.numel() != H * W or intr.numel() != 9 or mean.numel() != 3 or scale.numel() != 1:
+        raise ValueError("mesh_vertex_colors: mask must hold H*W values, intr 9, mean 3 and scale 1")
+    ss = int(supersample)
+    if ss < 1:
+        raise ValueError("mesh_vertex_colors: supersample must be >= 1, got %r" % (supersample,))
+    lib = _lib.load()
+    if mesh._device_weld is None:
+        mesh._device_weld = weld_mesh(mesh.device_triangles, normals=True)
+    vertices, faces, normals = mesh._device_weld
+    V, F, dev = vertices.shape[0], faces.shape[0], vertices.device
+    colors = torch.zeros(V, 3, dtype=torch.uint8, device=dev)
+    seen = torch.zeros(V, dtype=torch.uint8, device=dev)
+    source = torch.full((V,), -1, dtype=torch.int32, device=dev)
+    area = torch.zeros(2, dtype=torch.float64, device=dev)
+    if V:
+        nbytes = lib.zs_mesh_colors_workspace_bytes(V, F, H, W, ss)
+        if nbytes == 0:
+            raise _lib.ZeroShapeHipError("mesh_vertex_colors: V=%d F=%d at %dx%d x%d exceeds one launch" % (V, F, H, W, ss))
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        stream = _lib.current_stream_ptr(dev)
+        base = (ctypes.c_float * 3)(*[float(c) for c in base_rgb])
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_colors_seen(
+                _lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(normals), V, F, _lib.ptr(image), _lib.ptr(mask), H, W, _lib.ptr(intr),
+                _lib.ptr(mean), _lib.ptr(scale), ss, float(depth_tol), float(min_cos), _lib.ptr(colors), _lib.ptr(seen),
+                _lib.ptr(source), _lib.ptr(count), _lib.ptr(area), _lib.ptr(ws), stream), "zs_mesh_colors_seen")
+            n_seen = int(count.item())                       # 4-byte D2H: sizes the two lists
+            n_hidden = V - n_seen
+            if n_hidden:
+                seen_idx = torch.empty(n_seen, dtype=torch.int32, device=dev)
+                seen_xyz = torch.empty(n_seen, 3, dtype=torch.float32, device=dev)
+                hidden_idx = torch.empty(n_hidden, dtype=torch.int32, device=dev)
+                hidden_xyz = torch.empty(n_hidden, 3, dtype=torch.float32, device=dev)
+                _lib.check(lib.zs_mesh_colors_compact(_lib.ptr(vertices), _lib.ptr(seen), V, n_seen, _lib.ptr(ws), _lib.ptr(seen_idx),
+                                                      _lib.ptr(seen_xyz), _lib.ptr(hidden_idx), _lib.ptr(hidden_xyz), stream),
+                           "zs_mesh_colors_compact")
+                near = dist = None
+                if n_seen:
+                    dist = torch.empty(n_hidden, dtype=torch.float32, device=dev)
+                    near = torch.empty(n_hidden, dtype=torch.int32, device=dev)
+                    dist2 = torch.empty(n_seen, dtype=torch.float32, device=dev)
+                    near2 = torch.empty(n_seen, dtype=torch.int32, device=dev)
+                    cbytes = lib.zs_chamfer_workspace_bytes(1, n_hidden, n_seen)
+                    cws = torch.empty((cbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+                    _lib.check(lib.zs_chamfer_forward_ws(_lib.ptr(hidden_xyz), _lib.ptr(seen_xyz), 1, n_hidden, n_seen, _lib.ptr(dist),
+                                                         _lib.ptr(dist2), _lib.ptr(near), _lib.ptr(near2), _lib.ptr(cws), cbytes,
+                                                         stream), "zs_chamfer_forward_ws")
+                _lib.check(lib.zs_mesh_colors_fill(_lib.ptr(hidden_idx), _lib.ptr(seen_idx), _lib.ptr(near), _lib.ptr(dist), V, n_seen,
+                                                   float(fade), base, _lib.ptr(colors), _lib.ptr(source), stream),
+                           "zs_mesh_colors_fill")
+    mesh.device_vertex_colors, mesh.device_vertex_seen, mesh.device_color_source, mesh.device_seen_area = colors, seen, source, area
+    mesh._vertex_colors = mesh._vertex_seen = mesh._seen_area = None
+    return mesh
+
+
+def vertex_colors(opt, var, meshes=None, **kw):
+    """mesh_vertex_colors for every mesh of the batch (``meshes``, default ``var.mesh_pred``) with sample b of
+    ``var.rgb_input_map``, ``var.mask_input_map`` and ``var.intr_pred`` (``var.intr`` when there is no prediction).  (mean, scale)
+    come from camera.seen_surface on ``var.depth_pred`` - the kernel Graph.forward normalised the seen surface with, on the same
+    inputs, hence the same bits.  ``depth_tol`` defaults to default_color_depth_tol(opt); further keywords go to
+    mesh_vertex_colors.  -> meshes."""
+    from . import camera
+    meshes = var.mesh_pred if meshes is None else meshes
+    intr = var.intr_pred if getattr(var, "intr_pred", None) is not None else var.intr
+    _, _, _, mean, scale = camera.seen_surface(opt, var.depth_pred, intr, var.mask_input_map)
+    kw.setdefault("depth_tol", default_color_depth_tol(opt))
+    for b, mesh in enumerate(meshes):
+        mesh_vertex_colors(mesh, var.rgb_input_map[b], var.mask_input_map[b], intr[b], mean[b], scale[b:b + 1], **kw)
+    return meshes
+
+
+def color_options(opt):
+    """The keywords of vertex_colors when ``--eval.vertex_colors=true`` is set (``--eval.color_fade=<mesh units>``,
+    ``--eval.color_min_cos``, ``--eval.color_supersample``: no yaml file carries them), else None."""
+    if not bool(opt.eval.get("vertex_colors", False)):
+        return None
+    return dict(fade=float(opt.eval.get("color_fade", 0.0)), min_cos=float(opt.eval.get("color_min_cos", COLOR_MIN_COS)),
+                supersample=int(opt.eval.get("color_supersample", 2)))
 
 
 _MC_TABLES = {}

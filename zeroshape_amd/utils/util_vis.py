@@ -64,12 +64,14 @@ def dump_depths(opt, idx, name, depths, masks=None, rescale=False, folder="dump"
         Image.fromarray((x.clip(0, 1) * 65535 + 0.5).astype(np.uint16)).save(_path(opt, folder, i, name, "png"))
 
 
-def dump_meshes(opt, idx, name, meshes, folder="dump", normals=False, **_):
+def dump_meshes(opt, idx, name, meshes, folder="dump", normals=False, colors=False, **_):
     """meshes: eval_3D.SimpleMesh objects -> OBJ with shared vertices (the indexed form mcubes.marching_cubes returns in
     the reference; the marching-cubes kernel emits bit-identical coordinates for shared vertices): a comment line, one
     ``v %.6f %.6f %.6f`` per vertex, one ``f %d %d %d`` per face.  With ``normals`` also one ``vn %.6f %.6f %.6f`` per vertex
     (mesh.vertex_normals) after the vertices, and the faces as ``f a//a b//b c//c``, so that a viewer shades smoothly.
     ``normals="field"``: the same lines from mesh.field_normals (eval_3D.field_normals: minus the field's normalised gradient).
+    With ``colors`` the vertex lines become ``v %.6f %.6f %.6f %.6f %.6f %.6f`` - x y z r g b with r, g, b = mesh.vertex_colors / 255
+    (eval_3D.vertex_colors), the de-facto OBJ vertex-colour extension MeshLab, Blender and Open3D read; it combines with ``normals``.
     Formatted in bulk, one % per block and one write per file: the same bytes as a write per line, which took 64 ms for the
     vox-128 mesh."""
     if isinstance(normals, str) and normals != "field":
@@ -80,8 +82,12 @@ def dump_meshes(opt, idx, name, meshes, folder="dump", normals=False, **_):
         else:
             vn = mesh.vertex_normals if normals else None         # (first: a GPU-built mesh then welds once)
         verts, faces = mesh.vertices, mesh.faces + 1              # the indexed form (eval_3D.SimpleMesh welds the soup)
-        text = ["# zeroshape_amd mesh: %d vertices, %d faces\n" % (len(verts), len(faces)),
-                ("v %.6f %.6f %.6f\n" * len(verts)) % tuple(verts.astype(np.float64).ravel().tolist())]
+        text = ["# zeroshape_amd mesh: %d vertices, %d faces\n" % (len(verts), len(faces))]
+        if colors:
+            rows = np.concatenate([verts.astype(np.float64), mesh.vertex_colors.astype(np.float64) / 255.0], axis=1)
+            text.append(("v %.6f %.6f %.6f %.6f %.6f %.6f\n" * len(rows)) % tuple(rows.ravel().tolist()))
+        else:
+            text.append(("v %.6f %.6f %.6f\n" * len(verts)) % tuple(verts.astype(np.float64).ravel().tolist()))
         if normals:
             text += [("vn %.6f %.6f %.6f\n" * len(vn)) % tuple(vn.astype(np.float64).ravel().tolist()),
                      ("f %d//%d %d//%d %d//%d\n" * len(faces)) % tuple(np.repeat(faces, 2, axis=1).ravel().tolist())]
@@ -197,9 +203,11 @@ def mesh_stats(triangles):
     return out.cpu().numpy()
 
 
-def render_into(triangles, xform, cams, H, W, rgb, depth=None, tri=None, zbuffer=None):
+def render_into(triangles, xform, cams, H, W, rgb, depth=None, tri=None, zbuffer=None, corner_colors=None):
     """zs_render_frames into caller-owned GPU buffers: ``triangles`` [n,3,3] fp32, ``xform`` 8 host floats, ``cams`` [F,12]
-    fp32 on the device, ``rgb`` uint8 [F,H,W,3], ``depth`` fp32 / ``tri`` int32 [F,H,W] or None."""
+    fp32 on the device, ``rgb`` uint8 [F,H,W,3], ``depth`` fp32 / ``tri`` int32 [F,H,W] or None.  With ``corner_colors`` (uint8
+    [n,3,3] on the device: r g b of every triangle corner) zs_render_frames_colored: the albedo is interpolated from them
+    instead of BASE_RGB."""
     import ctypes
     import torch
     from .. import _lib
@@ -218,17 +226,26 @@ def render_into(triangles, xform, cams, H, W, rgb, depth=None, tri=None, zbuffer
     xf = (ctypes.c_float * 8)(*[float(v) for v in xform])
     base = (ctypes.c_float * 3)(*BASE_RGB)
     with _lib.on(dev):
+        if corner_colors is not None:
+            assert (corner_colors.device == dev and corner_colors.dtype == torch.uint8 and corner_colors.is_contiguous()
+                    and corner_colors.shape == (triangles.shape[0], 3, 3))
+            _lib.check(lib.zs_render_frames_colored(_lib.ptr(triangles), triangles.shape[0], xf, _lib.ptr(cams), F, H, W, float(YFOV),
+                                                    float(ZNEAR), _lib.ptr(corner_colors), _lib.ptr(rgb), _lib.ptr(depth),
+                                                    _lib.ptr(tri), _lib.ptr(zbuffer), _lib.current_stream_ptr(dev)),
+                       "zs_render_frames_colored")
+            return
         _lib.check(lib.zs_render_frames(_lib.ptr(triangles), triangles.shape[0], xf, _lib.ptr(cams), F, H, W, float(YFOV),
                                         float(ZNEAR), base, _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(tri), _lib.ptr(zbuffer),
                                         _lib.current_stream_ptr(dev)), "zs_render_frames")
 
 
 def render_mesh_frames(triangles, positions, rotations, resolution, return_depth=False, return_tri=False,
-                       pose_normalize=False):
+                       pose_normalize=False, corner_colors=None):
     """All frames of a camera path in one call.  ``triangles``: GPU tensor [n,3,3] fp32; ``positions`` / ``rotations``: what
     get_positions_and_rotations returns; ``resolution`` = (width, height) like pyrender.OffscreenRenderer's.  Returns the
     GPU tensor rgb uint8 [F,H,W,3], or the tuple (rgb[, depth fp32 [F,H,W]][, tri int32 [F,H,W]]).  With ``pose_normalize`` the
-    mesh is turned, centred and scaled on the fly as dump_meshes_viz does (pretransform_params of its zs_mesh_stats)."""
+    mesh is turned, centred and scaled on the fly as dump_meshes_viz does (pretransform_params of its zs_mesh_stats).
+    ``corner_colors``: uint8 [n,3,3] on the device (``vertex_colors[faces]``) instead of the one BASE_RGB."""
     import torch
     W, H = int(resolution[0]), int(resolution[1])
     dev = triangles.device
@@ -239,7 +256,7 @@ def render_mesh_frames(triangles, positions, rotations, resolution, return_depth
     rgb = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
     depth = torch.empty(F, H, W, dtype=torch.float32, device=dev) if return_depth else None
     tri = torch.empty(F, H, W, dtype=torch.int32, device=dev) if return_tri else None
-    render_into(triangles, xform, cams, H, W, rgb, depth, tri)
+    render_into(triangles, xform, cams, H, W, rgb, depth, tri, corner_colors=corner_colors)
     out = (rgb,) + ((depth,) if return_depth else ()) + ((tri,) if return_tri else ())
     return out[0] if len(out) == 1 else out
 
@@ -251,12 +268,21 @@ def _soup(mesh):
     return soup if soup is not None else getattr(mesh, "triangles", mesh)
 
 
+def corner_colors(mesh):
+    """uint8 [n,3,3] on the device: the vertex colours of a coloured GPU SimpleMesh at every corner of its soup (the weld's faces
+    are in soup order), for render_mesh_frames."""
+    if getattr(mesh, "device_vertex_colors", None) is None:
+        raise ValueError("this mesh has no vertex colours: eval_3D.vertex_colors(opt, var) computes them")
+    return mesh.device_vertex_colors[mesh._device_weld[1].long()].contiguous()
+
+
 def visualize_mesh(mesh, output_path, resolution=(200, 200), write_gif=True, write_frames=True, time_per_frame=80,
-                   n_frames=180, pose_normalize=False, device="cuda"):
+                   n_frames=180, pose_normalize=False, device="cuda", colors=False):
     """utils/util_vis.py:348-405.  ``mesh``: an eval_3D.SimpleMesh, or a triangle soup [n,3,3] as tensor or array (a host
     soup is uploaded once).  Renders the ``n_frames`` of get_positions_and_rotations in one call, copies them to the host
     once, writes ``<output_path>.gif`` (80 ms a frame, endless loop - the reference ignores ``time_per_frame`` too) and, with
-    ``write_frames``, ``<output_path>/0000.jpg ...``.  Returns the frames, uint8 [n_frames,H,W,3]."""
+    ``write_frames``, ``<output_path>/0000.jpg ...``.  With ``colors`` (a SimpleMesh that eval_3D.vertex_colors coloured) the
+    albedo is the mesh's vertex colours, gathered per triangle corner on the device.  Returns the frames, uint8 [n_frames,H,W,3]."""
     import torch
     from PIL import Image
     soup = _soup(mesh)
@@ -264,7 +290,8 @@ def visualize_mesh(mesh, output_path, resolution=(200, 200), write_gif=True, wri
         soup = torch.from_numpy(np.ascontiguousarray(soup, np.float32)).to(device)
     soup = soup.to(torch.float32).reshape(-1, 3, 3)
     positions, rotations = get_positions_and_rotations(n_frames=n_frames)
-    frames = render_mesh_frames(soup, positions, rotations, resolution, pose_normalize=pose_normalize).cpu().numpy()
+    frames = render_mesh_frames(soup, positions, rotations, resolution, pose_normalize=pose_normalize,
+                                corner_colors=corner_colors(mesh) if colors else None).cpu().numpy()
     images = [Image.fromarray(f, mode="RGB") for f in frames]
     if write_gif:
         _write_gif("{}.gif".format(output_path), images, 80)
@@ -275,15 +302,16 @@ def visualize_mesh(mesh, output_path, resolution=(200, 200), write_gif=True, wri
     return frames
 
 
-def dump_meshes_viz(opt, idx, name, meshes, save_frames=True, folder="dump"):
+def dump_meshes_viz(opt, idx, name, meshes, save_frames=True, folder="dump", colors=False):
     """utils/util_vis.py:112-127: ``<idx>_<name>.gif`` (and ``<idx>_<name>/0000.jpg ...`` with ``save_frames``) of every mesh,
     turned, centred and scaled to the unit cube.  An empty mesh writes nothing and raises nothing (the reference's
-    ``try/except`` around scale_to_unit_cube)."""
+    ``try/except`` around scale_to_unit_cube).  ``colors``: the meshes' vertex colours instead of BASE_RGB (visualize_mesh)."""
     for i, mesh in zip(idx, meshes):
         if len(_soup(mesh)) == 0:                    # (a tensor's length is its shape: no copy to the host)
             continue
         fname = _path(opt, folder, i, name, "gif")[:-4]
-        visualize_mesh(mesh, fname, write_frames=save_frames, pose_normalize=True, device=getattr(opt, "device", "cuda"))
+        visualize_mesh(mesh, fname, write_frames=save_frames, pose_normalize=True, device=getattr(opt, "device", "cuda"),
+                       colors=colors)
 
 
 # ---- seen-surface mesh (utils/util_vis.py:129-170) ----
