@@ -31,7 +31,9 @@
 //    after an lgkmcnt-retired read + barrier).
 //  * LDS: [params window 16 KiB][A staging 2 x 16 KiB][4 x 28 KiB activation slabs] = 160 KiB
 //    (tile 7 of a slab-resident array lives in registers).  Params are paged in five windows
-//    per tile instead of two.
+//    per tile instead of two.  The slab holds what a GEMM re-reads as B operands per output
+//    tile: LN1's output (q, k, v) and the odd layers' inputs of impl_mlp.  LN2's output (fc1) and
+//    the even layers' inputs stay in registers (LN2 IN REGISTERS below).
 //  * No asm register ring: LDS reads and MFMAs are builtins, scheduled and hazard-padded by
 //    hipcc (VGPR-form accumulators: -mllvm -amdgpu-mfma-vgpr-form, zeroshape_amd/build.py); only
 //    the DMA, the barrier and the prefetch pin are asm.
@@ -340,35 +342,45 @@ struct SoftplusStager {
 // zs::dm::gelu_erf / softplus100: bit-identical results.  The A / B operands are ordinary asm inputs
 // (hipcc waits for their LDS reads in front of the statement); the VALU part touches no MFMA operand.
 // gelu: 4 plain | rcp, exp, 1 plain | 7 plain
-DEV float kblock_gelu(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi, const u32x4 &blo, float x) {
-    float u, q, d, t, e, m, p;
-    const float c0 = 0.70710678118654752440f, c1 = 0.3275911f, c2 = -1.02753365f;
-    asm volatile(
+// (BREG: where the B operands live - "v", or "a" for an array pinned in the accumulator half; LEAD: that form's leading
+// s_nop, see mfma3_breg below)
 #ifndef ZS_EXP_TWO_TERM
-                 "v_mfma_f32_32x32x16_f16 %[acc], %[alo], %[bh], %[acc]\n\t"
+#define ZS_KBLOCK_MFMA_LO_HI "v_mfma_f32_32x32x16_f16 %[acc], %[alo], %[bh], %[acc]\n\t"
+#else
+#define ZS_KBLOCK_MFMA_LO_HI
 #endif
-                 "v_mul_f32_e64 %[u], |%[x]|, %[c0]\n\t"
-                 "v_mul_f32_e32 %[q], %[u], %[u]\n\t"
-                 "v_mul_f32_e32 %[q], 0xbfb8aa3b, %[q]\n\t"
-                 "v_fma_f32 %[d], %[u], %[c1], 1.0\n\t"
-                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bl], %[acc]\n\t"
-                 "v_rcp_f32_e32 %[t], %[d]\n\t"
-                 "v_exp_f32_e32 %[e], %[q]\n\t"
-                 "v_max_f32_e32 %[m], 0, %[x]\n\t"
-                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bh], %[acc]\n\t"
-                 "v_fmamk_f32 %[p], %[t], 0x3f40228a, %[c2]\n\t"
-                 "v_fmaak_f32 %[p], %[p], %[t], 0x3f80a6d5\n\t"
-                 "v_fmaak_f32 %[p], %[p], %[t], 0xbe4dff65\n\t"
-                 "v_fmaak_f32 %[p], %[p], %[t], 0x3e38842e\n\t"
-                 "v_mul_f32_e64 %[p], %[t], -%[p]\n\t"
-                 "v_mul_f32_e32 %[p], %[u], %[p]\n\t"
-                 "v_fmac_f32_e32 %[m], %[p], %[e]"
-                 : [acc] "+v"(acc), [u] "=&v"(u), [q] "=&v"(q), [d] "=&v"(d), [t] "=&v"(t), [e] "=&v"(e), [m] "=&v"(m),
-                   [p] "=&v"(p)
-                 : [alo] "v"(alo), [ahi] "v"(ahi), [bh] "v"(bhi), [bl] "v"(blo), [x] "v"(x), [c0] "s"(c0), [c1] "s"(c1),
-                   [c2] "v"(c2));
-    return m;
+#define ZS_KBLOCK_GELU(NAME, BREG, LEAD) \
+DEV float NAME(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi, const u32x4 &blo, float x) {             \
+    float u, q, d, t, e, m, p;                                                                                             \
+    const float c0 = 0.70710678118654752440f, c1 = 0.3275911f, c2 = -1.02753365f;                                          \
+    asm volatile(                                                                                                          \
+                 LEAD ZS_KBLOCK_MFMA_LO_HI                                                                                 \
+                 "v_mul_f32_e64 %[u], |%[x]|, %[c0]\n\t"                                                                   \
+                 "v_mul_f32_e32 %[q], %[u], %[u]\n\t"                                                                      \
+                 "v_mul_f32_e32 %[q], 0xbfb8aa3b, %[q]\n\t"                                                                \
+                 "v_fma_f32 %[d], %[u], %[c1], 1.0\n\t"                                                                    \
+                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bl], %[acc]\n\t"                                               \
+                 "v_rcp_f32_e32 %[t], %[d]\n\t"                                                                            \
+                 "v_exp_f32_e32 %[e], %[q]\n\t"                                                                            \
+                 "v_max_f32_e32 %[m], 0, %[x]\n\t"                                                                         \
+                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bh], %[acc]\n\t"                                               \
+                 "v_fmamk_f32 %[p], %[t], 0x3f40228a, %[c2]\n\t"                                                           \
+                 "v_fmaak_f32 %[p], %[p], %[t], 0x3f80a6d5\n\t"                                                            \
+                 "v_fmaak_f32 %[p], %[p], %[t], 0xbe4dff65\n\t"                                                            \
+                 "v_fmaak_f32 %[p], %[p], %[t], 0x3e38842e\n\t"                                                            \
+                 "v_mul_f32_e64 %[p], %[t], -%[p]\n\t"                                                                     \
+                 "v_mul_f32_e32 %[p], %[u], %[p]\n\t"                                                                      \
+                 "v_fmac_f32_e32 %[m], %[p], %[e]"                                                                         \
+                 : [acc] "+v"(acc), [u] "=&v"(u), [q] "=&v"(q), [d] "=&v"(d), [t] "=&v"(t), [e] "=&v"(e), [m] "=&v"(m),    \
+                   [p] "=&v"(p)                                                                                            \
+                 : [alo] "v"(alo), [ahi] "v"(ahi), [bh] BREG(bhi), [bl] BREG(blo), [x] "v"(x), [c0] "s"(c0), [c1] "s"(c1), \
+                   [c2] "v"(c2));                                                                                          \
+    return m;                                                                                                              \
 }
+ZS_KBLOCK_GELU(kblock_gelu, "v", "")
+ZS_KBLOCK_GELU(kblock_gelu_breg, "a", "s_nop 1\n\t")
+#undef ZS_KBLOCK_GELU
+#undef ZS_KBLOCK_MFMA_LO_HI
 // softplus100: 1 plain + exp | 2 plain + log | 1 plain
 DEV float kblock_softplus(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi, const u32x4 &blo, float x) {
     float t, m;
@@ -533,6 +545,21 @@ DEV void gemm_reg_act(AStream &s, const PT *X, f32x16 &acc, const f32x16 &cur, F
             s.step(kb & (CK - 1), ahi, alo);
             const float r = ACT == 0 ? kblock_gelu(acc, ahi, alo, X[kt].v[2 * j], X[kt].v[2 * j + 1], cur[kb])
                                      : kblock_softplus(acc, ahi, alo, X[kt].v[2 * j], X[kt].v[2 * j + 1], cur[kb]);
+            fin(kb, r);
+            tail(kb);
+        }
+}
+// gemm_areg with the GELU of cur[kb] in the gaps of K-block kb
+template <typename FIN, typename TAIL>
+DEV void gemm_areg_gelu(AStream &s, const PT *X, f32x16 &acc, const f32x16 &cur, FIN fin, TAIL tail) {
+#pragma unroll
+    for (int kt = 0; kt < NT; kt++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            u32x4 ahi, alo;
+            const int kb = kt * 2 + j;
+            s.step(kb & (CK - 1), ahi, alo);
+            const float r = kblock_gelu_breg(acc, ahi, alo, X[kt].v[2 * j], X[kt].v[2 * j + 1], cur[kb]);
             fin(kb, r);
             tail(kb);
         }
@@ -732,6 +759,36 @@ DEV void layer_norm_lds(const f32x16 *x, Slab &sl, const float *prm, int g_off, 
 #pragma unroll
         for (int r = 0; r < 16; r++) t[r] = fmaf((x[kt][r] - mean) * rstd, g[r], b[r]);
         sl.store(kt, pack_tile(t));
+    }
+}
+// LN2 IN REGISTERS.  fc1 re-reads LN2's output once per hidden tile: 32 passes over the 14 slab K-blocks per block, two
+// ds_read_b128 each.  hp and fp of impl_mlp are not live in the attention blocks, so the eight packed tiles stay in
+// registers instead - pinned in the accumulator half like fp (mfma3_breg; left to hipcc such an array spilled and crashed
+// its AGPR-copy rewrite pass) - and fc1 runs like impl_mlp's even layers (gemm_areg, kblock_gelu_breg).  The same values
+// reach every accumulator in the same order: bit-identical results.  LN1's output (q, k, v: 24 passes in block 1) stays in
+// the slab: with it in registers, or only its tiles 4-7, hipcc spills (DESIGN 3b.4 has the numbers).
+// -DZS_SPLIT_LN_SLAB builds the slab form (for A/B runs of two libraries: nothing selects it at run time).
+#ifndef ZS_SPLIT_LN_SLAB
+constexpr bool LN2_REGS = true;
+#else
+constexpr bool LN2_REGS = false;
+#endif
+// layer_norm_lds with the eight packed tiles returned in xn
+DEV void layer_norm_reg(const f32x16 *x, PT *xn, const float *prm, int g_off, int b_off, int hi) {
+    float mean, rstd;
+    ln_stats(x, mean, rstd);
+#pragma unroll
+    for (int kt = 0; kt < NT; kt++) {
+        float g[16], b[16], t[16];
+        rp(prm, g_off, kt, hi, g);
+        rp(prm, b_off, kt, hi, b);
+#pragma unroll
+        for (int r = 0; r < 16; r++) t[r] = fmaf((x[kt][r] - mean) * rstd, g[r], b[r]);
+        xn[kt] = pack_tile(t);
+        // tile by tile into the accumulator half (the statements keep their order): 1,392 / 1,333 static v_accvgpr moves
+        // in the two kernels instead of 1,604 / 1,637 with the tiles left to pile up in VGPRs
+#pragma unroll
+        for (int q = 0; q < 4; q++) asm volatile("" : "+a"(xn[kt].v[q]));
     }
 }
 
@@ -966,7 +1023,11 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
 
         ZS_STAMP(3 + blk * 4);
         // MLP (timm Mlp): y += b2 + W2 gelu(W1 LN2(y) + b1), one hidden tile at a time
-        layer_norm_lds(y, sl, prm, PB_LN2G, PB_LN2B, hi);
+        PT xn[NT];  // LN2_REGS
+        if constexpr (LN2_REGS)
+            layer_norm_reg(y, xn, prm, PB_LN2G, PB_LN2B, hi);
+        else
+            layer_norm_lds(y, sl, prm, PB_LN2G, PB_LN2B, hi);
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) y[nt] += rp16(prm, PB_B2, nt, hi);
         ZS_STAMP(4 + blk * 4);
@@ -975,16 +1036,26 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
         RowInit bi;
         f32x16 hid = rp16(prm, PB_B1, 0, hi);
         bi.start(prm, PB_B1, 1, hi);
-        gemm_lds(s, sl, hid, 0, [&](int kb, int g) {
+        auto bias_side = [&](int kb, int g) {
             if (g == 2 && (kb & 3) == 1) bi.step(kb & ~3);
-        });
+        };
+        if constexpr (LN2_REGS) {
+            gemm_areg<NT>(s, xn, hid, bias_side);
+            mfma_settle(hid);   // fc1(0)'s last MFMA (mfma3_breg) is a few instructions in front of GELU(hid[0]) in fc1(1)
+        } else {
+            gemm_lds(s, sl, hid, 0, bias_side);
+        }
 #pragma unroll 1
         for (int ht = 0; ht < HT - 1; ht++) {
             f32x16 nxt = bi.v;
             bi.start(prm, PB_B1, ht + 2 < HT ? ht + 2 : HT - 1, hi);
             TilePacker e;
-            gemm_lds_act<0>(s, sl, nxt, hid, [&](int kb, float r) { e.feed(kb, r); },
-                            [&](int kb) { if ((kb & 3) == 1) bi.step(kb & ~3); });
+            auto fin = [&](int kb, float r) { e.feed(kb, r); };
+            auto tail = [&](int kb) { if ((kb & 3) == 1) bi.step(kb & ~3); };
+            if constexpr (LN2_REGS)
+                gemm_areg_gelu(s, xn, nxt, hid, fin, tail);
+            else
+                gemm_lds_act<0>(s, sl, nxt, hid, fin, tail);
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) gemm_one(s, e.p, y[nt], (2 * nt) & (CK - 1));
             hid = nxt;
