@@ -33,6 +33,11 @@ detached blobs of a single-view reconstruction - and closed inner shells of nega
 per-component table (faces, vertices, edges, boundary / non-manifold / misoriented edges, area, signed volume) of the mesh
 that was written.
 
+--eval.smooth_iterations=10 (opt-in, shape task) smooths the mesh on the GPU before it is written (eval_3D.smooth_mesh, after
+the component filter): Taubin passes over the vertex neighbourhood, which take the terraces out of a sharp field's marching
+cubes without the shrinkage of plain Laplacian smoothing.  --eval.smooth_lambda (0.5) and --eval.smooth_mu (-0.53; none =
+plain Laplacian passes) are the two factors, --eval.smooth_free_boundary=true lets the vertices of open edges move too.
+
 --eval.vertex_colors=true (opt-in, shape task) colours the mesh from the input photo on the GPU (eval_3D.vertex_colors): a
 vertex the input camera saw takes the photo's bilinear texel, every other vertex the colour of the nearest seen one.
 <name>_mesh.obj then has `v x y z r g b` lines (the vertex-colour extension MeshLab, Blender and Open3D read), with --viz

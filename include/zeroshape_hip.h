@@ -460,6 +460,55 @@ int zs_mesh_components_select(const int *counts, const double *measures, int n_c
 int zs_mesh_filter_faces(const float *tris, const int *keep_pos, int n_tris, float *out_tris, int n_kept, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The vertex neighbourhood of an indexed mesh and Laplacian / Taubin smoothing over it
+ * (csrc/mesh_smooth.hip; eval_3D.mesh_adjacency_host and eval_3D.smooth_vertices_host restate
+ * both in numpy and define them: the kernels equal them bit for bit).  faces [n_tris][3] int32
+ * over n_verts vertices is the weld's output.
+ *   adjacency : a face with two equal indices contributes no edges, every other face its three
+ *               undirected edges.  offsets [n_verts + 1] int32; neighbors int32, allocated by the
+ *               caller for 6 n_tris entries, of which the first nnz = offsets[n_verts] are
+ *               written: row v = neighbors[offsets[v] .. offsets[v + 1]) holds the distinct other
+ *               endpoints of v's edges in ascending order.  boundary [n_verts] uint8 = 1 iff some
+ *               edge at the vertex is used by exactly one non-degenerate face (an edge used three
+ *               or more times is not a boundary edge).  out[2] (device ints) = nnz and a status
+ *               word: 0, or 2 when a face index lies outside [0, n_verts) - such a face
+ *               contributes nothing, and no index is used as an address before it is tested.
+ *               One radix sort of the 6 n_tris directed entries (64-bit keys), head flags, one
+ *               scan, a binary search per vertex.  Integers only and no atomic whose order
+ *               matters: two runs give the same bytes.
+ *   smooth    : `passes` passes over positions kept in fp64 between passes.  Pass t (from 0) uses
+ *               f = lambda, or f = mu when `alternate` is set and t is odd.  A vertex moves iff its
+ *               row is not empty and it is not pinned (boundary given and boundary[v] != 0):
+ *                 s = 0; for k in row order: s = s + x[neighbors[k]];  m = s / (double)degree;
+ *                 x' = x + f * (m - x)
+ *               per coordinate, every operation in fp64 as written; the other vertices are copied.
+ *               After the last pass the positions are rounded to fp32 into out_vertices (not the
+ *               input); passes == 0 copies the input's bits.  *status (device int) = 0, or
+ *               nonzero when a row had offsets[v] < 0, offsets[v + 1] < offsets[v] or
+ *               offsets[v + 1] > offsets[n_verts] (1) or a neighbour index outside [0, n_verts)
+ *               (2): such a row is not followed and its vertex is copied.  A thread per vertex
+ *               walks its row - the order of the additions is the contract - and every pass is a
+ *               launch of its own.  0 < lambda <= 1; -1 <= mu < 0 when `alternate` is set.
+ *               neighbors may be NULL for an adjacency without edges: a row that is not empty
+ *               then sets the status (1).
+ *   gather    : out_tris[f][k] = vertices[faces[f][k]]: the soup of an indexed mesh in face
+ *               order (NaN for an index outside [0, n_verts)).
+ * scratch, 8-byte aligned: zs_mesh_adjacency_scratch_bytes(n_tris, n_verts) and
+ * zs_mesh_smooth_scratch_bytes(n_verts) bytes (0 for empty and out-of-range sizes; smoothing needs
+ * none for passes <= 1).  Limits: those of zs_mesh_components, except n_tris <= 2^28 - the
+ * 6 n_tris directed entries are counted in int32; n_verts <= 3 * 2^28 for the smoothing.  Zero
+ * sizes return 1 and touch nothing.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_adjacency_scratch_bytes(int n_tris, int n_verts);
+int zs_mesh_adjacency(const int *faces, int n_tris, int n_verts, int *offsets, int *neighbors, uint8_t *boundary, int *out,
+                      void *scratch, void *stream);
+size_t zs_mesh_smooth_scratch_bytes(int n_verts);
+int zs_mesh_smooth(const float *vertices, int n_verts, const int *offsets, const int *neighbors, const uint8_t *boundary,
+                   int passes, double lambda, double mu, int alternate, float *out_vertices, int *status, void *scratch,
+                   void *stream);
+int zs_mesh_gather_faces(const float *vertices, const int *faces, int n_tris, int n_verts, float *out_tris, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
  * itself is Implicit.field_gradient's, between the two calls).
  *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G

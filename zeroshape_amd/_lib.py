@@ -108,7 +108,13 @@ SIGNATURES = {
     "zs_mesh_components_select": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_double, _c_int, _c_void_p, _c_void_p, _c_int, _c_int,
                                            _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_filter_faces": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p]),
-    "zs_mesh_to_field_points": (_c_int, [_c_void_p, _c_size_t, _c_float, _c_int, _c_void_p, _c_void_p]),
+    "zs_mesh_adjacency_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+    "zs_mesh_adjacency": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 6),
+    "zs_mesh_smooth_scratch_bytes": (_c_size_t, [_c_int]),
+    "zs_mesh_smooth": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_double, _c_double, _c_int,
+                                _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "zs_mesh_gather_faces": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "zs_mesh_to_field_points":(_c_int, [_c_void_p, _c_size_t, _c_float, _c_int, _c_void_p, _c_void_p]),
     "zs_field_normals_finish": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_stats_scratch_bytes": (_c_size_t, [_c_int]),
     "zs_mesh_stats": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),

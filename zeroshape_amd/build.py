@@ -49,6 +49,8 @@ EXTRA = {
     "mesh_components.hip": ["-ffp-contract=off"],
     # fp64 projection, z-buffer, seen test and colours equal to the numpy restatement in utils/eval_3D.py (mesh_vertex_colors_host)
     "mesh_colors.hip": ["-ffp-contract=off"],
+    # the fp64 neighbour sum, mean and step equal, operation for operation, to the numpy restatement in utils/eval_3D.py (smooth_vertices_host)
+    "mesh_smooth.hip": ["-ffp-contract=off"],
 }
 
 

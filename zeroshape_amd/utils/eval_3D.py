@@ -526,14 +526,14 @@ def _surface_clouds(opt, level_vox, seed=0):
     reference (utils/eval_3D.py:115-118,181-184)."""
     meshes, clouds = [], []
     range_min, range_max = opt.eval.range
-    cleaning = _component_options(opt)
+    cleaning, smoothing = _component_options(opt), _smooth_options(opt)
     for i in range(level_vox.shape[0]):
-        if cleaning is None:
+        if cleaning is None and smoothing is None:
             tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
-        else:                                            # eval.min_component_area / eval.drop_cavities: sample the cleaned mesh
-            tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)
-            mesh = filter_components(SimpleMesh(tris), *cleaning)
+        else:                                            # eval.min_component_area / eval.drop_cavities, then eval.smooth_*:
+            tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)          # sample the cleaned, smoothed mesh
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i)
         meshes.append(mesh)
         clouds.append(pts)
@@ -548,6 +548,40 @@ def _component_options(opt):
     if min_area is None and not drop:
         return None
     return (None if min_area is None else float(min_area)), drop
+
+
+SMOOTH_OPTIONS = ("smooth_iterations", "smooth_lambda", "smooth_mu", "smooth_free_boundary")
+
+
+def _smooth_options(opt):
+    """(iterations, lamb, mu, pin_boundary) for smooth_mesh when ``--eval.smooth_iterations=N`` is set (opt-in, command line
+    only: no yaml file carries it), else None: the pipelines then make today's calls.  ``--eval.smooth_lambda`` and
+    ``--eval.smooth_mu`` replace smooth_mesh's defaults (``--eval.smooth_mu=none``: plain Laplacian passes) and
+    ``--eval.smooth_free_boundary=true`` lets the vertices of open edges move; any of them without the pass count is an
+    error, not ignored."""
+    iterations = opt.eval.get("smooth_iterations", None)
+    if iterations is None:
+        extra = [k for k in SMOOTH_OPTIONS[1:] if k in opt.eval]
+        if extra:
+            raise ValueError("eval.%s needs eval.smooth_iterations" % extra[0])
+        return None
+    mu = opt.eval.get("smooth_mu", -0.53)
+    if isinstance(mu, str):
+        if mu.strip().lower() != "none":
+            raise ValueError("eval.smooth_mu must be a number in [-1, 0) or none, got %r" % (mu,))
+        mu = None
+    args = (iterations, opt.eval.get("smooth_lambda", 0.5), mu, not bool(opt.eval.get("smooth_free_boundary", False)))
+    _check_smooth_arguments(*args[:3])
+    return args
+
+
+def _cleaned_and_smoothed(mesh, cleaning, smoothing):
+    """The opt-in steps between marching cubes and sampling, in their order: filter_components, then smooth_mesh."""
+    if cleaning is not None:
+        mesh = filter_components(mesh, *cleaning)
+    if smoothing is not None:
+        mesh = smooth_mesh(mesh, *smoothing)
+    return mesh
 
 
 def _gt_to_view_frame(opt, var):
@@ -662,6 +696,8 @@ class SimpleMesh(object):
     ``components`` (a MeshComponents: labels, per-component counts, area and signed volume) and, from it, trimesh's ``area``,
     ``volume``, ``euler_number`` and ``is_watertight``; filter_components(mesh, ...) is the stand-in for ``mesh.split()`` + a
     choice among the parts.
+    ``adjacency`` (a MeshAdjacency: the vertex neighbourhood as a CSR, boundary flags) and trimesh's ``vertex_neighbors``;
+    smooth_mesh(mesh, ...) is the stand-in for ``trimesh.smoothing.filter_taubin`` / ``filter_laplacian``.
 
     Built from a GPU tensor the mesh stays in HBM: ``device_triangles`` is that tensor (the turntable renders from it),
     the weld and the normals come from weld_mesh (csrc/mesh_weld.hip) on first access, and ``triangles`` / ``vertices`` /
@@ -675,6 +711,7 @@ class SimpleMesh(object):
         # again), the field's normals [V,3] fp32 on the device, and the device count [1] int32 of vertices that fell back
         self._device_weld = self.device_field_normals = self.field_normal_fallbacks = self._field_normals = None
         self._components = None                          # mesh_components(self), cached by the ``components`` property
+        self._adjacency = None                           # mesh_adjacency(self), cached by the ``adjacency`` property
         # set by mesh_vertex_colors(): colours uint8 [V,3], seen flags uint8 [V], colour sources int32 [V] and (seen area, total
         # area) fp64 [2] on the device, and the host copies the properties below make when read
         self.device_vertex_colors = self.device_vertex_seen = self.device_color_source = self.device_seen_area = None
@@ -731,6 +768,21 @@ class SimpleMesh(object):
         if self._components is None:
             self._components = mesh_components(self)
         return self._components
+
+    @property
+    def adjacency(self):
+        """mesh_adjacency(self), computed once: the vertex neighbourhood as a CSR with the boundary flags (a MeshAdjacency, on
+        the device for a GPU mesh until an array is read); smooth_mesh(mesh, ...) runs over it."""
+        if self._adjacency is None:
+            self._adjacency = mesh_adjacency(self)
+        return self._adjacency
+
+    @property
+    def vertex_neighbors(self):
+        """trimesh's name: a list of V int arrays, the indices of the vertices that share an edge with each vertex, ascending
+        (``adjacency`` split into its rows on the host)."""
+        adj = self.adjacency
+        return np.split(adj.neighbors, adj.offsets[1:-1]) if len(adj.offsets) > 1 else []
 
     @property
     def area(self):
@@ -1152,6 +1204,197 @@ def filter_components(mesh, min_component_area=None, drop_cavities=False, keep=N
     return SimpleMesh(out)
 
 
+# ---- vertex neighbourhood and smoothing (csrc/mesh_smooth.hip) ----
+
+class MeshAdjacency(object):
+    """The vertex neighbourhood of an indexed mesh (mesh_adjacency / mesh_adjacency_host) as a CSR:
+
+      offsets [V + 1] int32, neighbors [nnz] int32   row v = neighbors[offsets[v]:offsets[v + 1]]: the distinct other endpoints of
+                                                     v's edges, ascending (a face with two equal indices has no edges)
+      boundary [V] uint8                             1 iff some edge at the vertex is used by exactly one non-degenerate face
+      degree [V] int32                               offsets[1:] - offsets[:-1]
+      n_edges                                        int, nnz / 2: the unique undirected edges
+
+    From a GPU mesh the ``device_*`` tensors (offsets, neighbors, boundary) hold the results and the arrays above are host
+    copies made when first read; from a host mesh they are None."""
+
+    def __init__(self, offsets, neighbors, boundary):
+        self.device_offsets = self.device_neighbors = self.device_boundary = None
+        self._host = {}
+        given = dict(offsets=offsets, neighbors=neighbors, boundary=boundary)
+        if isinstance(offsets, torch.Tensor):
+            for key, value in given.items():
+                setattr(self, "device_" + key, value)
+        else:
+            self._host = given
+        self.n_edges = int(neighbors.shape[0]) // 2
+
+    def _read(self, key):
+        if key not in self._host:
+            self._host[key] = getattr(self, "device_" + key).cpu().numpy()
+        return self._host[key]
+
+    offsets = property(lambda self: self._read("offsets"))
+    neighbors = property(lambda self: self._read("neighbors"))
+    boundary = property(lambda self: self._read("boundary"))
+    degree = property(lambda self: np.diff(self.offsets).astype(np.int32))
+
+
+def mesh_adjacency_host(faces, n_vertices):
+    """The definition of MeshAdjacency and the checker of zs_mesh_adjacency, in numpy.  ``faces`` [F,3] the weld's indices over
+    ``n_vertices`` vertices.  A face with two equal indices (the components' rule for a degenerate face) contributes no
+    edges, every other face its three undirected edges; a duplicated edge is listed once; an edge is a boundary edge when
+    exactly one such face uses it (three or more uses: not a boundary edge)."""
+    V = int(n_vertices)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    assert len(f) == 0 or (f.min() >= 0 and f.max() < V)
+    g = f[~((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2]))]
+    a, b = g.reshape(-1), g[:, [1, 2, 0]].reshape(-1)                # every use of an edge, entered in both of its rows
+    key = np.concatenate([(a << 32) | b, (b << 32) | a])
+    entry, uses = np.unique(key, return_counts=True)                 # row after row, each row ascending
+    source = entry >> 32
+    boundary = np.zeros(V, np.uint8)
+    boundary[source[uses == 1]] = 1
+    offsets = np.searchsorted(source, np.arange(V + 1)).astype(np.int32)
+    return MeshAdjacency(offsets, (entry & 0xffffffff).astype(np.int32), boundary)
+
+
+def _check_smooth_arguments(iterations, lamb, mu):
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise ValueError("smooth_mesh: iterations must be an integer >= 0, got %r" % (iterations,))
+    if isinstance(lamb, bool) or not isinstance(lamb, (int, float, np.integer, np.floating)) or not (0.0 < float(lamb) <= 1.0):
+        raise ValueError("smooth_mesh: lamb must lie in (0, 1], got %r" % (lamb,))
+    if mu is not None and (isinstance(mu, bool) or not isinstance(mu, (int, float, np.integer, np.floating))
+                           or not (-1.0 <= float(mu) < 0.0)):
+        raise ValueError("smooth_mesh: mu must be None (every pass uses lamb) or lie in [-1, 0), got %r" % (mu,))
+
+
+def smooth_vertices_host(vertices, offsets, neighbors, boundary, iterations=10, lamb=0.5, mu=-0.53, pin_boundary=True):
+    """The definition of smooth_mesh's passes and the checker of zs_mesh_smooth, in numpy: ``vertices`` [V,3] float32 are widened
+    once to float64 and stay float64 between passes; pass t (from 0) uses f = ``lamb``, or f = ``mu`` when ``mu`` is given and t
+    is odd (trimesh's counting: 10 iterations are 5 lambda|mu pairs).  A vertex moves iff its degree is positive and it is not
+    pinned (``pin_boundary`` and its boundary flag set): s = 0, then s = s + x[neighbour] along its row in row order, m = s /
+    degree, x' = x + f * (m - x), every operation as written - the sum goes slot by slot (slot k of every row that has one), so
+    the float64 additions happen in the kernel's order.  The other vertices are copied.  After the last pass the positions are
+    rounded to float32 -> [V,3] float32; ``iterations`` = 0 returns the input's bits."""
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    x = smooth_positions_host(v32.astype(np.float64), offsets, neighbors, boundary, iterations, lamb, mu, pin_boundary)
+    return x.astype(np.float32)
+
+
+def smooth_positions_host(x, offsets, neighbors, boundary, iterations, lamb, mu, pin_boundary):
+    """The passes of smooth_vertices_host on float64 positions [V,3] -> float64 [V,3], before the rounding to float32."""
+    _check_smooth_arguments(iterations, lamb, mu)
+    x = np.asarray(x, np.float64).reshape(-1, 3)
+    if iterations == 0 or len(x) == 0:
+        return x.copy()
+    offsets, neighbors = np.asarray(offsets, np.int64), np.asarray(neighbors, np.int64)
+    V = len(x)
+    assert offsets.shape == (V + 1,) and offsets[0] == 0 and np.all(np.diff(offsets) >= 0) and offsets[-1] == len(neighbors)
+    assert len(neighbors) == 0 or (neighbors.min() >= 0 and neighbors.max() < V)
+    degree = np.diff(offsets)
+    moving = degree > 0
+    if pin_boundary:
+        moving &= np.asarray(boundary).reshape(-1) == 0
+    rows = np.flatnonzero(moving)
+    begin, count = offsets[rows], degree[rows]
+    by_slot = []                                                     # slot k: (positions among ``rows``, the neighbours there)
+    for k in range(int(count.max()) if len(rows) else 0):
+        has = np.flatnonzero(count > k)
+        by_slot.append((has, neighbors[begin[has] + k]))
+    d = count.astype(np.float64)[:, None]
+    for t in range(int(iterations)):
+        f = np.float64(mu if (mu is not None and t % 2 == 1) else lamb)
+        s = np.zeros((len(rows), 3), np.float64)
+        for has, nb in by_slot:
+            s[has] = s[has] + x[nb]
+        m = s / d
+        new = x.copy()
+        new[rows] = x[rows] + f * (m - x[rows])
+        x = new
+    return x
+
+
+def _adjacency_device(faces, n_verts):
+    """zs_mesh_adjacency on a welded GPU mesh -> MeshAdjacency of device tensors.  One 8-byte device-to-host copy: nnz, which
+    sizes ``neighbors``, with the kernels' status word beside it."""
+    from .. import _lib
+    lib = _lib.load()
+    n, dev = faces.shape[0], faces.device
+    offsets = torch.zeros(n_verts + 1, dtype=torch.int32, device=dev)
+    boundary = torch.zeros(n_verts, dtype=torch.uint8, device=dev)
+    neighbors = torch.empty(0, dtype=torch.int32, device=dev)
+    if n and n_verts:
+        nbytes = lib.zs_mesh_adjacency_scratch_bytes(n, n_verts)
+        if nbytes == 0:
+            raise _lib.ZeroShapeHipError("mesh_adjacency: %d faces over %d vertices exceed the kernels' limits" % (n, n_verts))
+        scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+        room = torch.empty(6 * n, dtype=torch.int32, device=dev)
+        out = torch.zeros(2, dtype=torch.int32, device=dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_adjacency(_lib.ptr(faces), n, n_verts, _lib.ptr(offsets), _lib.ptr(room), _lib.ptr(boundary),
+                                             _lib.ptr(out), _lib.ptr(scratch), _lib.current_stream_ptr(dev)), "zs_mesh_adjacency")
+            nnz, status = out.tolist()                       # 8-byte D2H: sizes the neighbour list
+        if status:
+            raise _lib.ZeroShapeHipError("zs_mesh_adjacency: status %d (a face index outside the vertices)" % status)
+        neighbors = room[:nnz].clone()
+    return MeshAdjacency(offsets, neighbors, boundary)
+
+
+@torch.no_grad()
+def mesh_adjacency(mesh):
+    """The vertex neighbourhood of a SimpleMesh -> MeshAdjacency (the semantics: mesh_adjacency_host).  A GPU mesh is processed
+    on the device (csrc/mesh_smooth.hip) from the weld it carries or, if it has none yet, from one weld_mesh call whose result
+    it then keeps, as mesh_components does; a mesh built from a host array goes through the host checker.
+    ``mesh.adjacency`` caches the result."""
+    if getattr(mesh, "device_triangles", None) is not None:
+        if mesh._device_weld is None:
+            mesh._device_weld = weld_mesh(mesh.device_triangles, normals=True)
+        vertices, faces = mesh._device_weld[0], mesh._device_weld[1]
+        return _adjacency_device(faces, vertices.shape[0])
+    return mesh_adjacency_host(mesh.faces, len(mesh.vertices))
+
+
+@torch.no_grad()
+def smooth_mesh(mesh, iterations=10, lamb=0.5, mu=-0.53, pin_boundary=True):
+    """A new SimpleMesh whose vertices are those of ``mesh`` after ``iterations`` smoothing passes over its vertex
+    neighbourhood (the semantics: smooth_vertices_host) and whose soup is those vertices gathered through the faces, in the
+    input's face order - trimesh's ``smoothing.filter_taubin`` / ``filter_laplacian`` with uniform weights.  Pass t uses
+    ``lamb`` (0 < lamb <= 1), or ``mu`` (-1 <= mu < 0) when t is odd: 10 iterations are 5 shrink|inflate pairs, which keep the
+    volume that plain Laplacian smoothing (``mu=None``: every pass uses ``lamb``) loses.  The defaults are Taubin's published
+    pair - a design choice, not a measurement.  With ``pin_boundary`` the vertices of open edges stay where they are.  A GPU
+    mesh stays in HBM (zs_mesh_smooth + zs_mesh_gather_faces on the weld and the adjacency it carries; one 4-byte read-back, the
+    status word); a host mesh is computed in numpy.  The new mesh carries nothing from the old one - no weld, components or
+    colours: smooth first, then colour.  An empty mesh gives an empty mesh."""
+    _check_smooth_arguments(iterations, lamb, mu)
+    adj = mesh.adjacency
+    if getattr(mesh, "device_triangles", None) is None:
+        moved = smooth_vertices_host(mesh.vertices, adj.offsets, adj.neighbors, adj.boundary, iterations, lamb, mu, pin_boundary)
+        return SimpleMesh(moved[mesh.faces] if len(mesh.faces) else mesh.triangles.copy())
+    from .. import _lib
+    lib = _lib.load()
+    vertices, faces = mesh._device_weld[0], mesh._device_weld[1]
+    n, n_verts, dev = faces.shape[0], vertices.shape[0], vertices.device
+    out = torch.empty(n, 3, 3, dtype=torch.float32, device=dev)
+    if n and n_verts:
+        moved = torch.empty_like(vertices)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        scratch = torch.empty(lib.zs_mesh_smooth_scratch_bytes(n_verts) // 8 + 1, dtype=torch.int64, device=dev)
+        stream = _lib.current_stream_ptr(dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_smooth(_lib.ptr(vertices), n_verts, _lib.ptr(adj.device_offsets), _lib.ptr(adj.device_neighbors),
+                                          _lib.ptr(adj.device_boundary) if pin_boundary else None, int(iterations), float(lamb),
+                                          0.0 if mu is None else float(mu), int(mu is not None), _lib.ptr(moved), _lib.ptr(status),
+                                          _lib.ptr(scratch), stream), "zs_mesh_smooth")
+            _lib.check(lib.zs_mesh_gather_faces(_lib.ptr(moved), _lib.ptr(faces), n, n_verts, _lib.ptr(out), stream),
+                       "zs_mesh_gather_faces")
+            bad = int(status.item())                         # 4-byte D2H, after everything is enqueued
+        if bad:
+            raise _lib.ZeroShapeHipError("zs_mesh_smooth: status %d (%s)" % (
+                bad, "a neighbour index outside the vertices" if bad & 2 else "a row of the adjacency runs backwards"))
+    return SimpleMesh(out)
+
+
 def mesh_report(mesh):
     """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
     per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``."""
@@ -1506,7 +1749,8 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
     like the reference (an empty mesh gives zeros, :262).  The random stream is a
     counter-based generator seeded by ``seed`` + the grid index, not numpy's global RNG.
     With ``opt.eval.min_component_area`` / ``opt.eval.drop_cavities`` set (opt-in) every mesh goes through
-    filter_components first, and the points are sampled on what is left."""
+    filter_components first, with ``opt.eval.smooth_iterations`` set (opt-in, _smooth_options) through smooth_mesh after
+    that, and the points are sampled on what comes out."""
     device = getattr(opt, "device", "cuda")
     meshes, clouds = [], []
     for i, g in enumerate(level_grids):
@@ -1514,14 +1758,14 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
         vol = vol.to(device)
         assert vol.shape[0] == vol.shape[1] == vol.shape[2]
         range_min, range_max = opt.eval.range
-        cleaning = _component_options(opt)
-        if cleaning is None:
+        cleaning, smoothing = _component_options(opt), _smooth_options(opt)
+        if cleaning is None and smoothing is None:
             tris, pts = extract_surface(vol, isoval, range_min, range_max,
                                         opt.eval.num_points if to_pointcloud else 0, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
-        else:                                            # marching cubes, filter_components, then sampling with the same seed
+        else:                                  # marching cubes, filter_components, smooth_mesh, then sampling with the same seed
             tris, _ = extract_surface(vol, isoval, range_min, range_max)
-            mesh = filter_components(SimpleMesh(tris), *cleaning)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i) if to_pointcloud else None
         meshes.append(mesh)
         if to_pointcloud:
