@@ -38,6 +38,14 @@ the component filter): Taubin passes over the vertex neighbourhood, which take t
 cubes without the shrinkage of plain Laplacian smoothing.  --eval.smooth_lambda (0.5) and --eval.smooth_mu (-0.53; none =
 plain Laplacian passes) are the two factors, --eval.smooth_free_boundary=true lets the vertices of open edges move too.
 
+--eval.simplify_cells=2.0 (opt-in, shape task) makes the mesh lighter on the GPU before it is written (eval_3D.simplify_mesh,
+after the component filter and the smoothing, before the colours and any sampling - so every number reported describes the
+mesh that is delivered): the vertices inside each cube of that many marching-cubes cells become one vertex, placed where the
+quadric error of the faces around them is smallest, and the faces that collapse or repeat are dropped (2 cells: about a fifth
+of the faces).  --eval.simplify_position=mean places the vertex at the cluster's mean instead.  Watertightness is not
+guaranteed - coarse cells join sheets that pass through one cell; with --eval.mesh_report=true the report says what came out
+and gains a `simplification` entry with the counts.
+
 --eval.vertex_colors=true (opt-in, shape task) colours the mesh from the input photo on the GPU (eval_3D.vertex_colors): a
 vertex the input camera saw takes the photo's bilinear texel, every other vertex the colour of the nearest seen one.
 <name>_mesh.obj then has `v x y z r g b` lines (the vertex-colour extension MeshLab, Blender and Open3D read), with --viz

@@ -509,6 +509,46 @@ int zs_mesh_smooth(const float *vertices, int n_verts, const int *offsets, const
 int zs_mesh_gather_faces(const float *vertices, const int *faces, int n_tris, int n_verts, float *out_tris, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Mesh simplification by uniform-grid vertex clustering with quadric-error placement
+ * (csrc/mesh_simplify.hip; the semantics are eval_3D.simplify_mesh_host's, bit for bit).
+ * vertices [n_verts,3] fp32 and faces [n_tris,3] int32 are the weld's (zs_mesh_weld); origin is
+ * a DEVICE pointer to 3 doubles (the caller may have computed it on the device: nothing is read
+ * back), cell the cluster edge, mode 1 = quadric placement, 0 = the cluster mean.
+ *   cells     : c = floor(((double)v - origin) / cell) per axis, each in [0, 2^21); vertices with
+ *               equal (cx, cy, cz) form a cluster; cluster ids ascend with cx << 42 | cy << 21 | cz.
+ *   mean      : in coordinates local to the cell centre origin + (c + 0.5) cell: the members'
+ *               local positions added in fp64 in ascending vertex index, divided by the count.
+ *   quadrics  : every (face, corner) adds, to the cluster of that corner's vertex, the plane
+ *               quadric n n^T / |n| of its face (n = (v1 - v0) x (v2 - v0), |n| = twice the area:
+ *               area weighting), built in fp64 from the three fp32 vertices in that cluster's local
+ *               coordinates; a face whose |n| is zero or not finite adds nothing.  Summed per
+ *               cluster in ascending 3 face + corner.
+ *   placement : minimise x^T A x + 2 b^T x + w |x - m|^2, w = 1e-3 trace(A) / 3 (the constant is a
+ *               design choice): (A + w I) x = w m - b by Cramer's rule.  The mean m instead when
+ *               the trace is not positive, x is not finite or some |x| component exceeds cell
+ *               (counted in out_counts[5]).  A cluster of one vertex keeps that vertex's bits.
+ *               representative = (float)(centre + x).
+ *   faces     : corners -> cluster ids; a face with two equal ids is dropped (degenerate); among
+ *               faces whose ids are equal up to rotation the first in input order is kept, the
+ *               others are dropped (duplicate); a face and its mirror image are both kept.  The
+ *               kept faces go to out_tris [n_tris,3,3] (room for every input face) in input face
+ *               order with the input's corner order, each corner its cluster's representative.
+ * out_counts[6] (device ints): kept, clusters, degenerate, duplicate, status, fallbacks.  status:
+ * 0, |1 when a coordinate is not finite or a cell index lies outside [0, 2^21) (such a vertex is
+ * put into cell 0), |2 when a face index lies outside [0, n_verts) (such a face is dropped and
+ * counted with the degenerate ones; no index is used as an address before it is tested).  The
+ * call only enqueues: it returns 1 whatever the status word will say.
+ * scratch, 8-byte aligned: zs_mesh_simplify_scratch_bytes(n_tris, n_verts) bytes (0 for empty and
+ * out-of-range sizes).  Limits: n_tris <= 2^28, n_verts <= 2^21 (three cluster ids share one 63-bit
+ * sort key), n_verts <= 3 n_tris.  Zero sizes return 1 and touch nothing.
+ * Every sum is walked by one thread in a fixed order and the counters are integer atomics: two
+ * runs give the same bytes.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_simplify_scratch_bytes(int n_tris, int n_verts);
+int zs_mesh_simplify(const float *vertices, const int *faces, int n_tris, int n_verts, const double *origin, double cell,
+                     int mode, float *out_tris, int *out_counts, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
  * itself is Implicit.field_gradient's, between the two calls).
  *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G

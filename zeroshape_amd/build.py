@@ -51,6 +51,8 @@ EXTRA = {
     "mesh_colors.hip": ["-ffp-contract=off"],
     # the fp64 neighbour sum, mean and step equal, operation for operation, to the numpy restatement in utils/eval_3D.py (smooth_vertices_host)
     "mesh_smooth.hip": ["-ffp-contract=off"],
+    # the fp64 cluster means, quadrics and Cramer solve equal, operation for operation, to the numpy restatement in utils/eval_3D.py (simplify_mesh_host)
+    "mesh_simplify.hip": ["-ffp-contract=off"],
 }
 
 

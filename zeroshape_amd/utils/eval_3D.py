@@ -23,6 +23,8 @@ reference) runs on the GPU here: csrc/marching_cubes.hip (SURVEY.md section 8f r
 their triangles in HBM; the indexed form and the vertex normals come from csrc/mesh_weld.hip (``weld_mesh``) when read.
 """
 
+import collections
+
 import numpy as np
 import os
 
@@ -526,14 +528,14 @@ def _surface_clouds(opt, level_vox, seed=0):
     reference (utils/eval_3D.py:115-118,181-184)."""
     meshes, clouds = [], []
     range_min, range_max = opt.eval.range
-    cleaning, smoothing = _component_options(opt), _smooth_options(opt)
+    cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
     for i in range(level_vox.shape[0]):
-        if cleaning is None and smoothing is None:
+        if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
-        else:                                            # eval.min_component_area / eval.drop_cavities, then eval.smooth_*:
-            tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)          # sample the cleaned, smoothed mesh
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing)
+        else:                              # eval.min_component_area / eval.drop_cavities, eval.smooth_*, eval.simplify_cells:
+            tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)          # sample the mesh that is delivered
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i)
         meshes.append(mesh)
         clouds.append(pts)
@@ -575,12 +577,46 @@ def _smooth_options(opt):
     return args
 
 
-def _cleaned_and_smoothed(mesh, cleaning, smoothing):
-    """The opt-in steps between marching cubes and sampling, in their order: filter_components, then smooth_mesh."""
+SIMPLIFY_OPTIONS = ("simplify_cells", "simplify_position")
+
+
+def _mc_cell_edge(opt):
+    """A cell of the evaluation grid in mesh units, as default_color_depth_tol counts it."""
+    range_min, range_max = opt.eval.range
+    return (float(range_max) - float(range_min)) / float(opt.eval.vox_res)
+
+
+def _simplify_options(opt):
+    """(cell, origin, position) for simplify_mesh when ``--eval.simplify_cells=2.0`` is set (opt-in, command line only: no yaml
+    file carries it), else None: the pipelines then make today's calls.  The value is the cluster edge in marching-cubes cells
+    (_mc_cell_edge: the unit of default_color_depth_tol); the cluster planes sit half such a cell below ``eval.range``'s
+    minimum, so that with an integer setting the lattice coordinates of the marching-cubes vertices do not lie on them.
+    ``--eval.simplify_position=mean`` takes the cluster means instead of the quadric minimisers; without the cell count it is
+    an error, not ignored."""
+    cells = opt.eval.get("simplify_cells", None)
+    if cells is None:
+        if "simplify_position" in opt.eval:
+            raise ValueError("eval.simplify_position needs eval.simplify_cells")
+        return None
+    if isinstance(cells, bool) or not isinstance(cells, (int, float, np.integer, np.floating)) or not (0.0 < float(cells) < np.inf):
+        raise ValueError("eval.simplify_cells must be a finite number > 0, got %r" % (cells,))
+    position = opt.eval.get("simplify_position", "quadric")
+    edge = _mc_cell_edge(opt)
+    cell = float(cells) * edge
+    _check_simplify_arguments(cell, position)
+    return cell, (float(opt.eval.range[0]) - 0.5 * edge,) * 3, position
+
+
+def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None):
+    """The opt-in steps between marching cubes and sampling, in their order: filter_components, then smooth_mesh, then
+    simplify_mesh - last, so that the colours, the sampled points and with them the metrics describe the mesh that is
+    delivered."""
     if cleaning is not None:
         mesh = filter_components(mesh, *cleaning)
     if smoothing is not None:
         mesh = smooth_mesh(mesh, *smoothing)
+    if simplifying is not None:
+        mesh = simplify_mesh(mesh, *simplifying)
     return mesh
 
 
@@ -1395,15 +1431,265 @@ def smooth_mesh(mesh, iterations=10, lamb=0.5, mu=-0.53, pin_boundary=True):
     return SimpleMesh(out)
 
 
+# ---- simplification: vertex clustering with quadric-error placement (csrc/mesh_simplify.hip) ----
+
+# The weight of the pull towards the cluster mean relative to the mean eigenvalue of the cluster's quadric: a design choice, not
+# a measurement (MSIMP_RHO of csrc/mesh_simplify.hip is the same number).  It keeps the system solvable where the quadric
+# alone is singular (a flat or straight-creased neighbourhood) and is too small to move a well-determined minimiser visibly.
+SIMPLIFY_RHO = 1e-3
+SIMPLIFY_POSITIONS = ("mean", "quadric")                 # zs_mesh_simplify: mode
+SIMPLIFY_CELL_BITS = 21                                  # cells per axis: [0, 2^21)
+SIMPLIFY_MAX_VERTICES = 1 << 21                          # three cluster ids share one 63-bit key
+
+MeshSimplification = collections.namedtuple(
+    "MeshSimplification", "cell origin position input_faces clusters degenerate_faces duplicate_faces kept_faces fallbacks")
+MeshSimplification.__doc__ = """What simplify_mesh did, on the mesh it returns (``mesh.simplification``): ``cell`` (float), ``origin``
+(3 floats), ``position`` ("quadric" or "mean"), and the counts - ``input_faces`` = ``kept_faces`` + ``degenerate_faces`` (two
+corners in one cluster) + ``duplicate_faces`` (a kept face already has these three clusters in this rotation), ``clusters`` (the
+occupied cells), ``fallbacks`` (clusters of two or more vertices where quadric placement was asked for and the mean was
+taken)."""
+
+SimplifiedHost = collections.namedtuple("SimplifiedHost", "triangles cluster_of representatives kept fell_back counts")
+
+
+def _sums_in_order(values, starts, counts, short=64):
+    """Per segment i of the rows of ``values`` [N,k] float64 (rows starts[i] .. starts[i] + counts[i]): s = 0, then s = s + row,
+    row after row - the additions of one thread that walks the segment.  Segments of up to ``short`` rows go slot by slot (slot k
+    of every segment that has one), the longer ones one at a time through np.add.accumulate, which adds in index order; both are
+    that sequence of float64 additions -> [S,k]."""
+    sums = np.zeros((len(starts), values.shape[1]), np.float64)
+    if len(starts) == 0:
+        return sums
+    small = counts <= short
+    for k in range(int(counts[small].max()) if small.any() else 0):
+        has = np.flatnonzero(small & (counts > k))
+        sums[has] = sums[has] + values[starts[has] + k]
+    zero = np.zeros((1, values.shape[1]), np.float64)
+    for i in np.flatnonzero(~small):
+        sums[i] = np.add.accumulate(np.concatenate([zero, values[starts[i]:starts[i] + counts[i]]]), axis=0)[-1]
+    return sums
+
+
+def _check_simplify_arguments(cell, position):
+    if isinstance(cell, bool) or not isinstance(cell, (int, float, np.integer, np.floating)) or not (0.0 < float(cell) < np.inf):
+        raise ValueError("simplify_mesh: cell must be a finite number > 0, got %r" % (cell,))
+    if position not in SIMPLIFY_POSITIONS:
+        raise ValueError("simplify_mesh: position must be 'quadric' or 'mean', got %r" % (position,))
+
+
+def _simplify_origin(origin):
+    try:
+        o = np.asarray(origin, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        o = np.zeros(0)
+    if o.shape != (3,) or not np.all(np.isfinite(o)):
+        raise ValueError("simplify_mesh: origin must be None or three finite numbers, got %r" % (origin,))
+    return o
+
+
+def simplify_mesh_host(vertices, faces, origin, cell, position="quadric"):
+    """The definition of simplify_mesh and the checker of zs_mesh_simplify, in numpy: uniform-grid vertex clustering
+    (Rossignac-Borrel) with quadric-error placement (Lindstrom; Open3D's ``simplify_vertex_clustering``) of an indexed mesh -
+    ``vertices`` [V,3] float32, ``faces`` [F,3] - on the grid of edge ``cell`` (float64) whose planes pass through ``origin``
+    (3 float64).  Every formula is elementwise float64 in the order written; every sum goes through _sums_in_order.
+
+      cells       c = floor((float64(v) - origin) / cell) per axis, each in [0, 2^21): ValueError for a coordinate that is not
+                  finite or a c outside.  Vertices with equal c are one cluster; ids ascend with cx << 42 | cy << 21 | cz, and
+                  inside a cluster the members are taken in ascending vertex index (a stable sort).
+      mean        in coordinates local to the cell centre origin + (c + 0.5) * cell: s = 0, s = s + (float64(v) - centre) over
+                  the members, m = s / count.
+      quadrics    (``position`` = "quadric") every (face, corner) adds, to the cluster of that corner's vertex, its face's plane
+                  quadric in THAT cluster's local coordinates: p, q, r = the three vertices minus the centre, n = (q - p) x (r - p),
+                  |n| = sqrt((n0 n0 + n1 n1) + n2 n2), d = -((n0 p0 + n1 p1) + n2 p2); A += (n_i n_j) / |n|, b += (n_i d) / |n| -
+                  the weighting is n n^T / |n|: the unit normal's quadric times twice the face's area.  (The constant term
+                  d d / |n|, the tenth entry, does not enter the minimiser and is not kept.)  A face whose |n| is zero or not
+                  finite adds nothing.  Per cluster the terms are added in ascending 3 * face + corner.
+      placement   minimise x^T A x + 2 b^T x + w |x - m|^2 with w = SIMPLIFY_RHO * trace(A) / 3: (A + w I) x = w m - b solved by
+                  Cramer's rule through the six cofactors of the symmetric matrix.  The mean m is taken instead (a
+                  ``fallback``) when the trace is not positive, x is not finite or some |x| component exceeds ``cell``;
+                  ``position`` = "mean" always takes m.  representative = float32(centre + x); a cluster of one vertex keeps that
+                  vertex's bits.
+      faces       corners -> cluster ids.  A face with two equal ids is dropped (``degenerate``).  The others are compared
+                  after rotating the smallest id to the front, which keeps the orientation: of faces with the same rotated triple
+                  the first in input order is kept, the others are dropped (``duplicate``).  A face and its mirror image
+                  (opposite orientation) are both kept, as Open3D keeps them.  The kept faces come out in input face order
+                  with the input's corner order, each corner its cluster's representative.
+
+    Two guarantees follow: every input vertex lies within 1.5 * ``cell`` of its cluster's representative per axis, up to the
+    float32 rounding (half a cell to the centre, at most one from there), and when no two vertices share a cell and no input
+    face has two equal indices the output is the input's soup, bit for bit, in the input's order.  Manifoldness and
+    watertightness are NOT guaranteed: two sheets that pass through one cell are joined there.
+    -> SimplifiedHost(triangles [kept,3,3] float32, cluster_of [V] int64, representatives [clusters,3] float32, kept [F] bool,
+    fell_back [clusters] bool, counts dict(kept, clusters, degenerate, duplicate, fallbacks))."""
+    _check_simplify_arguments(cell, position)
+    o, h = _simplify_origin(origin), np.float64(cell)
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    V, F = len(v32), len(f)
+    if V > SIMPLIFY_MAX_VERTICES:
+        raise ValueError("simplify_mesh: %d vertices exceed the limit of 2^21" % V)
+    if F and (f.min() < 0 or f.max() >= V):
+        raise ValueError("simplify_mesh: a face index lies outside the vertices")
+    if V == 0 or F == 0:
+        return SimplifiedHost(np.zeros((0, 3, 3), np.float32), np.zeros(V, np.int64), np.zeros((0, 3), np.float32),
+                              np.zeros(F, bool), np.zeros(0, bool), dict(kept=0, clusters=0, degenerate=0, duplicate=0, fallbacks=0))
+    x = v32.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        t = np.floor((x - o) / h)
+        if not (np.all(np.isfinite(x)) and np.all((t >= 0.0) & (t < float(1 << SIMPLIFY_CELL_BITS)))):
+            raise ValueError("simplify_mesh: a vertex is not finite or lies outside the 2^21 cells per axis of this grid")
+    c = t.astype(np.int64)
+    key = (c[:, 0] << (2 * SIMPLIFY_CELL_BITS)) | (c[:, 1] << SIMPLIFY_CELL_BITS) | c[:, 2]
+    order = np.argsort(key, kind="stable")                           # cluster after cluster, members in ascending vertex index
+    skey = key[order]
+    head = np.concatenate([[True], skey[1:] != skey[:-1]])
+    cid_sorted = np.cumsum(head) - 1
+    cluster_of = np.empty(V, np.int64)
+    cluster_of[order] = cid_sorted
+    starts = np.flatnonzero(head)
+    C = len(starts)
+    counts = np.diff(np.concatenate([starts, [V]]))
+    centre = o + (c[order[starts]].astype(np.float64) + 0.5) * h     # [C,3]
+    mean = _sums_in_order(x[order] - centre[cid_sorted], starts, counts) / counts.astype(np.float64)[:, None]
+    local = mean
+    fell_back = np.zeros(C, bool)
+    if position == "quadric":
+        corner_cluster = cluster_of[f.reshape(-1)]
+        iorder = np.argsort(corner_cluster, kind="stable")           # key cluster << bits | (3 face + corner), ascending
+        icluster = corner_cluster[iorder]
+        face = f[iorder // 3]
+        ce = centre[icluster]
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            p, q, r = x[face[:, 0]] - ce, x[face[:, 1]] - ce, x[face[:, 2]] - ce
+            u, w = q - p, r - p
+            n0 = u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1]
+            n1 = u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2]
+            n2 = u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
+            length = np.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+            d = -((n0 * p[:, 0] + n1 * p[:, 1]) + n2 * p[:, 2])
+            has_normal = (length > 0.0) & (length < np.inf)
+            terms = np.stack([(n0 * n0) / length, (n0 * n1) / length, (n0 * n2) / length, (n1 * n1) / length, (n1 * n2) / length,
+                              (n2 * n2) / length, (n0 * d) / length, (n1 * d) / length, (n2 * d) / length], axis=1)
+            terms = np.where(has_normal[:, None], terms, 0.0)        # (s + 0.0 == s: a sum that starts at +0.0 is never -0.0)
+            istarts = np.searchsorted(icluster, np.arange(C))
+            icounts = np.bincount(corner_cluster, minlength=C)
+            a00, a01, a02, a11, a12, a22, b0, b1, b2 = _sums_in_order(terms, istarts, icounts).T
+            trace = (a00 + a11) + a22
+            wt = (SIMPLIFY_RHO * trace) / 3.0
+            M00, M11, M22, M01, M02, M12 = a00 + wt, a11 + wt, a22 + wt, a01, a02, a12
+            m0, m1, m2 = mean.T
+            r0, r1, r2 = wt * m0 - b0, wt * m1 - b1, wt * m2 - b2
+            C00, C01, C02 = M11 * M22 - M12 * M12, M02 * M12 - M01 * M22, M01 * M12 - M02 * M11
+            C11, C12, C22 = M00 * M22 - M02 * M02, M01 * M02 - M00 * M12, M00 * M11 - M01 * M01
+            det = (M00 * C00 + M01 * C01) + M02 * C02
+            y = np.stack([((C00 * r0 + C01 * r1) + C02 * r2) / det, ((C01 * r0 + C11 * r1) + C12 * r2) / det,
+                          ((C02 * r0 + C12 * r1) + C22 * r2) / det], axis=1)
+            ok = (trace > 0.0) & np.all(np.abs(y) <= h, axis=1)      # (False for NaN)
+        local = np.where(ok[:, None], y, mean)
+        fell_back = ~ok & (counts > 1)
+    rep = (centre + local).astype(np.float32)
+    single = counts == 1
+    rep[single] = v32[order[starts[single]]]
+    # faces
+    g = cluster_of[f]
+    a, b, cc = g[:, 0], g[:, 1], g[:, 2]
+    degenerate = (a == b) | (b == cc) | (a == cc)
+    first = np.where((a < b) & (a < cc), 0, np.where(b < cc, 1, 2))
+    rows = np.arange(F)
+    triple = (g[rows, first] << (2 * SIMPLIFY_CELL_BITS)) | (g[rows, (first + 1) % 3] << SIMPLIFY_CELL_BITS) | g[rows, (first + 2) % 3]
+    good = np.flatnonzero(~degenerate)
+    forder = good[np.argsort(triple[good], kind="stable")]           # equal triples in input face order
+    ft = triple[forder]
+    fhead = np.concatenate([[True], ft[1:] != ft[:-1]]) if len(ft) else np.zeros(0, bool)
+    kept = np.zeros(F, bool)
+    kept[forder[fhead]] = True
+    out_counts = dict(kept=int(kept.sum()), clusters=int(C), degenerate=int(degenerate.sum()),
+                      duplicate=int(len(good) - fhead.sum()), fallbacks=int(fell_back.sum()))
+    return SimplifiedHost(rep[g[kept]], cluster_of, rep, kept, fell_back, out_counts)
+
+
+def _simplified(triangles, cell, origin, position, n_faces, counts):
+    mesh = SimpleMesh(triangles)
+    mesh.simplification = MeshSimplification(float(cell), tuple(float(v) for v in origin), position, int(n_faces), counts["clusters"],
+                                             counts["degenerate"], counts["duplicate"], counts["kept"], counts["fallbacks"])
+    return mesh
+
+
+@torch.no_grad()
+def simplify_mesh(mesh, cell, origin=None, position="quadric"):
+    """A new, lighter SimpleMesh: the vertices of ``mesh`` that share a cell of the uniform grid of edge ``cell`` through
+    ``origin`` become one vertex - placed where the quadric error of the faces around them is smallest (``position`` =
+    "quadric": keeps edges, corners and the volume better) or at their mean ("mean") - and the faces that collapse or repeat
+    are dropped: the semantics are simplify_mesh_host's, the stand-in for Open3D's ``simplify_vertex_clustering`` /
+    trimesh-side decimation.  ``origin`` None is the per-axis minimum of the vertices (exact in float32 on either path).  A face
+    and its opposite-orientation twin are both kept, as Open3D keeps them.  Every input vertex lies within 1.5 ``cell`` per axis
+    of the vertex that replaces it; a mesh whose vertices all have a cell of their own comes back bit for bit.  Manifoldness
+    and watertightness are not guaranteed - coarse cells join sheets that pass through one cell: ``mesh_report`` of the result
+    says what came out.  A GPU mesh stays in HBM (zs_mesh_simplify on the weld it carries or, if it has none yet, on one
+    weld_mesh call whose result it then keeps; one small read-back at the end: the counts, the status word and the origin); a
+    host mesh is computed in numpy.  The new mesh carries nothing from the old one - no weld, components, adjacency, normals or
+    colours: simplify first, then colour - and one extra attribute, ``simplification`` (a MeshSimplification).  ValueError for
+    a ``cell`` that is not finite and positive, an unknown ``position``, a vertex that is not finite or a grid finer than 2^21
+    cells per axis over the mesh.  An empty mesh gives an empty mesh."""
+    _check_simplify_arguments(cell, position)
+    given = None if origin is None else _simplify_origin(origin)
+    zero = dict(kept=0, clusters=0, degenerate=0, duplicate=0, fallbacks=0)
+    if getattr(mesh, "device_triangles", None) is None:
+        vertices, faces = mesh.vertices, mesh.faces
+        if len(faces) == 0:
+            return _simplified(np.zeros((0, 3, 3), np.float32), cell, np.zeros(3) if given is None else given, position, 0, zero)
+        o = vertices.min(axis=0).astype(np.float64) if given is None else given
+        done = simplify_mesh_host(vertices, faces, o, cell, position)
+        return _simplified(done.triangles, cell, o, position, len(faces), done.counts)
+    from .. import _lib
+    lib = _lib.load()
+    if mesh._device_weld is None:
+        mesh._device_weld = weld_mesh(mesh.device_triangles, normals=True)
+    vertices, faces = mesh._device_weld[0], mesh._device_weld[1]
+    n, n_verts, dev = faces.shape[0], vertices.shape[0], vertices.device
+    if n == 0 or n_verts == 0:
+        return _simplified(torch.empty(0, 3, 3, dtype=torch.float32, device=dev), cell, np.zeros(3) if given is None else given,
+                           position, n, zero)
+    nbytes = lib.zs_mesh_simplify_scratch_bytes(n, n_verts)
+    if nbytes == 0:
+        raise _lib.ZeroShapeHipError("simplify_mesh: %d faces over %d vertices exceed the kernels' limits" % (n, n_verts))
+    if given is None:
+        o = vertices.amin(dim=0).to(torch.float64)                   # stays on the device: the kernels read it there
+    else:
+        o = torch.tensor(given, dtype=torch.float64, device=dev)
+    room = torch.empty(n, 3, 3, dtype=torch.float32, device=dev)
+    counts = torch.zeros(6, dtype=torch.int32, device=dev)
+    scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+    with _lib.on(dev):
+        _lib.check(lib.zs_mesh_simplify(_lib.ptr(vertices), _lib.ptr(faces), n, n_verts, _lib.ptr(o), float(cell),
+                                        SIMPLIFY_POSITIONS.index(position), _lib.ptr(room), _lib.ptr(counts), _lib.ptr(scratch),
+                                        _lib.current_stream_ptr(dev)), "zs_mesh_simplify")
+        tail = torch.cat([o, counts.to(torch.float64)]).tolist()     # the one D2H, after everything is enqueued: 72 bytes
+    kept, clusters, degenerate, duplicate, status, fallbacks = (int(v) for v in tail[3:])
+    if status & 2:
+        raise _lib.ZeroShapeHipError("zs_mesh_simplify: status %d (a face index outside the vertices)" % status)
+    if status:
+        raise ValueError("simplify_mesh: a vertex is not finite or lies outside the 2^21 cells per axis of this grid "
+                         "(zs_mesh_simplify: status %d)" % status)
+    return _simplified(room[:kept].clone(), cell, tail[:3], position, n,
+                       dict(kept=kept, clusters=clusters, degenerate=degenerate, duplicate=duplicate, fallbacks=fallbacks))
+
+
 def mesh_report(mesh):
     """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
-    per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``."""
+    per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``, and a mesh that
+    simplify_mesh made its ``simplification`` (the cell, the origin, the placement and the counts: with ``is_watertight`` and
+    the component table beside it, what the clustering did to the surface)."""
     comps = mesh.components
     report = dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
                   area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
                   component_table=comps.table())
     if getattr(mesh, "device_vertex_colors", None) is not None:
         report["seen_area_fraction"] = mesh.seen_area_fraction
+    if getattr(mesh, "simplification", None) is not None:
+        record = mesh.simplification._asdict()
+        record["origin"] = list(record["origin"])
+        report["simplification"] = record
     return report
 
 
@@ -1750,7 +2036,8 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
     counter-based generator seeded by ``seed`` + the grid index, not numpy's global RNG.
     With ``opt.eval.min_component_area`` / ``opt.eval.drop_cavities`` set (opt-in) every mesh goes through
     filter_components first, with ``opt.eval.smooth_iterations`` set (opt-in, _smooth_options) through smooth_mesh after
-    that, and the points are sampled on what comes out."""
+    that, with ``opt.eval.simplify_cells`` set (opt-in, _simplify_options) through simplify_mesh last, and the points are
+    sampled on what comes out: the metrics describe the mesh that is delivered."""
     device = getattr(opt, "device", "cuda")
     meshes, clouds = [], []
     for i, g in enumerate(level_grids):
@@ -1758,14 +2045,14 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
         vol = vol.to(device)
         assert vol.shape[0] == vol.shape[1] == vol.shape[2]
         range_min, range_max = opt.eval.range
-        cleaning, smoothing = _component_options(opt), _smooth_options(opt)
-        if cleaning is None and smoothing is None:
+        cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
+        if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(vol, isoval, range_min, range_max,
                                         opt.eval.num_points if to_pointcloud else 0, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
-        else:                                  # marching cubes, filter_components, smooth_mesh, then sampling with the same seed
+        else:                   # marching cubes, filter_components, smooth_mesh, simplify_mesh, then sampling with the same seed
             tris, _ = extract_surface(vol, isoval, range_min, range_max)
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i) if to_pointcloud else None
         meshes.append(mesh)
         if to_pointcloud:
