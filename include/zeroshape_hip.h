@@ -74,7 +74,15 @@ const char *zs_last_error(void);
  * the reference kernel under nvcc's default FMA contraction); ties resolve to the
  * LOWEST index (chamfer3D.cu:36,126).  If the other cloud is empty the outputs of
  * that direction are left untouched (the reference kernel writes nothing either;
- * its caller pre-zeroes them, dist_chamfer_3D.py:29-38). */
+ * its caller pre-zeroes them, dist_chamfer_3D.py:29-38).
+ * Non-finite points (zs_chamfer_forward and zs_chamfer_forward_ws alike, bit for bit): every
+ * query starts from the record (+inf, index 0) and a candidate replaces it only on a strict
+ * d < best, in index order.  So a candidate whose distance is NaN never wins; a query with a
+ * NaN coordinate gets (+inf, 0); a distance of +inf never replaces the initial (+inf, 0).
+ * This is NOT the reference's behaviour: its kernel takes the first candidate of every
+ * 512-candidate tile unconditionally, so its answer depends on where a NaN sits, and the test
+ * oracle (oracle/chamfer_ref.c) takes candidate 0 unconditionally - a NaN in candidate 0 or in
+ * the query makes its distance NaN.  On NaN-free input all of them agree. */
 int zs_chamfer_forward(const float *xyz1, const float *xyz2, int b, int n, int m,
                        float *dist1, float *dist2, int *idx1, int *idx2, void *stream);
 

@@ -16,8 +16,12 @@
  *  - argmin tie rule: inside a 512-point tile a later candidate wins only on
  *    strict d<best (:36,:46,...); across tiles the stored result is replaced only
  *    on strict result>best (:126).  Net effect: the LOWEST index among equal
- *    minima wins, and the tiling does not change the answer.  nm_distance()
- *    therefore scans linearly with strict '<'.
+ *    minima wins, and for NaN-free input the tiling does not change the answer
+ *    (the first candidate of every tile is taken unconditionally, so a NaN
+ *    distance there survives the tile).  nm_distance() therefore scans linearly
+ *    with strict '<'; it takes candidate 0 unconditionally, where the HIP kernels
+ *    start from (+inf, 0): see include/zeroshape_hip.h for their rule on
+ *    non-finite points.
  *  - outputs are SQUARED distances; the caller takes sqrt (utils/eval_3D.py:269).
  *  - backward accumulates with atomicAdd in a non-deterministic order on the
  *    GPU; here the order is (batch, point) ascending, first direction then second.

@@ -148,8 +148,10 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_fit_kernel(const float *__res
     for (int k = 0; k < 3; k++)
         for (int l = 0; l < 3; l++) S[k][l] = H[0][k] * H[0][l] + H[1][k] * H[1][l] + H[2][k] * H[2][l];   // H^T H
     jacobi3(S, V);
-    // order the triplets by decreasing singular value; u_i = H v_i / s_i, the last one completed by a cross product
-    // when its singular value vanishes (a planar or collinear cloud)
+    // order the triplets by decreasing singular value; u_i = H v_i / s_i.  s_i = sqrt(eigenvalue) is only good down to
+    // ~1e-8 smax (the eigenvalue carries an absolute error of ~1e-16 smax^2), so below 1e-4 smax u_i is H v_i over its own
+    // norm, and where that vanishes too (a planar or collinear cloud, coincident points) U is completed to a rotation: the
+    // last column by a cross product, the middle one by any unit vector orthogonal to the first
     int ord[3] = {0, 1, 2};
     for (int i = 0; i < 2; i++)
         for (int j = i + 1; j < 3; j++)
@@ -160,14 +162,26 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_fit_kernel(const float *__res
         const int c = ord[i];
         for (int k = 0; k < 3; k++) Vs[k][i] = V[k][c];
         const double sv = sqrt(fmax(S[c][c], 0.0));
-        if (sv > 1e-12 * smax && sv > 0.0) {
-            for (int k = 0; k < 3; k++) U[k][i] = (H[k][0] * V[0][c] + H[k][1] * V[1][c] + H[k][2] * V[2][c]) / sv;
+        double hv[3];
+        for (int k = 0; k < 3; k++) hv[k] = H[k][0] * V[0][c] + H[k][1] * V[1][c] + H[k][2] * V[2][c];
+        const double nrm = sqrt(hv[0] * hv[0] + hv[1] * hv[1] + hv[2] * hv[2]);
+        if (sv > 1e-4 * smax && sv > 0.0) {
+            for (int k = 0; k < 3; k++) U[k][i] = hv[k] / sv;
+        } else if (nrm > 1e-6 * smax && nrm > 0.0) {
+            for (int k = 0; k < 3; k++) U[k][i] = hv[k] / nrm;
         } else if (i == 2) {
             U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
             U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
             U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+        } else if (i == 1) {                                                // one direction: the axis U[:, 0] is least along
+            const int a = fabs(U[0][0]) <= fabs(U[1][0]) ? (fabs(U[0][0]) <= fabs(U[2][0]) ? 0 : 2)
+                                                         : (fabs(U[1][0]) <= fabs(U[2][0]) ? 1 : 2);
+            double w[3];
+            for (int k = 0; k < 3; k++) w[k] = (k == a ? 1.0 : 0.0) - U[a][0] * U[k][0];
+            const double wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+            for (int k = 0; k < 3; k++) U[k][1] = w[k] / wn;
         } else {
-            for (int k = 0; k < 3; k++) U[k][i] = k == i ? 1.0 : 0.0;       // degenerate input (fewer than two directions)
+            for (int k = 0; k < 3; k++) U[k][0] = k == 0 ? 1.0 : 0.0;       // H = 0 (one point, coincident points): R = I
         }
     }
     double R[3][3];

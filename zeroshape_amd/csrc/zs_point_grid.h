@@ -95,7 +95,10 @@ __device__ __forceinline__ void point_grid_build(POINT point, int mc, float *__r
         if (!(ext[a] > 0.f) || !isfinite(ext[a])) ext[a] = 0.f;   // flat or non-finite axis: one slab
         maxabs = fmaxf(maxabs, fmaxf(fabsf(mn[a]), fabsf(mx[a])));
     }
-    if (!isfinite(maxabs)) maxabs = 0.f;
+    // an infinite coordinate hides the magnitude of the finite ones, and with it the rounding of the cell faces: no margin
+    // can be stated, so the slack below becomes +inf - no bound is ever positive, every query scans every cell (exact)
+    const bool unbounded = !isfinite(maxabs);
+    if (unbounded) maxabs = 0.f;
     g.minx = mn[0]; g.miny = mn[1]; g.minz = mn[2];
     g.cx = ext[0] / na; g.cy = ext[1] / na; g.cz = ext[2] / na;
     g.ix = ext[0] > 0.f ? na / ext[0] : 0.f;
@@ -103,7 +106,7 @@ __device__ __forceinline__ void point_grid_build(POINT point, int mc, float *__r
     g.iz = ext[2] > 0.f ? na / ext[2] : 0.f;
     // cell assignment and cell faces are computed with different roundings: a few ulps of the
     // coordinates / extents of slack keep the bound conservative
-    g.slack = 8e-7f * (maxabs + ext[0] + ext[1] + ext[2]);
+    g.slack = unbounded ? INFINITY : 8e-7f * (maxabs + ext[0] + ext[1] + ext[2]);
     if (tid == 0) {
         slot[0] = g.minx; slot[1] = g.miny; slot[2] = g.minz;
         slot[3] = g.cx; slot[4] = g.cy; slot[5] = g.cz;
