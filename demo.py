@@ -46,6 +46,13 @@ of the faces).  --eval.simplify_position=mean places the vertex at the cluster's
 guaranteed - coarse cells join sheets that pass through one cell; with --eval.mesh_report=true the report says what came out
 and gains a `simplification` entry with the counts.
 
+--eval.mesh_deviation=true (opt-in, with --eval.smooth_iterations or --eval.simplify_cells; an error without either) measures
+how far the smoothing and the simplification moved the surface (eval_3D.mesh_deviation, exact point-to-triangle distances on
+the GPU): the distance of every vertex of the delivered mesh to the surface marching cubes extracted (after the component
+filter: dropping floaters is intended) and of every vertex of that surface to the delivered mesh.  With --eval.mesh_report=true
+the report gains a `deviation` entry: max, mean, rms and the vertex at the maximum for both directions, in mesh units and in
+marching-cubes cells.  It is sampled at the vertices: a lower bound on the Hausdorff distance, not the continuous one.
+
 --eval.vertex_colors=true (opt-in, shape task) colours the mesh from the input photo on the GPU (eval_3D.vertex_colors): a
 vertex the input camera saw takes the photo's bilinear texel, every other vertex the colour of the nearest seen one.
 <name>_mesh.obj then has `v x y z r g b` lines (the vertex-colour extension MeshLab, Blender and Open3D read), with --viz

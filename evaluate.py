@@ -13,7 +13,9 @@ search's rotations (BASELINE config 5: "SDF grid sharded 8-way with RCCL all-gat
 With --eval.dump_results the per-sample dumps take the demo's opt-in switches: --eval.vertex_colors=true (with
 --eval.color_fade=<mesh units>, --eval.color_min_cos, --eval.color_supersample) colours <idx>_mesh.obj and the turntable from
 the input photo on the GPU (eval_3D.vertex_colors), and --eval.mesh_report=true writes <idx>_mesh_report.json, with the
-seen area fraction of a coloured mesh.
+seen area fraction of a coloured mesh.  --eval.mesh_deviation=true (with --eval.smooth_iterations or --eval.simplify_cells; an
+error without either) records on every predicted mesh how far those steps moved the surface (eval_3D.mesh_deviation: vertex to
+surface distances both ways, on the GPU); the report then carries a `deviation` entry.
 
 ZS_VIRTUAL_RANKS=N (with ZS_DEVICE_OVERRIDE=0 ZS_DIST_BACKEND=gloo) rehearses the N-rank path on one GPU.
 """

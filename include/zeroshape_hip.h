@@ -557,6 +557,44 @@ int zs_mesh_simplify(const float *vertices, const int *faces, int n_tris, int n_
                      int mode, float *out_tris, int *out_counts, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Exact distance from points to a triangle mesh (csrc/mesh_distance.hip; the semantics are
+ * eval_3D.closest_point_on_mesh_host's, bit for bit).  vertices [n_verts,3] fp32 and faces
+ * [n_faces,3] int32 are the weld's (zs_mesh_weld), queries [n_queries,3] fp32.
+ * For every query the lexicographic minimum over the valid faces of (d2, face index):
+ *   out_sqdist [n_queries] fp64, out_face [n_queries] int32, out_closest [n_queries,3] fp64 (may be
+ *   NULL): the closest point of that face.  The point is the best of four fp64 candidates, taken in
+ *   this order, a later one only when strictly closer: the closest points of the segments (a, b),
+ *   (a, c), (b, c) - p0 when t = (q - p0).(p1 - p0) <= 0, p1 when t >= l = |p1 - p0|^2, else
+ *   p0 + (t / l)(p1 - p0) - and the foot of the perpendicular (a + (h / nn) u) + (g / nn) v when it
+ *   lies inside (nn = |u x v|^2 > 0, h = ((q - a) x v).n >= 0, g = (u x (q - a)).n >= 0, h + g <= nn).
+ *   d2 = (dx dx + dy dy) + dz dz.  Nothing is divided by zero: a face of zero area is the union of
+ *   its edges (a segment; a point when the corners are equal).  A query at a vertex gives exactly 0.
+ *   A face with an index outside [0, n_verts) or a corner that is not finite is skipped (no index is
+ *   used as an address before it is tested); a query that is not finite gets NaN, -1, NaN; with no
+ *   valid face every finite query gets +inf, -1, NaN.
+ * out_counts[5] (device ints): skipped faces, queries that are not finite, status (|1 a corner that
+ * is not finite, |2 a face index outside the vertices, |4 a query that is not finite), and the
+ * number of evaluated (query, face) pairs as two 32-bit halves, low first.
+ * The search is a uniform grid over the faces (each binned once, by the centre of its box; at most
+ * 64^3 cells, about two faces per cell) walked ring by ring under a bound that skips a face only
+ * when its d2 is provably larger: the result equals the scan over all faces.  The call only
+ * enqueues: it returns 1 whatever the status word will say.
+ * scratch, 8-byte aligned: zs_mesh_distance_scratch_bytes(n_faces, n_queries) bytes (a multiple of
+ * 256; 0 for sizes outside the limits n_faces <= 2^24, n_queries <= 2^28).  n_queries = 0 returns
+ * 1 and touches nothing; n_faces = 0 is an empty mesh.
+ *
+ * zs_mesh_distance_stats: out[4] fp64 = the largest d, the mean d, the rms d and the number n of
+ * entries of sqdist [n] that are finite (the others are left out), d = sqrt(d2); *out_index = the
+ * lowest index with the largest d (-1 and NaNs when n is 0).  One workgroup of 256 threads: thread
+ * t adds its elements i = t, t + 256, ... in ascending i, thread 0 the 256 partial sums in
+ * ascending t: a fixed sequence of fp64 additions.  n = 0 returns 1 and touches nothing.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_distance_scratch_bytes(int n_faces, int n_queries);
+int zs_mesh_distance(const float *vertices, const int *faces, int n_faces, int n_verts, const float *queries, int n_queries,
+                     double *out_sqdist, int *out_face, double *out_closest, int *out_counts, void *scratch, void *stream);
+int zs_mesh_distance_stats(const double *sqdist, int n, double *out, int *out_index, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
  * itself is Implicit.field_gradient's, between the two calls).
  *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G

@@ -53,6 +53,8 @@ EXTRA = {
     "mesh_smooth.hip": ["-ffp-contract=off"],
     # the fp64 cluster means, quadrics and Cramer solve equal, operation for operation, to the numpy restatement in utils/eval_3D.py (simplify_mesh_host)
     "mesh_simplify.hip": ["-ffp-contract=off"],
+    # the fp64 closest points and squared distances equal, operation for operation, to the numpy restatement in utils/eval_3D.py (closest_point_on_mesh_host)
+    "mesh_distance.hip": ["-ffp-contract=off"],
 }
 
 

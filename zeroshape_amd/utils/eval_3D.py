@@ -529,13 +529,14 @@ def _surface_clouds(opt, level_vox, seed=0):
     meshes, clouds = [], []
     range_min, range_max = opt.eval.range
     cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
+    deviation_cell = _deviation_option(opt, smoothing, simplifying)
     for i in range(level_vox.shape[0]):
         if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
         else:                              # eval.min_component_area / eval.drop_cavities, eval.smooth_*, eval.simplify_cells:
             tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)          # sample the mesh that is delivered
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i)
         meshes.append(mesh)
         clouds.append(pts)
@@ -607,16 +608,31 @@ def _simplify_options(opt):
     return cell, (float(opt.eval.range[0]) - 0.5 * edge,) * 3, position
 
 
-def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None):
+def _deviation_option(opt, smoothing, simplifying):
+    """The marching-cubes cell edge when ``--eval.mesh_deviation=true`` is set (opt-in, command line only: no yaml file carries
+    it), else None: the pipelines then make today's calls.  The record compares the delivered mesh with the mesh it was made
+    from, so without ``eval.smooth_iterations`` and ``eval.simplify_cells`` there is nothing to compare: an error, not ignored."""
+    if not bool(opt.eval.get("mesh_deviation", False)):
+        return None
+    if smoothing is None and simplifying is None:
+        raise ValueError("eval.mesh_deviation needs eval.smooth_iterations or eval.simplify_cells")
+    return _mc_cell_edge(opt)
+
+
+def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None, deviation_cell=None):
     """The opt-in steps between marching cubes and sampling, in their order: filter_components, then smooth_mesh, then
     simplify_mesh - last, so that the colours, the sampled points and with them the metrics describe the mesh that is
-    delivered."""
+    delivered.  With ``deviation_cell`` (_deviation_option) the delivered mesh gets ``deviation``: mesh_deviation against the
+    mesh as it stood after filter_components - dropping floaters is intended and is not deviation."""
     if cleaning is not None:
         mesh = filter_components(mesh, *cleaning)
+    reference = mesh
     if smoothing is not None:
         mesh = smooth_mesh(mesh, *smoothing)
     if simplifying is not None:
         mesh = simplify_mesh(mesh, *simplifying)
+    if deviation_cell is not None:
+        mesh.deviation = mesh_deviation(mesh, reference, cell_edge=deviation_cell)
     return mesh
 
 
@@ -812,6 +828,11 @@ class SimpleMesh(object):
         if self._adjacency is None:
             self._adjacency = mesh_adjacency(self)
         return self._adjacency
+
+    def distance_to(self, points, closest=False):
+        """mesh_distance(self, points, closest): the exact distance from ``points`` [M,3] to this surface - the nearest face and
+        the squared distance to it (a MeshDistance; CUDA tensors for a GPU mesh, whose points must be a CUDA tensor)."""
+        return mesh_distance(self, points, closest=closest)
 
     @property
     def vertex_neighbors(self):
@@ -1675,11 +1696,300 @@ def simplify_mesh(mesh, cell, origin=None, position="quadric"):
                        dict(kept=kept, clusters=clusters, degenerate=degenerate, duplicate=duplicate, fallbacks=fallbacks))
 
 
+# ---- exact point-to-mesh distance (csrc/mesh_distance.hip) ----
+
+MESH_DISTANCE_STATUS_VERTEX, MESH_DISTANCE_STATUS_INDEX, MESH_DISTANCE_STATUS_QUERY = 1, 2, 4   # zs_mesh_distance: status bits
+
+
+class MeshDistance(collections.namedtuple("MeshDistance", "sqdist face closest counts")):
+    """What mesh_distance returns: ``sqdist`` [M] float64 (the squared distance of every point to the mesh), ``face`` [M] (the
+    face that attains it, the lowest index among equals; -1 where there is none), ``closest`` [M,3] float64 (the closest point
+    of that face; None unless asked for) and ``counts`` [5] int32 - the faces that were skipped, the points that are not finite,
+    the status word and the number of (point, face) pairs that were evaluated as two 32-bit halves.  CUDA tensors for a GPU
+    mesh (int32 faces, nothing has been read back), numpy arrays for a host mesh (int64 faces)."""
+    __slots__ = ()
+
+    def check(self):
+        """Reads ``counts`` (for a GPU mesh the one device-to-host copy, 20 bytes) -> dict(skipped_faces, nonfinite_queries,
+        status, pairs).  ZeroShapeHipError when the status word says that a face index lay outside the vertices - a weld
+        never makes one."""
+        words = [int(v) for v in (self.counts.tolist() if self.counts is not None else [0] * 5)]
+        return _distance_counts(words)
+
+
+def _distance_counts(words):
+    skipped, bad, status, lo, hi = words
+    if status & MESH_DISTANCE_STATUS_INDEX:
+        from .. import _lib
+        raise _lib.ZeroShapeHipError("zs_mesh_distance: status %d (a face index outside the vertices)" % status)
+    return dict(skipped_faces=skipped, nonfinite_queries=bad, status=status, pairs=(lo & 0xffffffff) | ((hi & 0xffffffff) << 32))
+
+
+def _valid_faces(vertices, faces):
+    """-> (valid [F] bool, status): a face is valid when its three indices lie inside the vertices and its corners are finite."""
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    inside = np.all((f >= 0) & (f < len(v32)), axis=1)
+    finite = np.zeros(len(f), bool)
+    finite[inside] = np.all(np.isfinite(v32[f[inside]]), axis=(1, 2))
+    status = (MESH_DISTANCE_STATUS_INDEX if not inside.all() else 0) | (MESH_DISTANCE_STATUS_VERTEX if (inside & ~finite).any() else 0)
+    return inside & finite, status
+
+
+def _sub3(x, y):
+    return x[0] - y[0], x[1] - y[1], x[2] - y[2]
+
+
+def _dot3(x, y):
+    return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]
+
+
+def _cross3(x, y):
+    return x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]
+
+
+def _closest_on_faces(q, a, b, c, with_point=False):
+    """The points q against the faces (a, b, c), each a triple of float64 component arrays that broadcast against each other
+    (q [Q,1] and corners [1,F]: every pair; or all [Q]: row by row) -> d2, or (d2, the closest point as a triple): the formula of
+    closest_point_on_mesh_host, operation for operation."""
+    def segment(p0, p1, w):
+        e = _sub3(p1, p0)
+        t, l = _dot3(w, e), _dot3(e, e)
+        inner = (t > 0.0) & (t < l)
+        end = (t > 0.0) & ~inner
+        s = t / l                                                    # (used only where 0 < t < l)
+        point = tuple(np.where(inner, p0[k] + s * e[k], np.where(end, p1[k], p0[k])) for k in range(3))
+        d = _sub3(q, point)
+        return _dot3(d, d), point
+
+    w = _sub3(q, a)
+    best, point = segment(a, b, w)
+    for p0, p1, w0 in ((a, c, w), (b, c, _sub3(q, b))):
+        d2, other = segment(p0, p1, w0)
+        closer = d2 < best
+        best = np.where(closer, d2, best)
+        if with_point:
+            point = tuple(np.where(closer, other[k], point[k]) for k in range(3))
+    u, v = _sub3(b, a), _sub3(c, a)
+    n = _cross3(u, v)
+    nn = _dot3(n, n)
+    g, h = _dot3(_cross3(u, w), n), _dot3(_cross3(w, v), n)
+    inside = (nn > 0.0) & (h >= 0.0) & (g >= 0.0) & (h + g <= nn)
+    beta, gamma = h / nn, g / nn                                     # (used only where nn > 0)
+    other = tuple((a[k] + beta * u[k]) + gamma * v[k] for k in range(3))
+    d = _sub3(q, other)
+    d2 = _dot3(d, d)
+    closer = inside & (d2 < best)
+    best = np.where(closer, d2, best)
+    if with_point:
+        return best, tuple(np.where(closer, other[k], point[k]) for k in range(3))
+    return best
+
+
+def closest_point_on_mesh_host(points, vertices, faces, block=1 << 18):
+    """The definition of mesh_distance and the checker of zs_mesh_distance, in numpy: for every point q of ``points`` [M,3]
+    float32 the lexicographic minimum over the valid faces f of (d2(q, f), f) on the indexed mesh ``vertices`` [V,3] float32,
+    ``faces`` [F,3] - a brute force over all faces, ``block`` (point, face) pairs at a time.  A face is valid when its three
+    indices lie inside the vertices and its corners are finite; the others are skipped and counted.  Everything is elementwise
+    float64 in the order written, from the float32 corners a, b, c and the float32 point:
+
+      segment(p0, p1)    e = p1 - p0, w = q - p0, t = (wx ex + wy ey) + wz ez, l = (ex ex + ey ey) + ez ez;  t <= 0: p0;  else
+                         t >= l: p1 (the vertex's own bits);  else p0 + (t / l) e.  The denominator l is used only where
+                         0 < t < l: an edge of length zero has t = 0 and gives p0.
+      interior(a, b, c)  u = b - a, v = c - a, w = q - a, n = u x v, nn = (nx nx + ny ny) + nz nz, g = (u x w) . n,
+                         h = (w x v) . n (dots added left to right, cross products as a_y b_z - a_z b_y and its rotations);
+                         inside when nn > 0, h >= 0, g >= 0 and h + g <= nn; then the point is (a + (h / nn) u) + (g / nn) v.
+                         The denominator nn is used only where nn > 0: a face of zero area has no interior candidate.
+      d2                 d = q - point, d2 = (dx dx + dy dy) + dz dz.
+      the face           segment(a, b), segment(a, c), segment(b, c), interior, in this order; a later candidate replaces an
+                         earlier one only with a strictly smaller d2.
+
+    The closest point of a triangle is the foot of the perpendicular where that falls inside and a point of the boundary
+    otherwise, so the smallest candidate is the exact distance in each of the seven Voronoi regions.  A face with a
+    zero-length edge is a segment, a face with three equal corners a point: no NaN arises from finite inputs.  A point at a
+    vertex is at d2 = 0 exactly from every face around it: the lowest face index wins, as for a point on a shared edge or a
+    duplicated face.  A point that is not finite gets (NaN, -1, NaN); without a valid face every other point gets
+    (+inf, -1, NaN).  -> (sqdist [M] float64, face [M] int64, closest [M,3] float64, skipped_faces int)."""
+    p32 = np.asarray(points, np.float32).reshape(-1, 3)
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    valid, _ = _valid_faces(v32, f)
+    index = np.flatnonzero(valid)
+    corners = v32[f[index]].astype(np.float64)                       # [Fv,3,3]
+    M = len(p32)
+    sqdist, face, closest = np.full(M, np.inf), np.full(M, -1, np.int64), np.full((M, 3), np.nan)
+    finite = np.all(np.isfinite(p32), axis=1)
+    sqdist[~finite] = np.nan
+    rows = np.flatnonzero(finite)
+    chunk = 1024
+    step = max(1, int(block) // chunk)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        for r0 in range(0, len(rows), chunk):
+            sel = rows[r0:r0 + chunk]
+            q64 = p32[sel].astype(np.float64)
+            q = tuple(q64[:, k, None] for k in range(3))
+            best, best_f = np.full(len(sel), np.inf), np.full(len(sel), -1, np.int64)
+            lane = np.arange(len(sel))
+            for f0 in range(0, len(index), step):
+                tri = corners[f0:f0 + step]
+                a, b, c = (tuple(tri[None, :, i, k] for k in range(3)) for i in range(3))
+                d2 = _closest_on_faces(q, a, b, c)
+                j = np.argmin(d2, axis=1)                            # the first of equal minima: the lowest face index
+                d2 = d2[lane, j]
+                closer = d2 < best                                   # strictly: an earlier block holds the lower indices
+                best = np.where(closer, d2, best)
+                best_f = np.where(closer, index[f0 + j], best_f)
+            best_p = np.full((len(sel), 3), np.nan)
+            if len(index):                                           # the closest point: the same formula on the winning face alone
+                tri = v32[f[best_f]].astype(np.float64)
+                a, b, c = (tuple(tri[:, i, k] for k in range(3)) for i in range(3))
+                _, point = _closest_on_faces(tuple(q64[:, k] for k in range(3)), a, b, c, with_point=True)
+                best_p = np.stack(point, axis=1)
+            sqdist[sel], face[sel], closest[sel] = best, best_f, best_p
+    return sqdist, face, closest, int(len(f) - len(index))
+
+
+def mesh_distance_stats_host(sqdist):
+    """The checker of zs_mesh_distance_stats: over d = sqrt(d2) of the entries of ``sqdist`` that are finite (the others are
+    left out) -> (float64 [4]: the largest d, the mean d, the rms d = sqrt(sum d2 / n), n; the lowest index with the largest d).
+    The sums are the kernel's sequence of float64 additions: element i goes to thread i mod 256, a thread adds its elements in
+    ascending i, then the 256 partial sums are added in ascending thread - np.add.accumulate, which adds in index order, down
+    the columns of a zero-padded [-1, 256] view and then along the row of partial sums.  Without a finite entry: NaN, NaN, NaN,
+    0 and -1."""
+    d2 = np.asarray(sqdist, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ok = (d2 >= 0.0) & (d2 < np.inf)
+        n = int(ok.sum())
+        if n == 0:
+            return np.array([np.nan, np.nan, np.nan, 0.0]), -1
+        d = np.sqrt(np.where(ok, d2, 0.0))
+
+        def total(x):
+            padded = np.concatenate([np.where(ok, x, 0.0), np.zeros((-len(x)) % 256)]).reshape(-1, 256)
+            return np.add.accumulate(np.add.accumulate(padded, axis=0)[-1])[-1]
+
+        at = int(np.argmax(np.where(ok, d, -1.0)))                   # the first of equal maxima
+        return np.array([d[at], total(d) / float(n), np.sqrt(total(d2) / float(n)), float(n)]), at
+
+
+@torch.no_grad()
+def mesh_distance(mesh, points, closest=False):
+    """The exact distance from ``points`` [M,3] to the surface of ``mesh`` (a SimpleMesh): for every point the nearest face,
+    the squared distance to it and, with ``closest``, the nearest point of it -> a MeshDistance.  The semantics are
+    closest_point_on_mesh_host's: float64 arithmetic on the float32 vertices and points, the lowest face index among equal
+    distances, a face of zero area a segment or a point, faces with a corner that is not finite skipped, (NaN, -1) for a point
+    that is not finite and (+inf, -1) against an empty mesh.
+    A GPU mesh is searched on the device (zs_mesh_distance: a uniform grid over the faces, walked ring by ring under a bound
+    that only skips what is provably farther - the brute force's bits) on the weld it carries or, if it has none yet, on one
+    weld_mesh call whose result it then keeps; ``points`` must then be a CUDA float32 tensor (ValueError otherwise), the results
+    are CUDA tensors and nothing is read back: ``MeshDistance.check()`` reads the counts and raises ZeroShapeHipError for a
+    status word that reports a face index outside the vertices.  A host mesh goes through the numpy checker."""
+    if getattr(mesh, "device_triangles", None) is None:
+        if isinstance(points, torch.Tensor):
+            points = points.detach().cpu().numpy()
+        p32 = np.asarray(points, np.float32).reshape(-1, 3)
+        vertices, faces = mesh.vertices, mesh.faces
+        sq, face, point, skipped = closest_point_on_mesh_host(p32, vertices, faces)
+        valid, status = _valid_faces(vertices, faces)
+        bad = int((~np.all(np.isfinite(p32), axis=1)).sum())
+        pairs = int(valid.sum()) * (len(p32) - bad)
+        counts = np.array([skipped, bad, status | (MESH_DISTANCE_STATUS_QUERY if bad else 0), pairs & 0xffffffff, pairs >> 32],
+                          np.int64).astype(np.uint32).view(np.int32)
+        return MeshDistance(sq, face, point if closest else None, counts)
+    if not (isinstance(points, torch.Tensor) and points.is_cuda):
+        raise ValueError("mesh_distance: a GPU mesh needs its points as a CUDA tensor")
+    from .. import _lib
+    lib = _lib.load()
+    if mesh._device_weld is None:
+        mesh._device_weld = weld_mesh(mesh.device_triangles, normals=True)
+    vertices, faces = mesh._device_weld[0], mesh._device_weld[1]
+    dev = vertices.device
+    pts = points.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    n, n_verts, m = faces.shape[0], vertices.shape[0], pts.shape[0]
+    sq = torch.empty(m, dtype=torch.float64, device=dev)
+    face = torch.empty(m, dtype=torch.int32, device=dev)
+    point = torch.empty(m, 3, dtype=torch.float64, device=dev) if closest else None
+    counts = torch.zeros(5, dtype=torch.int32, device=dev)
+    if m == 0:
+        return MeshDistance(sq, face, point, counts)
+    nbytes = lib.zs_mesh_distance_scratch_bytes(n, m)
+    if nbytes == 0:
+        raise _lib.ZeroShapeHipError("mesh_distance: %d faces and %d points exceed the kernels' limits" % (n, m))
+    scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+    with _lib.on(dev):
+        _lib.check(lib.zs_mesh_distance(_lib.ptr(vertices), _lib.ptr(faces), n, n_verts, _lib.ptr(pts), m, _lib.ptr(sq),
+                                        _lib.ptr(face), _lib.ptr(point), _lib.ptr(counts), _lib.ptr(scratch),
+                                        _lib.current_stream_ptr(dev)), "zs_mesh_distance")
+    return MeshDistance(sq, face, point, counts)
+
+
+MeshDeviation = collections.namedtuple(
+    "MeshDeviation", "forward_max forward_mean forward_rms forward_index forward_vertices "
+                     "backward_max backward_mean backward_rms backward_index backward_vertices cell_edge")
+MeshDeviation.__doc__ = """What mesh_deviation measured between a mesh and the reference it was made from, in mesh units.  ``forward``:
+the distances of the vertices of the mesh to the surface of the reference - the largest, the mean, the root mean square, the
+index of the vertex (a row of ``mesh.vertices``) where the largest is attained (the lowest among equals) and the number of
+vertices.  ``backward``: the same for the vertices of the reference against the surface of the mesh (the index is a row of
+``reference.vertices``).  ``cell_edge``: None, or the edge of a marching-cubes cell in mesh units when the pipelines made the
+record - mesh_report then also gives the distances in cells.  The record is VERTEX-SAMPLED: each maximum is a lower bound on
+the one-sided Hausdorff distance of the two surfaces (the largest distance may be attained inside a face), not the continuous
+Hausdorff distance; the distances themselves are exact."""
+
+
+def _deviation_record(forward, forward_at, backward, backward_at, cell_edge):
+    return MeshDeviation(float(forward[0]), float(forward[1]), float(forward[2]), int(forward_at), int(forward[3]),
+                         float(backward[0]), float(backward[1]), float(backward[2]), int(backward_at), int(backward[3]),
+                         None if cell_edge is None else float(cell_edge))
+
+
+@torch.no_grad()
+def mesh_deviation(mesh, reference, cell_edge=None):
+    """How far the surface of ``mesh`` lies from the surface of ``reference`` (two SimpleMesh, both on the GPU or both on the
+    host; typically a smoothed or simplified mesh and the mesh it was made from) -> a MeshDeviation: max, mean and rms of the
+    exact distances of the vertices of ``mesh`` to the surface of ``reference`` (forward) and of the vertices of ``reference``
+    to the surface of ``mesh`` (backward), with the vertex at each maximum.  Vertex-sampled: a bound from the vertices, not the
+    continuous Hausdorff distance (see MeshDeviation).  On the GPU: two mesh_distance calls and two zs_mesh_distance_stats
+    calls on the welds the meshes carry (made and kept where missing), then ONE small read-back - the two records and the
+    two status words; on the host closest_point_on_mesh_host and mesh_distance_stats_host, the kernels' checkers, which give
+    the same numbers bit for bit.  A side without vertices, or against an empty mesh, gives NaN, NaN, NaN, -1 and 0."""
+    on_device = getattr(mesh, "device_triangles", None) is not None
+    if on_device != (getattr(reference, "device_triangles", None) is not None):
+        raise ValueError("mesh_deviation: both meshes must live on the GPU or both on the host")
+    if not on_device:
+        sides = []
+        for source, target in ((mesh, reference), (reference, mesh)):
+            done = mesh_distance(target, source.vertices)
+            done.check()
+            sides.extend(mesh_distance_stats_host(done.sqdist))
+        return _deviation_record(*sides, cell_edge=cell_edge)
+    from .. import _lib
+    lib = _lib.load()
+    for m in (mesh, reference):
+        if m._device_weld is None:
+            m._device_weld = weld_mesh(m.device_triangles, normals=True)
+    dev = mesh.device_triangles.device
+    tail = []
+    for source, target in ((mesh, reference), (reference, mesh)):
+        done = mesh_distance(target, source._device_weld[0])
+        out = torch.tensor([float("nan")] * 3 + [0.0], dtype=torch.float64, device=dev)
+        at = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_distance_stats(_lib.ptr(done.sqdist), done.sqdist.shape[0], _lib.ptr(out), _lib.ptr(at),
+                                                  _lib.current_stream_ptr(dev)), "zs_mesh_distance_stats")
+        tail += [out, at.to(torch.float64), done.counts.to(torch.float64)]
+    f, f_at, f_counts, b, b_at, b_counts = (t.tolist() for t in torch.cat(tail).split([4, 1, 5, 4, 1, 5]))      # the one D2H
+    for words in (f_counts, b_counts):
+        _distance_counts([int(v) for v in words])
+    return _deviation_record(f, f_at[0], b, b_at[0], cell_edge)
+
+
 def mesh_report(mesh):
     """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
-    per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``, and a mesh that
+    per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``, a mesh that
     simplify_mesh made its ``simplification`` (the cell, the origin, the placement and the counts: with ``is_watertight`` and
-    the component table beside it, what the clustering did to the surface)."""
+    the component table beside it, what the clustering did to the surface), and a mesh that carries a ``deviation`` (a
+    MeshDeviation, set by the pipelines under ``eval.mesh_deviation``) that record - with the six distances also in
+    marching-cubes cells (``*_cells``) when the record knows the cell edge."""
     comps = mesh.components
     report = dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
                   area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
@@ -1690,6 +2000,13 @@ def mesh_report(mesh):
         record = mesh.simplification._asdict()
         record["origin"] = list(record["origin"])
         report["simplification"] = record
+    if getattr(mesh, "deviation", None) is not None:
+        record = mesh.deviation._asdict()
+        if record["cell_edge"] is not None:
+            for side in ("forward", "backward"):
+                for what in ("max", "mean", "rms"):
+                    record["%s_%s_cells" % (side, what)] = record["%s_%s" % (side, what)] / record["cell_edge"]
+        report["deviation"] = record
     return report
 
 
@@ -2037,7 +2354,8 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
     With ``opt.eval.min_component_area`` / ``opt.eval.drop_cavities`` set (opt-in) every mesh goes through
     filter_components first, with ``opt.eval.smooth_iterations`` set (opt-in, _smooth_options) through smooth_mesh after
     that, with ``opt.eval.simplify_cells`` set (opt-in, _simplify_options) through simplify_mesh last, and the points are
-    sampled on what comes out: the metrics describe the mesh that is delivered."""
+    sampled on what comes out: the metrics describe the mesh that is delivered.  With ``opt.eval.mesh_deviation`` (opt-in,
+    _deviation_option) that mesh carries ``deviation``: how far the smoothing and the simplification moved the surface."""
     device = getattr(opt, "device", "cuda")
     meshes, clouds = [], []
     for i, g in enumerate(level_grids):
@@ -2046,13 +2364,14 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
         assert vol.shape[0] == vol.shape[1] == vol.shape[2]
         range_min, range_max = opt.eval.range
         cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
+        deviation_cell = _deviation_option(opt, smoothing, simplifying)
         if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(vol, isoval, range_min, range_max,
                                         opt.eval.num_points if to_pointcloud else 0, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
         else:                   # marching cubes, filter_components, smooth_mesh, simplify_mesh, then sampling with the same seed
             tris, _ = extract_surface(vol, isoval, range_min, range_max)
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i) if to_pointcloud else None
         meshes.append(mesh)
         if to_pointcloud:
