@@ -689,7 +689,9 @@ __global__ __launch_bounds__(PS_THREADS) void pose_finish_kernel(
     const int tid = threadIdx.x;
     if (tid == 0) s_alive = 0;
     __syncthreads();
-    float cd = INFINITY, acc = 0.f, comp = 0.f, f[6];
+    // (f zeroed: a batch whose rotations are all dead writes its lowest index with cd = +inf into a record that still
+    // holds +inf - reachable when best[12] is set before the first batch - and the record must not store floats without a value)
+    float cd = INFINITY, acc = 0.f, comp = 0.f, f[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int gidx = 0x7fffffff;
     const bool alive = tid < count && !(dead && dead[tid]);
     if (alive) atomicAdd(&s_alive, 1);
