@@ -53,6 +53,13 @@ filter: dropping floaters is intended) and of every vertex of that surface to th
 the report gains a `deviation` entry: max, mean, rms and the vertex at the maximum for both directions, in mesh units and in
 marching-cubes cells.  It is sampled at the vertices: a lower bound on the Hausdorff distance, not the continuous one.
 
+--eval.mesh_iou=true (opt-in, with --eval.smooth_iterations or --eval.simplify_cells; an error without either) measures how
+much volume those steps added or removed (eval_3D.mesh_volume_iou, exact point-in-mesh tests on the GPU): the occupancy of the
+delivered mesh and of the surface marching cubes extracted (after the component filter) at the points of the evaluation
+grid's own lattice.  With --eval.mesh_report=true the report gains a `volume_iou` entry: the lattice points inside each mesh,
+inside both and inside either, their ratio, and how many points were ambiguous (on the surface, or under a hole of an open
+mesh).  It is sampled on the lattice: counts of points, not integrals over the solids.
+
 --eval.vertex_colors=true (opt-in, shape task) colours the mesh from the input photo on the GPU (eval_3D.vertex_colors): a
 vertex the input camera saw takes the photo's bilinear texel, every other vertex the colour of the nearest seen one.
 <name>_mesh.obj then has `v x y z r g b` lines (the vertex-colour extension MeshLab, Blender and Open3D read), with --viz

@@ -15,7 +15,9 @@ With --eval.dump_results the per-sample dumps take the demo's opt-in switches: -
 the input photo on the GPU (eval_3D.vertex_colors), and --eval.mesh_report=true writes <idx>_mesh_report.json, with the
 seen area fraction of a coloured mesh.  --eval.mesh_deviation=true (with --eval.smooth_iterations or --eval.simplify_cells; an
 error without either) records on every predicted mesh how far those steps moved the surface (eval_3D.mesh_deviation: vertex to
-surface distances both ways, on the GPU); the report then carries a `deviation` entry.
+surface distances both ways, on the GPU); the report then carries a `deviation` entry.  --eval.mesh_iou=true (under the same
+condition) records how much volume they added or removed (eval_3D.mesh_volume_iou: the occupancy of both meshes on the
+evaluation grid's lattice, on the GPU); the report then carries a `volume_iou` entry.
 
 ZS_VIRTUAL_RANKS=N (with ZS_DEVICE_OVERRIDE=0 ZS_DIST_BACKEND=gloo) rehearses the N-rank path on one GPU.
 """

@@ -595,6 +595,52 @@ int zs_mesh_distance(const float *vertices, const int *faces, int n_faces, int n
 int zs_mesh_distance_stats(const double *sqdist, int n, double *out, int *out_index, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * On which side of a triangle mesh a point lies (csrc/mesh_inside.hip; the semantics are
+ * eval_3D.mesh_winding_host's, exactly).  vertices [n_verts,3] fp32 and faces [n_faces,3] int32 are
+ * the weld's (zs_mesh_weld), queries [n_queries,3] fp32.
+ * For every query the signed crossing numbers of the +z ray (out_up [n_queries] int32) and of the
+ * -z ray (out_down [n_queries] int32, may be NULL) over the valid faces.  fp64 as written, from the
+ * fp32 corners a, b, c and the fp32 query q:
+ *   box     a face is a candidate only if min(ax, bx, cx) <= qx <= max(ax, bx, cx), and so in y.
+ *   side    of each directed edge u -> v (a -> b, b -> c, c -> a): (lo, hi) = its endpoints ordered
+ *           lexicographically by their (x, y, z) values; s = (hx - lx)(qy - ly) - (hy - ly)(qx - lx);
+ *           where s == 0: -sign(hy - ly) if hy != ly, else sign(hx - lx); negated when the face
+ *           walks the edge hi -> lo (a symbolic shift of q by (eps, eps^2): no ray meets an edge).
+ *   facing  up when the three sides are > 0, down when they are < 0, else the face does not count.
+ *   height  A = a - q, B = b - q, C = c - q,
+ *           det = (Ax (By Cz - Bz Cy) + Ay (Bz Cx - Bx Cz)) + Az (Bx Cy - By Cx); 0 counts for neither.
+ *   up = #(up-facing, det > 0) - #(down-facing, det < 0), down = #(down-facing, det > 0) -
+ *   #(up-facing, det < 0).  For a closed mesh wound like marching cubes' both are the winding number.
+ *   A face with an index outside [0, n_verts) or a corner that is not finite is skipped (no index is
+ *   used as an address before it is tested); a query that is not finite gets 0, 0.
+ * out_counts[5] (device ints): as zs_mesh_distance's - skipped faces, queries that are not finite,
+ * status (|1 a corner that is not finite, |2 a face index outside the vertices, |4 a query that is
+ * not finite), and the number of (query, face) pairs read, as two 32-bit halves, low first.
+ * The search is a uniform grid of columns over x, y (each face binned once, by the centre of its
+ * box; at most 1024^2 columns, about two faces per column); a query visits the columns that can
+ * hold a face whose box contains it, found with integer reaches through one monotone index
+ * function: the counts equal the scan over all faces.  The call only enqueues.
+ * scratch, 8-byte aligned: zs_mesh_winding_scratch_bytes(n_faces, n_queries) bytes (a multiple of
+ * 256; 0 for sizes outside the limits n_faces <= 2^24, n_queries <= 2^28).  n_queries = 0 returns 1
+ * and touches nothing; n_faces = 0 is an empty mesh.
+ *
+ * zs_mesh_winding_grid: the same for the G^3 lattice points (fmaf(ix, scale, offset),
+ * fmaf(iy, scale, offset), fmaf(iz, scale, offset)) - marching cubes' own vertex formula - made in
+ * the kernel: out_inside [G^3] int8, x slowest, = (up != 0).  out_counts[6]: the five words above and
+ * the number of ambiguous points (up != down).  scratch: zs_mesh_winding_scratch_bytes(n_faces, G^3);
+ * G <= 645 (G^3 <= 2^28); G = 0 returns 1 and touches nothing.
+ *
+ * zs_occupancy_counts: out[4] int64 (device, 8-byte aligned) = |A|, |B|, |A and B|, |A or B| of two
+ * int8 arrays of n elements (non-zero = inside): integer sums, exact.  n = 0 writes four zeros.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_winding_scratch_bytes(int n_faces, int n_queries);
+int zs_mesh_winding(const float *vertices, const int *faces, int n_faces, int n_verts, const float *queries, int n_queries,
+                    int *out_up, int *out_down, int *out_counts, void *scratch, void *stream);
+int zs_mesh_winding_grid(const float *vertices, const int *faces, int n_faces, int n_verts, int G, float scale, float offset,
+                         signed char *out_inside, int *out_counts, void *scratch, void *stream);
+int zs_occupancy_counts(const signed char *a, const signed char *b, long long n, long long *out, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
  * itself is Implicit.field_gradient's, between the two calls).
  *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G

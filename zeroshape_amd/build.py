@@ -55,6 +55,8 @@ EXTRA = {
     "mesh_simplify.hip": ["-ffp-contract=off"],
     # the fp64 closest points and squared distances equal, operation for operation, to the numpy restatement in utils/eval_3D.py (closest_point_on_mesh_host)
     "mesh_distance.hip": ["-ffp-contract=off"],
+    # the fp64 edge sides and heights equal, operation for operation, to the numpy restatement in utils/eval_3D.py (mesh_winding_host)
+    "mesh_inside.hip": ["-ffp-contract=off"],
 }
 
 

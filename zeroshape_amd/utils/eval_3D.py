@@ -530,13 +530,14 @@ def _surface_clouds(opt, level_vox, seed=0):
     range_min, range_max = opt.eval.range
     cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
     deviation_cell = _deviation_option(opt, smoothing, simplifying)
+    iou_lattice = _iou_option(opt, smoothing, simplifying, G=level_vox.shape[1])
     for i in range(level_vox.shape[0]):
         if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
         else:                              # eval.min_component_area / eval.drop_cavities, eval.smooth_*, eval.simplify_cells:
             tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)          # sample the mesh that is delivered
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell, iou_lattice)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i)
         meshes.append(mesh)
         clouds.append(pts)
@@ -619,11 +620,28 @@ def _deviation_option(opt, smoothing, simplifying):
     return _mc_cell_edge(opt)
 
 
-def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None, deviation_cell=None):
+def _iou_option(opt, smoothing, simplifying, G=None):
+    """The marching-cubes lattice (G, scale, offset) of the evaluation grid when ``--eval.mesh_iou=true`` is set (opt-in, command
+    line only: no yaml file carries it), else None: the pipelines then make today's calls.  ``G`` samples per axis - the level
+    grid's own size where the caller has one, else ``eval.vox_res`` + 1 as get_dense_3D_grid makes it - at
+    scale = (range_max - range_min) / G as extract_surface computes it and offset = range_min.  The record compares the
+    delivered mesh with the mesh it was made from, so without ``eval.smooth_iterations`` and ``eval.simplify_cells`` there is
+    nothing to compare: an error, not ignored."""
+    if not bool(opt.eval.get("mesh_iou", False)):
+        return None
+    if smoothing is None and simplifying is None:
+        raise ValueError("eval.mesh_iou needs eval.smooth_iterations or eval.simplify_cells")
+    range_min, range_max = opt.eval.range
+    G = int(opt.eval.vox_res) + 1 if G is None else int(G)
+    return G, float(np.float32((range_max - range_min) / G)), float(range_min)
+
+
+def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None, deviation_cell=None, iou_lattice=None):
     """The opt-in steps between marching cubes and sampling, in their order: filter_components, then smooth_mesh, then
     simplify_mesh - last, so that the colours, the sampled points and with them the metrics describe the mesh that is
     delivered.  With ``deviation_cell`` (_deviation_option) the delivered mesh gets ``deviation``: mesh_deviation against the
-    mesh as it stood after filter_components - dropping floaters is intended and is not deviation."""
+    mesh as it stood after filter_components - dropping floaters is intended and is not deviation.  With ``iou_lattice``
+    (_iou_option) it gets ``volume_iou``: mesh_volume_iou against the same mesh on that lattice."""
     if cleaning is not None:
         mesh = filter_components(mesh, *cleaning)
     reference = mesh
@@ -633,6 +651,8 @@ def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None, deviation
         mesh = simplify_mesh(mesh, *simplifying)
     if deviation_cell is not None:
         mesh.deviation = mesh_deviation(mesh, reference, cell_edge=deviation_cell)
+    if iou_lattice is not None:
+        mesh.volume_iou = mesh_volume_iou(mesh, reference, *iou_lattice)
     return mesh
 
 
@@ -833,6 +853,16 @@ class SimpleMesh(object):
         """mesh_distance(self, points, closest): the exact distance from ``points`` [M,3] to this surface - the nearest face and
         the squared distance to it (a MeshDistance; CUDA tensors for a GPU mesh, whose points must be a CUDA tensor)."""
         return mesh_distance(self, points, closest=closest)
+
+    def contains(self, points):
+        """trimesh's name: mesh_contains(self, points) - whether each of ``points`` [M,3] lies inside this mesh ([M] bool; a
+        CUDA tensor for a GPU mesh, whose points must be a CUDA tensor)."""
+        return mesh_contains(self, points)
+
+    def signed_distance_to(self, points, closest=False):
+        """mesh_signed_distance(self, points, closest): the exact distance from ``points`` [M,3] to this surface, negative
+        inside ([M] float64; with ``closest`` also the nearest point of the surface)."""
+        return mesh_signed_distance(self, points, closest=closest)
 
     @property
     def vertex_neighbors(self):
@@ -1983,13 +2013,276 @@ def mesh_deviation(mesh, reference, cell_edge=None):
     return _deviation_record(f, f_at[0], b, b_at[0], cell_edge)
 
 
+# ---- on which side of a mesh a point lies (csrc/mesh_inside.hip) ----
+
+
+class MeshWinding(collections.namedtuple("MeshWinding", "up down counts")):
+    """What mesh_winding returns: ``up`` [M] int32 and ``down`` [M] int32, the signed crossing numbers of the +z and the -z ray
+    from every point (for a closed mesh wound like marching cubes' both are the winding number: 1 in a solid, 0 outside and in
+    a cavity, 2 where two solids overlap, -1 in a solid wound the other way; ``up != down`` marks a point as AMBIGUOUS - the
+    mesh is open along the point's column, or the point lies on the surface), and ``counts`` [5] int32 as MeshDistance's: the
+    faces that were skipped, the points that are not finite, the status word and the number of (point, face) pairs that were
+    read as two 32-bit halves.  CUDA tensors for a GPU mesh (nothing has been read back), numpy arrays for a host mesh."""
+    __slots__ = ()
+
+    def check(self):
+        """Reads ``counts`` (for a GPU mesh the one device-to-host copy, 20 bytes) -> dict(skipped_faces, nonfinite_queries,
+        status, pairs).  ZeroShapeHipError when the status word says that a face index lay outside the vertices - a weld
+        never makes one."""
+        return _winding_counts([int(v) for v in self.counts.tolist()])
+
+
+def _winding_counts(words, who="zs_mesh_winding"):
+    skipped, bad, status, lo, hi = words[:5]
+    if status & MESH_DISTANCE_STATUS_INDEX:
+        from .. import _lib
+        raise _lib.ZeroShapeHipError("%s: status %d (a face index outside the vertices)" % (who, status))
+    return dict(skipped_faces=skipped, nonfinite_queries=bad, status=status, pairs=(lo & 0xffffffff) | ((hi & 0xffffffff) << 32))
+
+
+def _edge_side_host(u, v, qx, qy):
+    """The sign (float64 -1, 0, 1) of the side of (qx, qy) against the directed edge u -> v (triples of float64 arrays), ties
+    broken by the symbolic shift: mesh_winding_host's step 2, operation for operation."""
+    forward = (u[0] < v[0]) | ((u[0] == v[0]) & ((u[1] < v[1]) | ((u[1] == v[1]) & (u[2] <= v[2]))))     # walks lo -> hi
+    lx, ly = np.where(forward, u[0], v[0]), np.where(forward, u[1], v[1])
+    hx, hy = np.where(forward, v[0], u[0]), np.where(forward, v[1], u[1])
+    ex, ey = hx - lx, hy - ly
+    s = ex * (qy - ly) - ey * (qx - lx)
+    s = np.sign(np.where(s == 0.0, np.where(ey != 0.0, -np.sign(ey), np.sign(ex)), s))
+    return np.where(forward, s, -s)
+
+
+def mesh_winding_host(points, vertices, faces, block=1 << 22):
+    """The definition of mesh_winding and the checker of zs_mesh_winding, in numpy: for every point q of ``points`` [M,3]
+    float32 the signed crossing numbers of the +z ray (up) and of the -z ray (down) over the valid faces of the indexed mesh
+    ``vertices`` [V,3] float32, ``faces`` [F,3] - every point against every face, ``block`` (point, face) pairs at a time.  A
+    face is valid when its three indices lie inside the vertices and its corners are finite; the others are skipped and
+    counted.  A point that is not finite gets (0, 0) and is counted.  Everything is elementwise float64 in the order written,
+    from the float32 corners a, b, c and the float32 point:
+
+      box        the face is a candidate only if min(ax, bx, cx) <= qx <= max(ax, bx, cx) and the same in y (the float32
+                 values themselves).  It excludes no face that lies over q; as a part of the definition it makes pruning by
+                 boxes exact by construction.
+      side       of each directed edge u -> v (a -> b, b -> c, c -> a): (lo, hi) = the endpoints ordered lexicographically by
+                 their (x, y, z) values - not indices: a soup, a weld of it and duplicated vertices give a shared edge the same
+                 number;  s = (hx - lx) (qy - ly) - (hy - ly) (qx - lx);  where s == 0: s = -sign(hy - ly) if hy != ly, else
+                 sign(hx - lx) (0 when the edge projects to a point);  negated when the face walks the edge hi -> lo.  The tie
+                 rule is a symbolic shift of q by (eps, eps^2) in x, y: a ray never meets a projected edge or vertex, and a
+                 face that projects to a segment never contains q.
+      facing     up-facing over q when the three sides are > 0, down-facing when they are < 0; otherwise it does not count.
+      height     A = a - q, B = b - q, C = c - q, det = (Ax (By Cz - Bz Cy) + Ay (Bz Cx - Bx Cz)) + Az (Bx Cy - By Cx);
+                 det == 0 counts for neither ray.
+      counts     up = #(up-facing, det > 0) - #(down-facing, det < 0);  down = #(down-facing, det > 0) - #(up-facing, det < 0).
+
+    For a closed mesh wound like marching cubes' (positive ``volume``) both equal the winding number; a point is inside when
+    up != 0, and up != down marks it ambiguous (see MeshWinding).  Nothing here repairs open meshes.
+    -> (up [M] int32, down [M] int32, counts [5] int32: skipped faces, points that are not finite, the status word of
+    mesh_distance, and valid faces x finite points - the pairs of a scan over all faces - as two 32-bit halves)."""
+    p32 = np.asarray(points, np.float32).reshape(-1, 3)
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    valid, status = _valid_faces(v32, f)
+    corners32 = v32[f[valid]]                                        # [Fv,3,3]
+    corners = corners32.astype(np.float64)
+    lo32, hi32 = corners32[:, :, :2].min(axis=1), corners32[:, :, :2].max(axis=1)
+    M = len(p32)
+    up, down = np.zeros(M, np.int32), np.zeros(M, np.int32)
+    finite = np.all(np.isfinite(p32), axis=1)
+    rows = np.flatnonzero(finite)
+    chunk = max(1, int(block) // max(len(corners), 1))
+    with np.errstate(over="ignore", invalid="ignore"):
+        for r0 in range(0, len(rows) if len(corners) else 0, chunk):
+            sel = rows[r0:r0 + chunk]
+            qx32, qy32 = p32[sel, 0, None], p32[sel, 1, None]
+            box = (lo32[None, :, 0] <= qx32) & (qx32 <= hi32[None, :, 0]) & (lo32[None, :, 1] <= qy32) & (qy32 <= hi32[None, :, 1])
+            qi, fi = np.nonzero(box)                                 # the candidates, pair by pair from here on
+            q = p32[sel[qi]].astype(np.float64)
+            a, b, c = (tuple(corners[fi, k, j] for j in range(3)) for k in range(3))
+            sides = [_edge_side_host(u, v, q[:, 0], q[:, 1]) for u, v in ((a, b), (b, c), (c, a))]
+            faces_up = (sides[0] > 0) & (sides[1] > 0) & (sides[2] > 0)
+            faces_down = (sides[0] < 0) & (sides[1] < 0) & (sides[2] < 0)
+            A, B, C = (tuple(x[j] - q[:, j] for j in range(3)) for x in (a, b, c))
+            det = (A[0] * (B[1] * C[2] - B[2] * C[1]) + A[1] * (B[2] * C[0] - B[0] * C[2])) + A[2] * (B[0] * C[1] - B[1] * C[0])
+            above, below = det > 0.0, det < 0.0
+            for out, plus, minus in ((up, faces_up & above, faces_down & below), (down, faces_down & above, faces_up & below)):
+                term = plus.astype(np.int64) - minus.astype(np.int64)
+                out[sel] = np.bincount(qi, weights=term, minlength=len(sel)).astype(np.int32)
+    bad = int(M - len(rows))
+    pairs = int(valid.sum()) * len(rows)
+    counts = np.array([len(f) - int(valid.sum()), bad, status | (MESH_DISTANCE_STATUS_QUERY if bad else 0), pairs & 0xffffffff,
+                       pairs >> 32], np.int64).astype(np.uint32).view(np.int32)
+    return up, down, counts
+
+
+def _device_weld_of(mesh):
+    if mesh._device_weld is None:
+        mesh._device_weld = weld_mesh(mesh.device_triangles, normals=True)
+    return mesh._device_weld[0], mesh._device_weld[1]
+
+
+def _winding_scratch(lib, n_faces, n_queries, dev, who):
+    from .. import _lib
+    nbytes = lib.zs_mesh_winding_scratch_bytes(n_faces, n_queries)
+    if nbytes == 0:
+        raise _lib.ZeroShapeHipError("%s: %d faces and %d points exceed the kernels' limits" % (who, n_faces, n_queries))
+    return torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+
+
+@torch.no_grad()
+def mesh_winding(mesh, points):
+    """On which side of the surface of ``mesh`` (a SimpleMesh) the ``points`` [M,3] lie: the signed crossing numbers of the
+    +z and the -z ray from every point -> a MeshWinding.  The semantics are mesh_winding_host's: float64 arithmetic on the
+    float32 vertices and points, a symbolic shift of the point where a ray would meet an edge or a vertex, faces with a corner
+    that is not finite skipped, (0, 0) for a point that is not finite.  Exact, and meaningful for meshes that are open, folded
+    or overlapping: an open mesh gives ambiguous points (``up != down``) instead of a wrong answer.
+    A GPU mesh is searched on the device (zs_mesh_winding: a uniform grid of columns over x, y that skips only faces whose box
+    does not contain the point - the brute force's integers) on the weld it carries or, if it has none yet, on one weld_mesh
+    call whose result it then keeps; ``points`` must then be a CUDA float32 tensor (ValueError otherwise), the results are
+    CUDA tensors and nothing is read back: ``MeshWinding.check()`` reads the counts.  A host mesh goes through the numpy
+    checker."""
+    if getattr(mesh, "device_triangles", None) is None:
+        if isinstance(points, torch.Tensor):
+            points = points.detach().cpu().numpy()
+        return MeshWinding(*mesh_winding_host(points, mesh.vertices, mesh.faces))
+    if not (isinstance(points, torch.Tensor) and points.is_cuda):
+        raise ValueError("mesh_winding: a GPU mesh needs its points as a CUDA tensor")
+    from .. import _lib
+    lib = _lib.load()
+    vertices, faces = _device_weld_of(mesh)
+    dev = vertices.device
+    pts = points.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    n, n_verts, m = faces.shape[0], vertices.shape[0], pts.shape[0]
+    up = torch.empty(m, dtype=torch.int32, device=dev)
+    down = torch.empty(m, dtype=torch.int32, device=dev)
+    counts = torch.zeros(5, dtype=torch.int32, device=dev)
+    if m == 0:
+        return MeshWinding(up, down, counts)
+    scratch = _winding_scratch(lib, n, m, dev, "mesh_winding")
+    with _lib.on(dev):
+        _lib.check(lib.zs_mesh_winding(_lib.ptr(vertices), _lib.ptr(faces), n, n_verts, _lib.ptr(pts), m, _lib.ptr(up),
+                                       _lib.ptr(down), _lib.ptr(counts), _lib.ptr(scratch), _lib.current_stream_ptr(dev)),
+                   "zs_mesh_winding")
+    return MeshWinding(up, down, counts)
+
+
+def mesh_contains(mesh, points):
+    """trimesh's ``contains``: whether each of ``points`` [M,3] lies inside ``mesh`` - mesh_winding(mesh, points).up != 0 ->
+    [M] bool, a CUDA tensor for a GPU mesh (nothing is read back), a numpy array for a host mesh.  A point on the surface or
+    under a hole gets the answer of its +z ray; mesh_winding tells which points those are."""
+    return mesh_winding(mesh, points).up != 0
+
+
+def mesh_signed_distance(mesh, points, closest=False):
+    """The signed distance from ``points`` [M,3] to the surface of ``mesh``: sqrt(sqdist) of mesh_distance, negative where
+    mesh_winding's ``up`` != 0 (inside: the usual sign of a signed distance field) -> [M] float64, or with ``closest`` the pair
+    (signed distance, the nearest point of the surface [M,3] float64).  A point that is not finite keeps NaN and every point
+    against an empty mesh keeps +inf.  CUDA tensors for a GPU mesh - two searches, the sign applied on the device, nothing
+    read back - and numpy arrays for a host mesh."""
+    done = mesh_distance(mesh, points, closest=closest)
+    inside = mesh_winding(mesh, points).up != 0
+    if isinstance(done.sqdist, torch.Tensor):
+        d = torch.sqrt(done.sqdist)
+        signed = torch.where(inside, -d, d)
+    else:
+        with np.errstate(invalid="ignore"):
+            d = np.sqrt(done.sqdist)
+        signed = np.where(inside, -d, d)
+    return (signed, done.closest) if closest else signed
+
+
+def _lattice_host(G, scale, offset):
+    """The G^3 lattice points of zs_mesh_winding_grid, x slowest: fmaf(i, scale, offset) per axis in float32."""
+    axis = _fma32(np.arange(G, dtype=np.float32), np.full(G, scale, np.float32), np.full(G, offset, np.float32))
+    return np.stack(np.meshgrid(axis, axis, axis, indexing="ij"), axis=-1).reshape(-1, 3)
+
+
+@torch.no_grad()
+def mesh_occupancy_grid(mesh, G, scale, offset):
+    """The inverse of marching cubes: the occupancy of ``mesh`` on the G^3 lattice whose point (ix, iy, iz) lies at
+    fmaf(i, scale, offset) per axis in float32 - the formula marching cubes uses for its vertices, so with
+    scale = (range_max - range_min) / G and offset = range_min a mesh is tested on the lattice it was made on.
+    -> (inside [G,G,G] int8, x slowest: mesh_winding's ``up`` != 0 at every lattice point; counts [6] int32: MeshWinding's
+    five words and the number of ambiguous points).  A GPU mesh makes the lattice in the kernel (zs_mesh_winding_grid) on the
+    weld it carries or makes and keeps; the results are CUDA tensors and nothing is read back.  A host mesh goes through the
+    numpy checker."""
+    G = int(G)
+    if G < 0:
+        raise ValueError("mesh_occupancy_grid: G must not be negative, got %d" % G)
+    scale, offset = float(np.float32(scale)), float(np.float32(offset))
+    if getattr(mesh, "device_triangles", None) is None:
+        up, down, counts = mesh_winding_host(_lattice_host(G, scale, offset), mesh.vertices, mesh.faces)
+        return (up != 0).astype(np.int8).reshape(G, G, G), np.append(counts, np.int32((up != down).sum()))
+    from .. import _lib
+    lib = _lib.load()
+    vertices, faces = _device_weld_of(mesh)
+    dev = vertices.device
+    inside = torch.empty(G, G, G, dtype=torch.int8, device=dev)
+    counts = torch.zeros(6, dtype=torch.int32, device=dev)
+    if G == 0:
+        return inside, counts
+    if G > 645:
+        raise _lib.ZeroShapeHipError("mesh_occupancy_grid: G = %d exceeds the kernels' limit (G^3 <= 2^28)" % G)
+    n, n_verts = faces.shape[0], vertices.shape[0]
+    scratch = _winding_scratch(lib, n, G ** 3, dev, "mesh_occupancy_grid")
+    with _lib.on(dev):
+        _lib.check(lib.zs_mesh_winding_grid(_lib.ptr(vertices), _lib.ptr(faces), n, n_verts, G, scale, offset, _lib.ptr(inside),
+                                            _lib.ptr(counts), _lib.ptr(scratch), _lib.current_stream_ptr(dev)),
+                   "zs_mesh_winding_grid")
+    return inside, counts
+
+
+MeshVolumeIoU = collections.namedtuple(
+    "MeshVolumeIoU", "inside inside_reference both either iou ambiguous ambiguous_reference cell_volume")
+MeshVolumeIoU.__doc__ = """What mesh_volume_iou counted on a lattice: the lattice points inside the mesh (``inside``), inside the reference
+(``inside_reference``), inside both and inside either; ``iou`` = both / either (NaN when either is 0); the lattice points
+whose two rays disagreed (``ambiguous`` for the mesh, ``ambiguous_reference`` for the reference: points on the surface, or
+under a hole of an open mesh - counted, not repaired); and ``cell_volume`` = scale^3, so that a count times it approximates a
+volume in mesh units.  The record is LATTICE-SAMPLED: counts of lattice points, not integrals over the solids."""
+
+
+@torch.no_grad()
+def mesh_volume_iou(mesh, reference, G, scale, offset):
+    """The volume intersection-over-union of ``mesh`` and ``reference`` (two SimpleMesh, both on the GPU or both on the host;
+    typically a smoothed or simplified mesh and the mesh it was made from), LATTICE-SAMPLED: the occupancies of both meshes on
+    the G^3 lattice of mesh_occupancy_grid are counted, not the solids integrated -> a MeshVolumeIoU.  Unlike the signed sum
+    behind ``mesh.volume`` the occupancy is meaningful for meshes that are open, folded or overlapping; the record says how
+    many lattice points were ambiguous.  On the GPU: two zs_mesh_winding_grid calls and one zs_occupancy_counts call on the
+    welds the meshes carry (made and kept where missing), then ONE small read-back - the four counts and the two count
+    records; on the host the numpy checker, which gives the same integers."""
+    on_device = getattr(mesh, "device_triangles", None) is not None
+    if on_device != (getattr(reference, "device_triangles", None) is not None):
+        raise ValueError("mesh_volume_iou: both meshes must live on the GPU or both on the host")
+    a, counts_a = mesh_occupancy_grid(mesh, G, scale, offset)
+    b, counts_b = mesh_occupancy_grid(reference, G, scale, offset)
+    if not on_device:
+        x, y = a != 0, b != 0
+        totals = [int(x.sum()), int(y.sum()), int((x & y).sum()), int((x | y).sum())]
+        words_a, words_b = counts_a.tolist(), counts_b.tolist()
+    else:
+        from .. import _lib
+        lib = _lib.load()
+        dev = a.device
+        out = torch.zeros(4, dtype=torch.int64, device=dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_occupancy_counts(_lib.ptr(a), _lib.ptr(b), a.numel(), _lib.ptr(out), _lib.current_stream_ptr(dev)),
+                       "zs_occupancy_counts")
+        tail = torch.cat([out, counts_a.to(torch.int64), counts_b.to(torch.int64)]).tolist()               # the one D2H
+        totals, words_a, words_b = tail[:4], tail[4:10], tail[10:]
+    for words in (words_a, words_b):
+        _winding_counts([int(v) for v in words], "zs_mesh_winding_grid")
+    inside, inside_reference, both, either = (int(v) for v in totals)
+    return MeshVolumeIoU(inside, inside_reference, both, either, both / float(either) if either else float("nan"),
+                         int(words_a[5]), int(words_b[5]), float(np.float32(scale)) ** 3)
+
+
 def mesh_report(mesh):
     """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
     per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``, a mesh that
     simplify_mesh made its ``simplification`` (the cell, the origin, the placement and the counts: with ``is_watertight`` and
     the component table beside it, what the clustering did to the surface), and a mesh that carries a ``deviation`` (a
     MeshDeviation, set by the pipelines under ``eval.mesh_deviation``) that record - with the six distances also in
-    marching-cubes cells (``*_cells``) when the record knows the cell edge."""
+    marching-cubes cells (``*_cells``) when the record knows the cell edge; a mesh that carries a ``volume_iou`` (a
+    MeshVolumeIoU, set by the pipelines under ``eval.mesh_iou``) that record."""
     comps = mesh.components
     report = dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
                   area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
@@ -2007,6 +2300,8 @@ def mesh_report(mesh):
                 for what in ("max", "mean", "rms"):
                     record["%s_%s_cells" % (side, what)] = record["%s_%s" % (side, what)] / record["cell_edge"]
         report["deviation"] = record
+    if getattr(mesh, "volume_iou", None) is not None:
+        report["volume_iou"] = mesh.volume_iou._asdict()
     return report
 
 
@@ -2355,7 +2650,9 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
     filter_components first, with ``opt.eval.smooth_iterations`` set (opt-in, _smooth_options) through smooth_mesh after
     that, with ``opt.eval.simplify_cells`` set (opt-in, _simplify_options) through simplify_mesh last, and the points are
     sampled on what comes out: the metrics describe the mesh that is delivered.  With ``opt.eval.mesh_deviation`` (opt-in,
-    _deviation_option) that mesh carries ``deviation``: how far the smoothing and the simplification moved the surface."""
+    _deviation_option) that mesh carries ``deviation``: how far the smoothing and the simplification moved the surface; with
+    ``opt.eval.mesh_iou`` (opt-in, _iou_option) it carries ``volume_iou``: how much volume they added or removed, counted on
+    the level grid's own marching-cubes lattice."""
     device = getattr(opt, "device", "cuda")
     meshes, clouds = [], []
     for i, g in enumerate(level_grids):
@@ -2365,13 +2662,14 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
         range_min, range_max = opt.eval.range
         cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
         deviation_cell = _deviation_option(opt, smoothing, simplifying)
+        iou_lattice = _iou_option(opt, smoothing, simplifying, G=vol.shape[0])
         if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(vol, isoval, range_min, range_max,
                                         opt.eval.num_points if to_pointcloud else 0, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
         else:                   # marching cubes, filter_components, smooth_mesh, simplify_mesh, then sampling with the same seed
             tris, _ = extract_surface(vol, isoval, range_min, range_max)
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell, iou_lattice)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i) if to_pointcloud else None
         meshes.append(mesh)
         if to_pointcloud:
