@@ -68,6 +68,15 @@ vertex the input camera saw takes the photo's bilinear texel, every other vertex
 surface (0, the default: no fade), --eval.color_min_cos (0.1) is the smallest cosine between a vertex normal and the ray to the
 camera that still counts as facing it, --eval.color_supersample (2) the z-buffer's resolution over the photo's.  Applied
 after the component filter and the field normals.
+
+--eval.mesh_reprojection=true (opt-in, shape task; needs no smoothing or simplification: it scores the prediction itself)
+relates the mesh to the photo it was predicted from, without ground truth (eval_3D.reprojection, exact first hits of the input
+camera's rays on the GPU): does the silhouette of the mesh cover the input mask, and does its first surface lie where the
+predicted depth says the seen surface is?  <name>_mesh_depth.png is the depth map of the mesh in the input camera (written
+like <name>_depth_est.png, over the pixels the mesh covers), and with --eval.mesh_report=true the report gains a
+`reprojection` entry: the pixel counts and the silhouette IoU, max / mean / rms of |Z_mesh - depth| in camera units, mesh
+units and marching-cubes cells with the pixel at the maximum, the pixels that agree within the colour pass's depth tolerance,
+and the pixels whose first hit is a back face.  It is sampled at the pixel centres.
 """
 import importlib
 import os
@@ -168,6 +177,7 @@ def main():
     field_normals = bool(opt.eval.get("field_normals", False))
     mesh_report = bool(opt.eval.get("mesh_report", False))
     colors = eval_3D.color_options(opt)
+    reprojection = eval_3D.reprojection_option(opt)
     for var, name in zip(data_list, name_list):
         with torch.no_grad():
             var = graph.forward(opt, var, training=False, get_loss=False)
@@ -180,6 +190,11 @@ def main():
                     eval_3D.field_normals(opt, graph.impl_network, var.latent_depth, var.latent_semantic, var.mesh_pred)
                 if colors is not None:  # --eval.vertex_colors=true: `v x y z r g b` lines, a coloured turntable, the seen fraction
                     eval_3D.vertex_colors(opt, var, **colors)
+                if reprojection:       # --eval.mesh_reprojection=true: <name>_mesh_depth.png, the report's `reprojection` entry
+                    eval_3D.reprojection(opt, var)
+                    depth = torch.stack([m.depth_map.depth for m in var.mesh_pred])[:, None]
+                    util_vis.dump_depths(opt, [name], "mesh_depth", torch.nan_to_num(depth, nan=0.0, posinf=0.0),
+                                         torch.isfinite(depth), rescale=True, folder='preds')
                 util_vis.dump_meshes(opt, [name], "mesh", var.mesh_pred, folder='preds',
                                      normals="field" if field_normals else False, colors=colors is not None)
                 if mesh_report:        # --eval.mesh_report=true: <name>_mesh_report.json, the totals and components of that mesh

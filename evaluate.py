@@ -17,7 +17,10 @@ seen area fraction of a coloured mesh.  --eval.mesh_deviation=true (with --eval.
 error without either) records on every predicted mesh how far those steps moved the surface (eval_3D.mesh_deviation: vertex to
 surface distances both ways, on the GPU); the report then carries a `deviation` entry.  --eval.mesh_iou=true (under the same
 condition) records how much volume they added or removed (eval_3D.mesh_volume_iou: the occupancy of both meshes on the
-evaluation grid's lattice, on the GPU); the report then carries a `volume_iou` entry.
+evaluation grid's lattice, on the GPU); the report then carries a `volume_iou` entry.  --eval.mesh_reprojection=true (no
+condition: it scores the prediction itself) casts the rays of the input camera at every predicted mesh on the GPU
+(eval_3D.reprojection) and compares the silhouette with the input mask and the first surface with the predicted depth; the
+report then carries a `reprojection` entry.
 
 ZS_VIRTUAL_RANKS=N (with ZS_DEVICE_OVERRIDE=0 ZS_DIST_BACKEND=gloo) rehearses the N-rank path on one GPU.
 """

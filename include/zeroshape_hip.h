@@ -641,6 +641,53 @@ int zs_mesh_winding_grid(const float *vertices, const int *faces, int n_faces, i
 int zs_occupancy_counts(const signed char *a, const signed char *b, long long n, long long *out, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Where a ray first meets a triangle mesh (csrc/mesh_rays.hip; the semantics are
+ * eval_3D.mesh_rays_host's, bit for bit).  vertices [n_verts,3] fp32 and faces [n_faces,3] int32 are
+ * the weld's (zs_mesh_weld), origins and directions [n_rays,3] fp32, t_min <= t <= t_max the range
+ * of the ray parameter (both ends inclusive; -inf and +inf allowed).
+ * The watertight test of Woop, Benthin and Wald (2013), fp64 as written from the fp32 values:
+ *   ray     kz = the first axis with the largest |d|, kx = (kz + 1) mod 3, ky = (kx + 1) mod 3, kx and
+ *           ky swapped when d[kz] < 0; Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].
+ *   face    A = a - o; Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz], Az = Sz A[kz]; so for B and C;
+ *           U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax; det = (U + V) + W;
+ *           t = ((U Az + V Bz) + W Cz) / det.
+ *   hit     iff U, V, W are all >= 0 or all <= 0, det != 0, t_min <= t <= t_max and t is finite.
+ *   result  the smallest t, the lowest face index among equal t: out_t [n_rays] fp64 (+inf for a
+ *           miss), out_face [n_rays] int32 (-1), out_side [n_rays] int8 (+1 when det > 0: the ray
+ *           meets the face against its normal (b - a) x (c - a); -1 from behind; 0 for a miss) and
+ *           out_bary [n_rays,3] fp64 (may be NULL): U / det, V / det, W / det, the weights of
+ *           a, b, c (NaN for a miss).
+ *   A face with an index outside [0, n_verts) or a corner that is not finite is skipped (no index is
+ *   used as an address before it is tested); a ray with a component that is not finite or with
+ *   d = 0 gets (NaN, -1, 0).
+ * out_counts[5] (device ints): as zs_mesh_distance's - skipped faces, invalid rays, status (|1 a
+ * corner that is not finite, |2 a face index outside the vertices, |4 an invalid ray), and the
+ * number of (ray, face) pairs read, as two 32-bit halves, low first.
+ * The search is the uniform grid of zs_mesh_distance (each face binned once, by the centre of its
+ * box; at most 64^3 cells) walked slab by slab along the ray's major axis with the integer reaches
+ * of zs_mesh_winding; it ends when the next slab begins beyond the best t.  The call only enqueues.
+ * scratch, 8-byte aligned: zs_mesh_rays_scratch_bytes(n_faces, n_rays) bytes (a multiple of 256; 0
+ * for n_rays = 0 and for sizes outside the limits n_faces <= 2^24, n_rays <= 2^28).  n_rays = 0
+ * returns 1 and touches nothing; n_faces = 0 is an empty mesh.
+ *
+ * zs_mesh_rays_image: the same for the H x W rays of a pinhole camera, made in the kernel
+ * (eval_3D.camera_rays_host): pixel (row i, col j) is at (j, i, 1), D = K^-1 (j, i, 1) by the
+ * adjugate in fp64 from intr [9] fp32 (device), D / D_z, o = -mean / scale and d = D / scale
+ * (mean [3], scale [1] fp32, device) rounded to fp32; a pixel whose D_z is not > 0 and finite is an
+ * invalid ray.  out_depth [H,W] fp32 = (float)t - the camera depth Z of the first surface -
+ * out_face [H,W] int32, out_side [H,W] int8.  out_counts[6]: the five words above and the number of
+ * pixels that hit.  scratch: zs_mesh_rays_scratch_bytes(n_faces, H * W); H, W <= 16384 and
+ * H * W <= 2^28; H = 0 or W = 0 returns 1 and touches nothing.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_rays_scratch_bytes(int n_faces, int n_rays);
+int zs_mesh_rays(const float *vertices, const int *faces, int n_faces, int n_verts, const float *origins, const float *directions,
+                 int n_rays, double t_min, double t_max, double *out_t, int *out_face, signed char *out_side, double *out_bary,
+                 int *out_counts, void *scratch, void *stream);
+int zs_mesh_rays_image(const float *vertices, const int *faces, int n_faces, int n_verts, const float *intr, const float *mean,
+                       const float *scale, int H, int W, double t_min, double t_max, float *out_depth, int *out_face,
+                       signed char *out_side, int *out_counts, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
  * itself is Implicit.field_gradient's, between the two calls).
  *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G

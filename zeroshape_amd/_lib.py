@@ -123,6 +123,11 @@ SIGNATURES = {
     "zs_mesh_winding": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int] + [_c_void_p] * 5),
     "zs_mesh_winding_grid": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float] + [_c_void_p] * 4),
     "zs_occupancy_counts": (_c_int, [_c_void_p, _c_void_p, ctypes.c_longlong, _c_void_p, _c_void_p]),
+    "zs_mesh_rays_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+    "zs_mesh_rays": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_double, _c_double]
+                     + [_c_void_p] * 7),
+    "zs_mesh_rays_image": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int,
+                                    _c_double, _c_double] + [_c_void_p] * 6),
     "zs_mesh_to_field_points":(_c_int, [_c_void_p, _c_size_t, _c_float, _c_int, _c_void_p, _c_void_p]),
     "zs_field_normals_finish": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_stats_scratch_bytes": (_c_size_t, [_c_int]),

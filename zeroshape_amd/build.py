@@ -57,6 +57,8 @@ EXTRA = {
     "mesh_distance.hip": ["-ffp-contract=off"],
     # the fp64 edge sides and heights equal, operation for operation, to the numpy restatement in utils/eval_3D.py (mesh_winding_host)
     "mesh_inside.hip": ["-ffp-contract=off"],
+    # the fp64 sheared corners, edge functions and ray parameters equal, operation for operation, to the numpy restatement in utils/eval_3D.py (mesh_rays_host)
+    "mesh_rays.hip": ["-ffp-contract=off"],
 }
 
 

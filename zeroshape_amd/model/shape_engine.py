@@ -451,6 +451,8 @@ class Runner:
         if colors is not None and 'depth_pred' in var:
             eval_3D.vertex_colors(opt, var, **colors)
         colored = colors is not None and 'depth_pred' in var
+        if eval_3D.reprojection_option(opt) and 'depth_pred' in var:    # --eval.mesh_reprojection=true: the report's entry
+            eval_3D.reprojection(opt, var)
         util_vis.dump_meshes(opt, idx, "mesh", var.mesh_pred, folder=folder, colors=colored)
         util_vis.dump_meshes_viz(opt, idx, "mesh_viz", var.mesh_pred, folder=folder, colors=colored)   # image frames + gif
         if bool(opt.eval.get("mesh_report", False)):

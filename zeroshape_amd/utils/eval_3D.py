@@ -864,6 +864,11 @@ class SimpleMesh(object):
         inside ([M] float64; with ``closest`` also the nearest point of the surface)."""
         return mesh_signed_distance(self, points, closest=closest)
 
+    def ray_cast(self, origins, directions, t_min=0.0, t_max=float("inf"), bary=False):
+        """trimesh's ``ray.intersects_first``: mesh_ray_cast(self, origins, directions, ...) - where the rays o + t d first
+        meet this surface (a MeshRays: t, face, side, weights; CUDA tensors for a GPU mesh, whose rays must be CUDA tensors)."""
+        return mesh_ray_cast(self, origins, directions, t_min=t_min, t_max=t_max, bary=bary)
+
     @property
     def vertex_neighbors(self):
         """trimesh's name: a list of V int arrays, the indices of the vertices that share an edge with each vertex, ascending
@@ -2275,6 +2280,424 @@ def mesh_volume_iou(mesh, reference, G, scale, offset):
                          int(words_a[5]), int(words_b[5]), float(np.float32(scale)) ** 3)
 
 
+# ---- where a ray first meets a mesh (csrc/mesh_rays.hip) ----
+
+
+class MeshRays(collections.namedtuple("MeshRays", "t face side bary counts")):
+    """What mesh_ray_cast returns: ``t`` [N] float64 (the ray parameter of the first hit: the point is o + t d; +inf for a
+    miss, NaN for an invalid ray), ``face`` [N] int32 (the face that is hit, the lowest index among equal t; -1 without a
+    hit), ``side`` [N] int8 (+1: the ray meets the face against its normal (b - a) x (c - a), from outside on a marching-cubes
+    mesh; -1: from behind; 0 without a hit), ``bary`` [N,3] float64 (the weights of the face's corners a, b, c at the hit, NaN
+    without one; None unless asked for) and ``counts`` [5] int32 as MeshDistance's - the faces that were skipped, the rays that
+    are invalid, the status word and the number of (ray, face) pairs that were read as two 32-bit halves.  CUDA tensors for a
+    GPU mesh (nothing has been read back), numpy arrays for a host mesh.  ``mesh`` is the mesh that was cast against."""
+    mesh = None
+
+    def check(self):
+        """Reads ``counts`` (for a GPU mesh the one device-to-host copy, 20 bytes) -> dict(skipped_faces, nonfinite_queries,
+        status, pairs).  ZeroShapeHipError when the status word says that a face index lay outside the vertices - a weld
+        never makes one."""
+        return _winding_counts([int(v) for v in self.counts.tolist()], "zs_mesh_rays")
+
+    def points(self):
+        """The hit points [N,3] float64 from the weights, (wa a + wb b) + wc c per component on the mesh's welded corners
+        (NaN rows without a hit) - on the device for a GPU mesh, nothing is read back.  Needs ``bary``."""
+        if self.bary is None:
+            raise ValueError("MeshRays.points needs the weights: cast with bary=True")
+        if isinstance(self.t, torch.Tensor):
+            vertices, faces = _device_weld_of(self.mesh)
+            hit = self.face >= 0
+            corners = vertices.to(torch.float64)[faces.long()[self.face.clamp(min=0).long()]] if faces.shape[0] else \
+                torch.zeros(self.face.shape[0], 3, 3, dtype=torch.float64, device=self.face.device)
+            w = self.bary
+            p = (w[:, 0, None] * corners[:, 0] + w[:, 1, None] * corners[:, 1]) + w[:, 2, None] * corners[:, 2]
+            return torch.where(hit[:, None], p, torch.full_like(p, float("nan")))
+        vertices, faces = self.mesh.vertices, self.mesh.faces
+        hit = self.face >= 0
+        corners = vertices.astype(np.float64)[faces[np.maximum(self.face, 0)]] if len(faces) else np.zeros((len(self.face), 3, 3))
+        w = self.bary
+        with np.errstate(invalid="ignore"):
+            p = (w[:, 0, None] * corners[:, 0] + w[:, 1, None] * corners[:, 1]) + w[:, 2, None] * corners[:, 2]
+        return np.where(hit[:, None], p, np.nan)
+
+
+def _ray_frames(o32, d32):
+    """-> (ok [N] bool, K [N,3] int: the axes kx, ky, kz of every ray, S [N,3] float64: Sx, Sy, Sz) - mesh_rays_host's
+    'per ray' step.  Invalid rays get the frame of +z."""
+    ok = np.all(np.isfinite(o32), axis=1) & np.all(np.isfinite(d32), axis=1) & np.any(d32 != 0.0, axis=1)
+    d = np.where(ok[:, None], d32, np.float32([0.0, 0.0, 1.0])).astype(np.float64)
+    kz = np.argmax(np.abs(d), axis=1)                                # the first of the largest
+    kx = (kz + 1) % 3
+    ky = (kx + 1) % 3
+    rows = np.arange(len(d))
+    dz = d[rows, kz]
+    kx, ky = np.where(dz < 0.0, ky, kx), np.where(dz < 0.0, kx, ky)
+    with np.errstate(over="ignore"):
+        S = np.stack([d[rows, kx] / dz, d[rows, ky] / dz, 1.0 / dz], axis=1)
+    return ok, np.stack([kx, ky, kz], axis=1), S
+
+
+def mesh_rays_host(origins, directions, vertices, faces, t_min=0.0, t_max=np.inf, bary=False, block=1 << 19):
+    """The definition of mesh_ray_cast and the checker of zs_mesh_rays, in numpy: for every ray (o, d) of ``origins`` and
+    ``directions`` [N,3] float32 the first face it meets on the indexed mesh ``vertices`` [V,3] float32, ``faces`` [F,3] - every
+    ray against every valid face, ``block`` (ray, face) pairs at a time.  A face is valid when its three indices lie inside the
+    vertices and its corners are finite; the others are skipped and counted.  A ray is invalid when a component of o or d is
+    not finite or d = 0: it gets (NaN, -1, 0) and is counted.  The test is the watertight one of Woop, Benthin and Wald (2013);
+    everything is elementwise float64 in the order written, from the float32 corners a, b, c and the float32 ray:
+
+      per ray    kz = the first axis with the largest |d|, kx = (kz + 1) mod 3, ky = (kx + 1) mod 3; kx and ky are swapped when
+                 d[kz] < 0;  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].
+      per face   A = a - o;  Ax = A[kx] - (Sx A[kz]), Ay = A[ky] - (Sy A[kz]), Az = Sz A[kz];  the same for B = b - o and
+                 C = c - o;  U = (Cx By) - (Cy Bx), V = (Ax Cy) - (Ay Cx), W = (Bx Ay) - (By Ax);  det = (U + V) + W;
+                 t = (((U Az) + (V Bz)) + (W Cz)) / det.
+      hit        iff (U >= 0 and V >= 0 and W >= 0) or (U <= 0 and V <= 0 and W <= 0), det != 0, t_min <= t <= t_max (edges
+                 and both ends of the range inclusive) and |t| < inf.  The last is a guard: |A| < 2^129 and |Sx|, |Sy| <= 1
+                 keep U, V, W below 2^262 and |Sz| <= 2^149 keeps the numerator below 2^542, but a det that cancels to its
+                 last bits can make the quotient overflow for inputs that span the whole float32 range; such a face is not
+                 hit, so that +inf stays the mark of a miss.  An intermediate that overflows on the way (inf - inf = NaN)
+                 fails the comparisons and is not hit either.
+      result     the smallest t wins, among equal t the lowest face index.  side = +1 where det > 0, -1 where det < 0: with
+                 d = +z the frame is (x, y, z) and det = -((b - a) x (c - a))_z, so det > 0 means that the ray runs AGAINST
+                 the normal - from outside on a mesh wound like marching cubes'; the swap keeps that reading for d[kz] < 0.
+                 The weights of (a, b, c) are U / det, V / det, W / det.
+
+    Watertight: the sheared corner (Ax, Ay) depends on the corner and the ray only, so the two faces at a shared edge compute
+    edge functions that are exact negatives of each other: a ray through a shared edge or a vertex hits at least one of the
+    faces around it.  A ray in the plane of a face, or a face without area, has det = 0 and is not hit.
+    -> (t [N] float64: +inf for a miss, NaN for an invalid ray; face [N] int32: -1; side [N] int8: 0; bary [N,3] float64 with
+    NaN rows, or None without ``bary``; counts [5] int32: skipped faces, invalid rays, the status word of mesh_distance, and
+    valid faces x valid rays - the pairs of a scan over all faces - as two 32-bit halves)."""
+    o32 = np.asarray(origins, np.float32).reshape(-1, 3)
+    d32 = np.asarray(directions, np.float32).reshape(-1, 3)
+    if len(o32) != len(d32):
+        raise ValueError("mesh_rays_host: %d origins and %d directions" % (len(o32), len(d32)))
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    t_min, t_max = np.float64(t_min), np.float64(t_max)
+    valid, status = _valid_faces(v32, f)
+    index = np.flatnonzero(valid)
+    corners = v32[f[index]].astype(np.float64)                       # [Fv,3,3]
+    N = len(o32)
+    ok, K, S = _ray_frames(o32, d32)
+    t_out = np.where(ok, np.inf, np.nan)
+    face_out, side_out = np.full(N, -1, np.int32), np.zeros(N, np.int8)
+    bary_out = np.full((N, 3), np.nan) if bary else None
+    rows = np.flatnonzero(ok)
+    chunk = max(1, int(block) // max(len(corners), 1))
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        for r0 in range(0, len(rows) if len(corners) else 0, chunk):
+            sel = rows[r0:r0 + chunk]
+            k, s = K[sel], S[sel]
+            o = np.take_along_axis(o32[sel].astype(np.float64), k, axis=1)              # [r,3]: o[kx], o[ky], o[kz]
+            P = corners[:, :, k].transpose(2, 0, 1, 3) - o[:, None, None, :]            # [r,Fv,corner,(kx ky kz)]: A, B, C
+            X = P[..., 0] - s[:, 0, None, None] * P[..., 2]
+            Y = P[..., 1] - s[:, 1, None, None] * P[..., 2]
+            Z = s[:, 2, None, None] * P[..., 2]
+            Ax, Bx, Cx = X[..., 0], X[..., 1], X[..., 2]
+            Ay, By, Cy = Y[..., 0], Y[..., 1], Y[..., 2]
+            U = Cx * By - Cy * Bx
+            V = Ax * Cy - Ay * Cx
+            W = Bx * Ay - By * Ax
+            det = (U + V) + W
+            t = ((U * Z[..., 0] + V * Z[..., 1]) + W * Z[..., 2]) / det
+            hit = (((U >= 0.0) & (V >= 0.0) & (W >= 0.0)) | ((U <= 0.0) & (V <= 0.0) & (W <= 0.0))) & (det != 0.0) \
+                & (t >= t_min) & (t <= t_max) & (np.abs(t) < np.inf)
+            t = np.where(hit, t, np.inf)
+            j = np.argmin(t, axis=1)                                 # the first of equal minima: the lowest face index
+            lane = np.arange(len(sel))
+            got = hit[lane, j]
+            t_out[sel] = t[lane, j]
+            face_out[sel] = np.where(got, index[j], -1)
+            side_out[sel] = np.where(got, np.where(det[lane, j] > 0.0, 1, -1), 0)
+            if bary:
+                w = np.stack([U[lane, j], V[lane, j], W[lane, j]], axis=1) / det[lane, j, None]
+                bary_out[sel] = np.where(got[:, None], w, np.nan)
+    bad = int(N - len(rows))
+    pairs = int(valid.sum()) * len(rows)
+    counts = np.array([len(f) - int(valid.sum()), bad, status | (MESH_DISTANCE_STATUS_QUERY if bad else 0), pairs & 0xffffffff,
+                       pairs >> 32], np.int64).astype(np.uint32).view(np.int32)
+    return t_out, face_out, side_out, bary_out, counts
+
+
+def camera_rays_host(intr, mean, scale, H, W):
+    """The rays of zs_mesh_rays_image, in numpy: one ray per pixel of an H x W pinhole camera with the intrinsics ``intr``
+    [3,3] float32, in the frame of a mesh that was normalised by (``mean`` [3], ``scale``) float32 - v = (X - mean) / scale for a
+    camera point X.  Pixel (row i, col j) is at (j, i, 1), camera.get_pixel_grid's and mesh_vertex_colors_host's convention.
+    Float64 in the order written, from the float32 values K = intr:
+
+      c00 = K11 K22 - K12 K21,  c01 = K02 K21 - K01 K22,  c02 = K01 K12 - K02 K11
+      c10 = K12 K20 - K10 K22,  c11 = K00 K22 - K02 K20,  c12 = K02 K10 - K00 K12
+      c20 = K10 K21 - K11 K20,  c21 = K01 K20 - K00 K21,  c22 = K00 K11 - K01 K10      (the adjugate)
+      det = (K00 c00 + K01 c10) + K02 c20
+      D_r = ((c_r0 j + c_r1 i) + c_r2) / det  for r = x, y, z:  D = K^-1 (j, i, 1)
+      o = -mean / scale;  d = ((Dx / Dz) / scale, (Dy / Dz) / scale, 1 / scale)
+
+    both rounded to float32.  A pixel whose Dz is not > 0 and finite gets d = NaN - an invalid ray.  With D / Dz the third
+    component of the camera point o + t d is t itself: the ray parameter is the camera depth Z, up to the rounding of o and d.
+    -> (origins [H*W,3] float32, directions [H*W,3] float32), pixel (i, j) in row i W + j."""
+    K = np.asarray(intr, np.float32).reshape(3, 3).astype(np.float64)
+    mu = np.asarray(mean, np.float32).reshape(3).astype(np.float64)
+    s = np.float64(np.asarray(scale, np.float32).reshape(-1)[0])
+    H, W = int(H), int(W)
+    n = H * W
+    pj = (np.arange(n) % max(W, 1)).astype(np.float64)
+    pi = (np.arange(n) // max(W, 1)).astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        c = [[K[1, 1] * K[2, 2] - K[1, 2] * K[2, 1], K[0, 2] * K[2, 1] - K[0, 1] * K[2, 2], K[0, 1] * K[1, 2] - K[0, 2] * K[1, 1]],
+             [K[1, 2] * K[2, 0] - K[1, 0] * K[2, 2], K[0, 0] * K[2, 2] - K[0, 2] * K[2, 0], K[0, 2] * K[1, 0] - K[0, 0] * K[1, 2]],
+             [K[1, 0] * K[2, 1] - K[1, 1] * K[2, 0], K[0, 1] * K[2, 0] - K[0, 0] * K[2, 1], K[0, 0] * K[1, 1] - K[0, 1] * K[1, 0]]]
+        det = (K[0, 0] * c[0][0] + K[0, 1] * c[1][0]) + K[0, 2] * c[2][0]
+        D = [((c[r][0] * pj + c[r][1] * pi) + c[r][2]) / det for r in range(3)]
+        forward = (D[2] > 0.0) & (D[2] < np.inf)
+        d = np.stack([(D[0] / D[2]) / s, (D[1] / D[2]) / s, np.full(n, 1.0 / s)], axis=1)
+        d = np.where(forward[:, None], d, np.nan).astype(np.float32)
+        o = np.broadcast_to((-mu / s).astype(np.float32), (n, 3)).copy()
+    return o, d
+
+
+def _rays_scratch(lib, n_faces, n_rays, dev, who):
+    from .. import _lib
+    nbytes = lib.zs_mesh_rays_scratch_bytes(n_faces, n_rays)
+    if nbytes == 0:
+        raise _lib.ZeroShapeHipError("%s: %d faces and %d rays exceed the kernels' limits" % (who, n_faces, n_rays))
+    return torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+
+
+@torch.no_grad()
+def mesh_ray_cast(mesh, origins, directions, t_min=0.0, t_max=float("inf"), bary=False):
+    """trimesh's ``ray.intersects_first`` / ``intersects_location``: where the rays o + t d (``origins``, ``directions`` [N,3],
+    t_min <= t <= t_max) first meet the surface of ``mesh`` (a SimpleMesh) -> a MeshRays: the parameter, the face, the side
+    the ray came from and, with ``bary``, the weights of the face's corners (``MeshRays.points()`` makes the hit points of
+    them).  The semantics are mesh_rays_host's: the watertight test in float64 on the float32 vertices and rays, edges and
+    both ends of the range inclusive, the lowest face index among equal t, faces with a corner that is not finite skipped,
+    (NaN, -1, 0) for a ray that is not finite or has no direction.  Directions need not be normalised: t counts in units of |d|.
+    A GPU mesh is searched on the device (zs_mesh_rays: a uniform grid over the faces, walked slab by slab along the ray under
+    bounds that only skip what the test cannot hit - the brute force's bits) on the weld it carries or, if it has none yet, on
+    one weld_mesh call whose result it then keeps; the rays must then be CUDA float32 tensors (ValueError otherwise), the
+    results are CUDA tensors and nothing is read back: ``MeshRays.check()`` reads the counts.  A host mesh goes through the
+    numpy checker."""
+    if getattr(mesh, "device_triangles", None) is None:
+        o, d = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (origins, directions))
+        out = MeshRays(*mesh_rays_host(o, d, mesh.vertices, mesh.faces, t_min, t_max, bary))
+        out.mesh = mesh
+        return out
+    for x in (origins, directions):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise ValueError("mesh_ray_cast: a GPU mesh needs its rays as CUDA tensors")
+    from .. import _lib
+    lib = _lib.load()
+    vertices, faces = _device_weld_of(mesh)
+    dev = vertices.device
+    o = origins.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    d = directions.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    if o.shape[0] != d.shape[0]:
+        raise ValueError("mesh_ray_cast: %d origins and %d directions" % (o.shape[0], d.shape[0]))
+    n, n_verts, m = faces.shape[0], vertices.shape[0], o.shape[0]
+    t = torch.empty(m, dtype=torch.float64, device=dev)
+    face = torch.empty(m, dtype=torch.int32, device=dev)
+    side = torch.empty(m, dtype=torch.int8, device=dev)
+    weights = torch.empty(m, 3, dtype=torch.float64, device=dev) if bary else None
+    counts = torch.zeros(5, dtype=torch.int32, device=dev)
+    if m:
+        scratch = _rays_scratch(lib, n, m, dev, "mesh_ray_cast")
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_rays(_lib.ptr(vertices), _lib.ptr(faces), n, n_verts, _lib.ptr(o), _lib.ptr(d), m, float(t_min),
+                                        float(t_max), _lib.ptr(t), _lib.ptr(face), _lib.ptr(side), _lib.ptr(weights),
+                                        _lib.ptr(counts), _lib.ptr(scratch), _lib.current_stream_ptr(dev)), "zs_mesh_rays")
+    out = MeshRays(t, face, side, weights, counts)
+    out.mesh = mesh
+    return out
+
+
+class MeshDepthMap(collections.namedtuple("MeshDepthMap", "depth face side counts")):
+    """What mesh_depth_map returns: ``depth`` [H,W] float32 (the camera depth Z of the first surface along the pixel's ray:
+    (float)t of mesh_rays_host on camera_rays_host's rays; +inf where the ray misses, NaN for an invalid pixel), ``face``
+    [H,W] int32 and ``side`` [H,W] int8 as MeshRays', and ``counts`` [6] int32: MeshRays' five words and the number of pixels
+    that hit.  CUDA tensors for a GPU mesh (nothing has been read back), numpy arrays for a host mesh."""
+    __slots__ = ()
+
+    def check(self):
+        """Reads ``counts`` -> dict(skipped_faces, nonfinite_queries, status, pairs, hit_pixels); ZeroShapeHipError as
+        MeshRays.check()."""
+        words = [int(v) for v in self.counts.tolist()]
+        return dict(_winding_counts(words, "zs_mesh_rays_image"), hit_pixels=words[5])
+
+
+def _camera_host(intr, mean, scale):
+    return tuple(np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, np.float32) for x in (intr, mean, scale))
+
+
+@torch.no_grad()
+def mesh_depth_map(mesh, intr, mean, scale, H, W, t_min=0.0, t_max=float("inf")):
+    """The image of ``mesh`` in a pinhole camera: for every pixel of an H x W image the depth of the first surface, the face and
+    the side -> a MeshDepthMap.  ``intr`` [3,3], ``mean`` [3] and ``scale`` (one value) are the camera and the normalisation
+    of the mesh frame - one sample of var.intr_pred and of camera.seen_surface's (mean, scale); the rays and their semantics
+    are camera_rays_host's and mesh_rays_host's.  A GPU mesh makes the rays in the kernel (zs_mesh_rays_image) on the weld it
+    carries or makes and keeps; the camera must then be CUDA tensors (ValueError otherwise), the results are CUDA tensors and
+    nothing is read back.  A host mesh goes through the numpy checkers."""
+    H, W = int(H), int(W)
+    if H < 0 or W < 0:
+        raise ValueError("mesh_depth_map: H and W must not be negative, got %d x %d" % (H, W))
+    if getattr(mesh, "device_triangles", None) is None:
+        o, d = camera_rays_host(*_camera_host(intr, mean, scale), H, W)
+        t, face, side, _, counts = mesh_rays_host(o, d, mesh.vertices, mesh.faces, t_min, t_max)
+        with np.errstate(over="ignore"):
+            depth = t.astype(np.float32)
+        return MeshDepthMap(depth.reshape(H, W), face.reshape(H, W), side.reshape(H, W), np.append(counts, np.int32((face >= 0).sum())))
+    tensors = dict(intr=intr, mean=mean, scale=scale)
+    for name, x in tensors.items():
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise ValueError("mesh_depth_map: a GPU mesh needs %s as a CUDA tensor" % name)
+    intr, mean, scale = [_gpu_f32(tensors[k], k) for k in ("intr", "mean", "scale")]
+    if intr.numel() != 9 or mean.numel() != 3 or scale.numel() != 1:
+        raise ValueError("mesh_depth_map: intr must hold 9 values, mean 3 and scale 1")
+    from .. import _lib
+    lib = _lib.load()
+    vertices, faces = _device_weld_of(mesh)
+    dev = vertices.device
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    face = torch.empty(H, W, dtype=torch.int32, device=dev)
+    side = torch.empty(H, W, dtype=torch.int8, device=dev)
+    counts = torch.zeros(6, dtype=torch.int32, device=dev)
+    if H * W:
+        n, n_verts = faces.shape[0], vertices.shape[0]
+        scratch = _rays_scratch(lib, n, H * W, dev, "mesh_depth_map")
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_rays_image(_lib.ptr(vertices), _lib.ptr(faces), n, n_verts, _lib.ptr(intr), _lib.ptr(mean),
+                                              _lib.ptr(scale), H, W, float(t_min), float(t_max), _lib.ptr(depth), _lib.ptr(face),
+                                              _lib.ptr(side), _lib.ptr(counts), _lib.ptr(scratch), _lib.current_stream_ptr(dev)),
+                       "zs_mesh_rays_image")
+    return MeshDepthMap(depth, face, side, counts)
+
+
+MeshReprojection = collections.namedtuple(
+    "MeshReprojection", "mask_pixels mesh_pixels both either silhouette_iou depth_pixels depth_max depth_mean depth_rms "
+                        "depth_max_pixel depth_max_mesh depth_mean_mesh depth_rms_mesh depth_max_cells depth_mean_cells "
+                        "depth_rms_cells agreeing back_faces depth_tol scale cell_edge")
+MeshReprojection.__doc__ = """What mesh_reprojection measured between a mesh and the photo it was predicted from, in the input camera.  With R
+the pixels whose ray hits the mesh and M the pixels of the mask (> 0.5): ``mask_pixels`` = |M|, ``mesh_pixels`` = |R|, ``both``,
+``either`` and ``silhouette_iou`` = both / either (NaN when either is 0).  Over the ``depth_pixels`` pixels of M and R whose
+predicted depth is finite and positive: ``depth_max``, ``depth_mean`` and ``depth_rms`` of |Z_mesh - depth| in camera units (NaN
+without such a pixel), ``depth_max_pixel`` the (row, col) where the largest is attained (the first in row order; None
+without one), the same three in mesh units (``*_mesh``: / scale) and, when ``cell_edge`` is known, in marching-cubes cells
+(``*_cells``, else None).  ``agreeing``: the pixels among them with |Z_mesh - depth| <= depth_tol scale (``depth_tol`` in mesh
+units).  ``back_faces``: the pixels of R whose first hit has side -1 - the camera is inside the mesh, or the mesh is open
+towards it.  ``scale``: the normalisation's.  The record is PIXEL-SAMPLED: one ray through each pixel's centre."""
+
+
+def _reprojection_record(counts4, stats, at, agreeing, back_faces, depth_tol, scale, cell_edge, W):
+    mask_pixels, mesh_pixels, both, either = (int(v) for v in counts4)
+    n = int(stats[3])
+    mx, mean, rms = (float(v) for v in stats[:3])
+    scale = float(scale)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        in_mesh = [float(np.float64(v) / np.float64(scale)) for v in (mx, mean, rms)]
+        in_cells = [None] * 3 if cell_edge is None else [float(np.float64(v) / np.float64(cell_edge)) for v in in_mesh]
+    pixel = None if int(at) < 0 else (int(at) // int(W), int(at) % int(W))
+    return MeshReprojection(mask_pixels, mesh_pixels, both, either, both / float(either) if either else float("nan"), n, mx, mean,
+                            rms, pixel, in_mesh[0], in_mesh[1], in_mesh[2], in_cells[0], in_cells[1], in_cells[2], int(agreeing),
+                            int(back_faces), float(depth_tol), scale, None if cell_edge is None else float(cell_edge))
+
+
+def mesh_reprojection_host(vertices, faces, mask, depth, intr, mean, scale, depth_tol, cell_edge=None):
+    """The definition of mesh_reprojection and its checker, in numpy on mesh_rays_host: ``mask`` and ``depth`` hold H x W
+    float32 values (``mask`` gives H and W), the camera is camera_rays_host's.  Z_mesh = float32(t) of the pixel's ray (what
+    mesh_depth_map stores), R = the pixels that hit, M = mask > 0.5, the depth pixels = M and R and depth finite and > 0;
+    e = |float64(Z_mesh) - float64(depth)|; max, mean and rms = mesh_distance_stats_host of e e (the kernel's summation
+    order); agreeing = #(e <= float64(depth_tol) float64(scale)); back_faces = #(side = -1).  -> a MeshReprojection."""
+    msk = np.asarray(mask, np.float32)
+    msk = msk.reshape(msk.shape[-2:])
+    H, W = msk.shape
+    dep = np.asarray(depth, np.float32).reshape(H, W)
+    K, mu, s = (np.asarray(x, np.float32) for x in (intr, mean, scale))
+    o, d = camera_rays_host(K, mu, s, H, W)
+    t, face, side, _, _ = mesh_rays_host(o, d, vertices, faces)
+    with np.errstate(over="ignore", invalid="ignore"):
+        z = t.astype(np.float32).reshape(H, W)
+        R, M = (face >= 0).reshape(H, W), msk > np.float32(0.5)
+        use = M & R & np.isfinite(dep) & (dep > 0.0)
+        e = np.abs(z.astype(np.float64) - dep.astype(np.float64))
+        sq = np.where(use, e * e, np.nan).reshape(-1)
+        stats, at = mesh_distance_stats_host(sq)
+        tol = np.float64(depth_tol) * np.float64(s.reshape(-1)[0])
+        agreeing = int((use & (e <= tol)).sum())
+    return _reprojection_record([M.sum(), R.sum(), (M & R).sum(), (M | R).sum()], stats, at, agreeing, int((side == -1).sum()),
+                                depth_tol, s.reshape(-1)[0], cell_edge, W)
+
+
+@torch.no_grad()
+def mesh_reprojection(mesh, mask, depth, intr, mean, scale, depth_tol, cell_edge=None, depth_map=None):
+    """A ground-truth-free score of a predicted mesh: its image in the input camera against the input mask and the predicted
+    depth -> a MeshReprojection (the semantics: mesh_reprojection_host).  ``mask`` and ``depth`` hold H x W values (one sample
+    of var.mask_input_map and var.depth_pred), ``intr``, ``mean``, ``scale`` as for mesh_depth_map, ``depth_tol`` in mesh units,
+    ``cell_edge`` the edge of a marching-cubes cell in mesh units when the distances are wanted in cells too.  On the GPU:
+    mesh_depth_map (or ``depth_map``, a MeshDepthMap of the same camera made before), zs_occupancy_counts on the two
+    silhouettes, zs_mesh_distance_stats on the squared differences, then ONE small read-back; a host mesh goes through the
+    numpy checker, which gives the same numbers bit for bit."""
+    if getattr(mesh, "device_triangles", None) is None:
+        args = [x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (mask, depth, intr, mean, scale)]
+        return mesh_reprojection_host(mesh.vertices, mesh.faces, *args, depth_tol=depth_tol, cell_edge=cell_edge)
+    tensors = dict(mask=mask, depth=depth, intr=intr, mean=mean, scale=scale)
+    for name, x in tensors.items():
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise ValueError("mesh_reprojection: a GPU mesh needs %s as a CUDA tensor" % name)
+    mask, depth, scale = _gpu_f32(mask, "mask"), _gpu_f32(depth, "depth"), _gpu_f32(scale, "scale")
+    if mask.dim() < 2 or depth.numel() != mask.numel():
+        raise ValueError("mesh_reprojection: mask must be [..,H,W] and depth must hold as many values")
+    H, W = int(mask.shape[-2]), int(mask.shape[-1])
+    if mask.numel() != H * W:
+        raise ValueError("mesh_reprojection: one sample at a time, got a mask of shape %s" % (tuple(mask.shape),))
+    from .. import _lib
+    lib = _lib.load()
+    image = mesh_depth_map(mesh, intr, mean, scale, H, W) if depth_map is None else depth_map
+    dev = image.depth.device
+    mask, depth = mask.reshape(H, W).to(dev), depth.reshape(H, W).to(dev)
+    R, M = image.face >= 0, mask > 0.5
+    use = M & R & torch.isfinite(depth) & (depth > 0.0)
+    e = (image.depth.to(torch.float64) - depth.to(torch.float64)).abs()
+    sq = torch.where(use, e * e, torch.full_like(e, float("nan"))).reshape(-1).contiguous()
+    tol = float(depth_tol) * scale.reshape(-1)[0].to(device=dev, dtype=torch.float64)
+    a, b = R.to(torch.int8).contiguous(), M.to(torch.int8).contiguous()
+    totals = torch.zeros(4, dtype=torch.int64, device=dev)
+    stats = torch.tensor([float("nan")] * 3 + [0.0], dtype=torch.float64, device=dev)
+    at = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    with _lib.on(dev):
+        _lib.check(lib.zs_occupancy_counts(_lib.ptr(b), _lib.ptr(a), H * W, _lib.ptr(totals), _lib.current_stream_ptr(dev)),
+                   "zs_occupancy_counts")
+        _lib.check(lib.zs_mesh_distance_stats(_lib.ptr(sq), H * W, _lib.ptr(stats), _lib.ptr(at), _lib.current_stream_ptr(dev)),
+                   "zs_mesh_distance_stats")
+    more = torch.stack([(use & (e <= tol)).sum(), (image.side == -1).sum()]).to(torch.float64)
+    tail = torch.cat([totals.to(torch.float64), stats, at.to(torch.float64), more, scale.reshape(-1)[:1].to(dev, torch.float64),
+                      image.counts.to(torch.float64)]).tolist()                                      # the one D2H
+    _winding_counts([int(v) for v in tail[12:17]], "zs_mesh_rays_image")
+    return _reprojection_record(tail[:4], tail[4:8], tail[8], tail[9], tail[10], depth_tol, tail[11], cell_edge, W)
+
+
+def reprojection(opt, var, meshes=None, depth_tol=None):
+    """mesh_reprojection for every mesh of the batch (``meshes``, default ``var.mesh_pred``) with sample b of
+    ``var.mask_input_map``, ``var.depth_pred`` and ``var.intr_pred`` (``var.intr`` when there is no prediction); (mean, scale)
+    come from camera.seen_surface on ``var.depth_pred``, as in vertex_colors.  ``depth_tol`` defaults to
+    default_color_depth_tol(opt); the record knows the marching-cubes cell edge.  Sets ``mesh.reprojection`` (the record) and
+    ``mesh.depth_map`` (the MeshDepthMap it was made from, on the device).  -> meshes."""
+    from . import camera
+    meshes = var.mesh_pred if meshes is None else meshes
+    intr = var.intr_pred if getattr(var, "intr_pred", None) is not None else var.intr
+    _, _, _, mean, scale = camera.seen_surface(opt, var.depth_pred, intr, var.mask_input_map)
+    depth_tol = default_color_depth_tol(opt) if depth_tol is None else depth_tol
+    for b, mesh in enumerate(meshes):
+        mask, depth = var.mask_input_map[b], var.depth_pred[b]
+        mesh.depth_map = mesh_depth_map(mesh, intr[b], mean[b], scale[b:b + 1], int(mask.shape[-2]), int(mask.shape[-1]))
+        mesh.reprojection = mesh_reprojection(mesh, mask, depth, intr[b], mean[b], scale[b:b + 1], depth_tol,
+                                              cell_edge=_mc_cell_edge(opt), depth_map=mesh.depth_map)
+    return meshes
+
+
+def reprojection_option(opt):
+    """Whether ``--eval.mesh_reprojection=true`` is set (opt-in, command line only: no yaml file carries it).  It scores the
+    prediction itself, so it needs no smoothing or simplification."""
+    return bool(opt.eval.get("mesh_reprojection", False))
+
+
 def mesh_report(mesh):
     """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
     per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``, a mesh that
@@ -2282,7 +2705,8 @@ def mesh_report(mesh):
     the component table beside it, what the clustering did to the surface), and a mesh that carries a ``deviation`` (a
     MeshDeviation, set by the pipelines under ``eval.mesh_deviation``) that record - with the six distances also in
     marching-cubes cells (``*_cells``) when the record knows the cell edge; a mesh that carries a ``volume_iou`` (a
-    MeshVolumeIoU, set by the pipelines under ``eval.mesh_iou``) that record."""
+    MeshVolumeIoU, set by the pipelines under ``eval.mesh_iou``) that record; a mesh that carries a ``reprojection`` (a
+    MeshReprojection, set by the pipelines under ``eval.mesh_reprojection``) that record."""
     comps = mesh.components
     report = dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
                   area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
@@ -2302,6 +2726,11 @@ def mesh_report(mesh):
         report["deviation"] = record
     if getattr(mesh, "volume_iou", None) is not None:
         report["volume_iou"] = mesh.volume_iou._asdict()
+    if getattr(mesh, "reprojection", None) is not None:
+        record = mesh.reprojection._asdict()
+        if record["depth_max_pixel"] is not None:
+            record["depth_max_pixel"] = list(record["depth_max_pixel"])
+        report["reprojection"] = record
     return report
 
 

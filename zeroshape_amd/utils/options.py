@@ -94,7 +94,8 @@ def load_options(fname):
 COMMAND_LINE_ONLY = ("eval.dump_results", "eval.min_component_area", "eval.drop_cavities", "eval.vertex_colors",
                      "eval.color_fade", "eval.color_min_cos", "eval.color_supersample", "eval.mesh_report",
                      "eval.smooth_iterations", "eval.smooth_lambda", "eval.smooth_mu", "eval.smooth_free_boundary",
-                     "eval.simplify_cells", "eval.simplify_position", "eval.mesh_deviation", "eval.mesh_iou")
+                     "eval.simplify_cells", "eval.simplify_position", "eval.mesh_deviation", "eval.mesh_iou",
+                     "eval.mesh_reprojection")
 
 
 def override_options(opt, opt_over, key_stack=None, safe_check=False):
