@@ -77,6 +77,13 @@ like <name>_depth_est.png, over the pixels the mesh covers), and with --eval.mes
 `reprojection` entry: the pixel counts and the silhouette IoU, max / mean / rms of |Z_mesh - depth| in camera units, mesh
 units and marching-cubes cells with the pixel at the maximum, the pixels that agree within the colour pass's depth tolerance,
 and the pixels whose first hit is a back face.  It is sampled at the pixel centres.
+
+--eval.mesh_self_intersections=true (opt-in, shape task; needs no smoothing or simplification: it scores the delivered mesh
+itself) finds the faces of the mesh that pass through each other (eval_3D.mesh_self_intersections, an exact face-against-face
+test on the GPU; Open3D's is_self_intersecting).  With --eval.mesh_report=true the report gains a `self_intersections` entry:
+crossing_pairs, faces_crossed, coincident_pairs (two faces on the same three corners: the one coplanar contact that is
+counted, apart from the crossings) and skipped_faces - and, when --eval.smooth_iterations or --eval.simplify_cells ran, the
+same four of the mesh before those steps under `before`: what they added.  Nothing is repaired.
 """
 import importlib
 import os

@@ -20,7 +20,10 @@ condition) records how much volume they added or removed (eval_3D.mesh_volume_io
 evaluation grid's lattice, on the GPU); the report then carries a `volume_iou` entry.  --eval.mesh_reprojection=true (no
 condition: it scores the prediction itself) casts the rays of the input camera at every predicted mesh on the GPU
 (eval_3D.reprojection) and compares the silhouette with the input mask and the first surface with the predicted depth; the
-report then carries a `reprojection` entry.
+report then carries a `reprojection` entry.  --eval.mesh_self_intersections=true (no condition either: it scores the delivered
+mesh) finds the faces of every predicted mesh that pass through each other, on the GPU (eval_3D.mesh_self_intersections); the
+report then carries a `self_intersections` entry, with the counts of the mesh before smoothing and simplification under
+`before` when such a step ran.
 
 ZS_VIRTUAL_RANKS=N (with ZS_DEVICE_OVERRIDE=0 ZS_DIST_BACKEND=gloo) rehearses the N-rank path on one GPU.
 """

@@ -688,6 +688,44 @@ int zs_mesh_rays_image(const float *vertices, const int *faces, int n_faces, int
                        signed char *out_side, int *out_counts, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Which faces of a triangle mesh pass through each other (csrc/mesh_selfx.hip; the semantics are
+ * eval_3D.mesh_self_intersections_host's, in every integer).  vertices [n_verts,3] fp32 and faces
+ * [n_faces,3] int32 are the weld's (zs_mesh_weld).  fp64 as written, from the fp32 corners of two
+ * valid faces i != j:
+ *   box     a candidate pair only if the fp32 boxes overlap on every axis, ends included.
+ *   det     det(D, L, H) = (Dx (Ly Hz - Lz Hy) + Dy (Lz Hx - Lx Hz)) + Dz (Lx Hy - Ly Hx).
+ *   segment (p, q) = its ends ordered lexicographically by their (x, y, z) values, against the face
+ *           (a, b, c): sp = det(a - p, b - p, c - p), sq = det(a - q, b - q, c - q) strictly of
+ *           opposite signs; D = q - p; for each directed edge u -> v of a -> b, b -> c, c -> a:
+ *           (lo, hi) = u, v ordered by value, e = det(D, lo - p, hi - p), negated when the face walks
+ *           hi -> lo; crosses iff the three e are all >= 0 or all <= 0 and not all 0.
+ *   cross   iff an edge of one crosses the other, either way round.  Touching, coplanar overlap and
+ *           the contact of faces that share a vertex or an edge are not crossings (sp = 0 exactly).
+ *   coincident  iff the three corner positions of one are those of the other in some order, by value
+ *           (either orientation): the one coplanar case that is counted, separately.
+ *   A face with an index outside [0, n_verts) or a corner that is not finite is skipped (no index is
+ *   used as an address before it is tested) and crosses nothing.
+ * out_face_counts [n_faces] int32: the number of other faces each face crosses (plain stores).
+ * out_pairs [capacity,2] int32 (may be NULL with capacity 0): the crossing pairs (i, j), i < j, in
+ * lexicographic order - the first `capacity` of them when there are more; rows beyond the total are
+ * not touched.
+ * out_counts[9] (device ints): skipped faces, status (|1 a corner that is not finite, |2 a face index
+ * outside the vertices), crossing pairs (i < j) as two 32-bit halves, low first, coincident pairs
+ * likewise, faces with a count > 0, and the ORDERED candidate pairs examined (every record read with
+ * j != i, before the box test; each face counts all j != i it crosses, so a pair is tested from both
+ * sides) as two halves.
+ * The search is the uniform grid of zs_mesh_distance (each face binned once, by the centre of its
+ * box; at most 64^3 cells) with the integer reaches of zs_mesh_winding through one monotone index
+ * function: the counts equal the test of all pairs.  The call only enqueues.
+ * scratch, 8-byte aligned: zs_mesh_self_intersections_scratch_bytes(n_faces, capacity) bytes (a
+ * multiple of 256; 0 for sizes outside the limits n_faces <= 2^24, capacity <= 2^30).  n_faces = 0 is
+ * an empty mesh: nine zeros.
+ * ------------------------------------------------------------------------- */
+size_t zs_mesh_self_intersections_scratch_bytes(int n_faces, int capacity);
+int zs_mesh_self_intersections(const float *vertices, const int *faces, int n_faces, int n_verts, int *out_face_counts,
+                               int *out_pairs, int capacity, int *out_counts, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Vertex normals from the occupancy field's own gradient (csrc/field_normals.hip; the gradient
  * itself is Implicit.field_gradient's, between the two calls).
  *   to_field_points : marching cubes scales a vertex at grid index u to v = min + u (max - min) / G

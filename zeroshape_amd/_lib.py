@@ -128,6 +128,8 @@ SIGNATURES = {
                      + [_c_void_p] * 7),
     "zs_mesh_rays_image": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int,
                                     _c_double, _c_double] + [_c_void_p] * 6),
+    "zs_mesh_self_intersections_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+    "zs_mesh_self_intersections": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int] + [_c_void_p] * 3),
     "zs_mesh_to_field_points":(_c_int, [_c_void_p, _c_size_t, _c_float, _c_int, _c_void_p, _c_void_p]),
     "zs_field_normals_finish": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
     "zs_mesh_stats_scratch_bytes": (_c_size_t, [_c_int]),

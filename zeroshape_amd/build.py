@@ -59,6 +59,8 @@ EXTRA = {
     "mesh_inside.hip": ["-ffp-contract=off"],
     # the fp64 sheared corners, edge functions and ray parameters equal, operation for operation, to the numpy restatement in utils/eval_3D.py (mesh_rays_host)
     "mesh_rays.hip": ["-ffp-contract=off"],
+    # the fp64 sides and edge functions equal, operation for operation, to the numpy restatement in utils/eval_3D.py (mesh_self_intersections_host)
+    "mesh_selfx.hip": ["-ffp-contract=off"],
 }
 
 

@@ -531,13 +531,16 @@ def _surface_clouds(opt, level_vox, seed=0):
     cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
     deviation_cell = _deviation_option(opt, smoothing, simplifying)
     iou_lattice = _iou_option(opt, smoothing, simplifying, G=level_vox.shape[1])
+    selfx = self_intersections_option(opt)
     for i in range(level_vox.shape[0]):
         if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(level_vox[i], 0.5, range_min, range_max, opt.eval.num_points, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
+            if selfx:                      # eval.mesh_self_intersections: the report's entry
+                _with_self_intersections(mesh)
         else:                              # eval.min_component_area / eval.drop_cavities, eval.smooth_*, eval.simplify_cells:
             tris, _ = extract_surface(level_vox[i], 0.5, range_min, range_max)          # sample the mesh that is delivered
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell, iou_lattice)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell, iou_lattice, selfx)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i)
         meshes.append(mesh)
         clouds.append(pts)
@@ -636,12 +639,14 @@ def _iou_option(opt, smoothing, simplifying, G=None):
     return G, float(np.float32((range_max - range_min) / G)), float(range_min)
 
 
-def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None, deviation_cell=None, iou_lattice=None):
+def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None, deviation_cell=None, iou_lattice=None, selfx=False):
     """The opt-in steps between marching cubes and sampling, in their order: filter_components, then smooth_mesh, then
     simplify_mesh - last, so that the colours, the sampled points and with them the metrics describe the mesh that is
     delivered.  With ``deviation_cell`` (_deviation_option) the delivered mesh gets ``deviation``: mesh_deviation against the
     mesh as it stood after filter_components - dropping floaters is intended and is not deviation.  With ``iou_lattice``
-    (_iou_option) it gets ``volume_iou``: mesh_volume_iou against the same mesh on that lattice."""
+    (_iou_option) it gets ``volume_iou``: mesh_volume_iou against the same mesh on that lattice.  With ``selfx``
+    (self_intersections_option) it gets its ``self_intersections`` and, when a smoothing or simplification step ran,
+    ``self_intersections_before``: the record of that same mesh (_with_self_intersections)."""
     if cleaning is not None:
         mesh = filter_components(mesh, *cleaning)
     reference = mesh
@@ -653,6 +658,8 @@ def _cleaned_and_smoothed(mesh, cleaning, smoothing, simplifying=None, deviation
         mesh.deviation = mesh_deviation(mesh, reference, cell_edge=deviation_cell)
     if iou_lattice is not None:
         mesh.volume_iou = mesh_volume_iou(mesh, reference, *iou_lattice)
+    if selfx:
+        _with_self_intersections(mesh, reference)
     return mesh
 
 
@@ -770,6 +777,8 @@ class SimpleMesh(object):
     choice among the parts.
     ``adjacency`` (a MeshAdjacency: the vertex neighbourhood as a CSR, boundary flags) and trimesh's ``vertex_neighbors``;
     smooth_mesh(mesh, ...) is the stand-in for ``trimesh.smoothing.filter_taubin`` / ``filter_laplacian``.
+    ``self_intersections`` (a MeshSelfIntersections: per face the number of other faces it crosses, the totals) and Open3D's
+    ``is_self_intersecting()`` / ``get_self_intersecting_triangles()``.
 
     Built from a GPU tensor the mesh stays in HBM: ``device_triangles`` is that tensor (the turntable renders from it),
     the weld and the normals come from weld_mesh (csrc/mesh_weld.hip) on first access, and ``triangles`` / ``vertices`` /
@@ -784,6 +793,7 @@ class SimpleMesh(object):
         self._device_weld = self.device_field_normals = self.field_normal_fallbacks = self._field_normals = None
         self._components = None                          # mesh_components(self), cached by the ``components`` property
         self._adjacency = None                           # mesh_adjacency(self), cached by the ``adjacency`` property
+        self._self_intersections = None                  # mesh_self_intersections(self), cached by ``self_intersections``
         # set by mesh_vertex_colors(): colours uint8 [V,3], seen flags uint8 [V], colour sources int32 [V] and (seen area, total
         # area) fp64 [2] on the device, and the host copies the properties below make when read
         self.device_vertex_colors = self.device_vertex_seen = self.device_color_source = self.device_seen_area = None
@@ -848,6 +858,27 @@ class SimpleMesh(object):
         if self._adjacency is None:
             self._adjacency = mesh_adjacency(self)
         return self._adjacency
+
+    @property
+    def self_intersections(self):
+        """mesh_self_intersections(self), computed once: for every face the number of other faces it crosses, and the counts
+        (a MeshSelfIntersections, on the device for a GPU mesh until ``check()`` reads the counts)."""
+        if self._self_intersections is None:
+            self._self_intersections = mesh_self_intersections(self)
+        return self._self_intersections
+
+    def is_self_intersecting(self):
+        """Open3D's name: whether two faces of this mesh cross (mesh_self_intersections_host's rule: touching, coplanar
+        overlap, coincident faces and the contact of neighbours do not count)."""
+        return self.self_intersections.check()["n_pairs"] > 0
+
+    def get_self_intersecting_triangles(self):
+        """Open3D's name: [n,2] int64 on the host, the crossing pairs of faces (i, j), i < j, in lexicographic order
+        (mesh_self_intersections(self, pairs=True): for a GPU mesh two calls with a read of the total in between)."""
+        found = mesh_self_intersections(self, pairs=True).pairs
+        if isinstance(found, torch.Tensor):
+            found = found.cpu().numpy()
+        return np.asarray(found, np.int64).reshape(-1, 2)
 
     def distance_to(self, points, closest=False):
         """mesh_distance(self, points, closest): the exact distance from ``points`` [M,3] to this surface - the nearest face and
@@ -2698,6 +2729,248 @@ def reprojection_option(opt):
     return bool(opt.eval.get("mesh_reprojection", False))
 
 
+# ---- which faces pass through each other (csrc/mesh_selfx.hip) ----
+
+
+class MeshSelfIntersections(collections.namedtuple("MeshSelfIntersections", "face_counts pairs counts")):
+    """What mesh_self_intersections returns: ``face_counts`` [F] (for every face the number of other faces it crosses),
+    ``pairs`` [n,2] (the crossing pairs (i, j), i < j, in lexicographic order - the first ``capacity`` of them when a capacity
+    was given, rows beyond the total left at -1; None unless asked for) and ``counts`` [9] int32: the faces that were skipped,
+    the status word, the crossing pairs as two 32-bit halves, the coincident pairs as two halves, the faces with a count > 0
+    and the ordered candidate pairs that were examined as two halves.  CUDA int32 tensors for a GPU mesh (nothing has been
+    read back), numpy arrays for a host mesh (int64 counts and pairs).  Coincident pairs - two faces on the same three
+    corner positions, either orientation - are the one coplanar contact that is counted, apart from the crossings; touching,
+    coplanar overlap and the contact of faces that share a vertex or an edge are neither.  Nothing is repaired."""
+    __slots__ = ()
+
+    def check(self):
+        """Reads ``counts`` (for a GPU mesh the one device-to-host copy, 36 bytes) -> dict(n_pairs, n_coincident,
+        n_faces_crossed, skipped_faces, status, examined, truncated: whether ``pairs`` holds fewer rows than there are
+        pairs).  ZeroShapeHipError when the status word says that a face index lay outside the vertices - a weld never makes
+        one."""
+        w = [int(v) & 0xffffffff for v in self.counts.tolist()]
+        if w[1] & MESH_DISTANCE_STATUS_INDEX:
+            from .. import _lib
+            raise _lib.ZeroShapeHipError("zs_mesh_self_intersections: status %d (a face index outside the vertices)" % w[1])
+        n_pairs = w[2] | (w[3] << 32)
+        return dict(n_pairs=n_pairs, n_coincident=w[4] | (w[5] << 32), n_faces_crossed=w[6], skipped_faces=w[0], status=w[1],
+                    examined=w[7] | (w[8] << 32), truncated=self.pairs is not None and int(self.pairs.shape[0]) < n_pairs)
+
+
+def _lex_before(u, v):
+    """u before v in the lexicographic order of the values (triples of component arrays)."""
+    return (u[0] < v[0]) | ((u[0] == v[0]) & ((u[1] < v[1]) | ((u[1] == v[1]) & (u[2] < v[2]))))
+
+
+def _choose3(first, u, v):
+    return tuple(np.where(first, u[k], v[k]) for k in range(3))
+
+
+def _det3(D, L, H):
+    return (D[0] * (L[1] * H[2] - L[2] * H[1]) + D[1] * (L[2] * H[0] - L[0] * H[2])) + D[2] * (L[0] * H[1] - L[1] * H[0])
+
+
+def _edges_cross_host(S, T):
+    """Whether an edge of the faces S crosses the faces T, row by row: S and T are triples of corners, each a triple of
+    float64 component arrays [N] - mesh_self_intersections_host's segment rule, operation for operation."""
+    a, b, c = T
+    side = [_det3(_sub3(a, x), _sub3(b, x), _sub3(c, x)) for x in S]
+    out = np.zeros(len(a[0]), bool)
+    for k0, k1 in ((0, 1), (1, 2), (2, 0)):
+        ss, st = side[k0], side[k1]
+        at = np.flatnonzero(((ss > 0.0) & (st < 0.0)) | ((ss < 0.0) & (st > 0.0)))
+        if len(at) == 0:
+            continue
+        s, t = tuple(x[at] for x in S[k0]), tuple(x[at] for x in S[k1])
+        fa, fb, fc = (tuple(x[at] for x in corner) for corner in T)
+        swap = _lex_before(t, s)
+        p, q = _choose3(swap, t, s), _choose3(swap, s, t)
+        D = _sub3(q, p)
+        e = []
+        for u, v in ((fa, fb), (fb, fc), (fc, fa)):
+            down = _lex_before(v, u)                                 # the face walks the edge hi -> lo
+            lo, hi = _choose3(down, v, u), _choose3(down, u, v)
+            value = _det3(D, _sub3(lo, p), _sub3(hi, p))
+            e.append(np.where(down, -value, value))
+        out[at] |= (((e[0] >= 0.0) & (e[1] >= 0.0) & (e[2] >= 0.0)) | ((e[0] <= 0.0) & (e[1] <= 0.0) & (e[2] <= 0.0))) & \
+            ~((e[0] == 0.0) & (e[1] == 0.0) & (e[2] == 0.0))
+    return out
+
+
+def mesh_self_intersections_host(vertices, faces, rows=None, pairs=False):
+    """The definition of mesh_self_intersections and the checker of zs_mesh_self_intersections, in numpy: every face of
+    ``rows`` (default: all) against every face of the indexed mesh ``vertices`` [V,3] float32, ``faces`` [F,3].  A face is
+    valid when its three indices lie inside the vertices and its corners are finite; the others are skipped, counted, and
+    cross nothing.  Everything is elementwise float64 in the order written, from the float32 corners of two valid faces
+    i != j:
+
+      candidates   only if the float32 boxes overlap on every axis, ends included: min_i <= max_j and min_j <= max_i.  The
+                   box test is part of the definition (as in mesh_winding_host), so pruning by boxes is exact by construction.
+      det(D, L, H) = (Dx (Ly Hz - Lz Hy) + Dy (Lz Hx - Lx Hz)) + Dz (Lx Hy - Ly Hx), mesh_winding_host's grouping.
+      a segment crosses the face (a, b, c): (p, q) = its ends ordered lexicographically by their (x, y, z) values;
+                   sp = det(a - p, b - p, c - p) and sq = det(a - q, b - q, c - q) strictly of opposite signs; D = q - p; for
+                   each directed edge u -> v of a -> b, b -> c, c -> a: (lo, hi) = u, v ordered by value,
+                   e = det(D, lo - p, hi - p), negated when the face walks hi -> lo; the three e all >= 0 or all <= 0, and
+                   not all three 0.
+      S, T cross   iff an edge of S crosses T or an edge of T crosses S (symmetric).
+      coincident   iff the three corner positions of S are those of T in some order, by value: either orientation, so a
+                   mirror twin is one coincident pair (the unordered triples are compared: the degenerate faces (a, a, b)
+                   and (a, b, b) are not coincident).
+
+    What follows: an end that equals a corner of the face makes a zero row, so its det is exactly 0 - faces that share a
+    vertex or an edge are never reported for that contact, on a soup, on any weld and with duplicated vertices alike, with no
+    special case; a face that pokes through a neighbour it shares one vertex with is still found, through the opposite edge.
+    Touching is not crossing (a vertex lying in another face has det 0), coplanar overlap and a coplanar fold across a shared
+    edge are not crossing (every det 0): coincident pairs are the one coplanar case that is counted, separately.  A face of
+    zero area has a plane that nothing crosses, but its edges can cross others.  An edge function depends on the segment and
+    the ordered edge alone, so the two faces at an edge compute exact negatives: a segment through a shared edge crosses at
+    least one of them.
+    -> (face_counts [R] int64: for every row the number of other faces it crosses; pairs [n,2] int64, the crossing (i, j)
+    with i in ``rows`` and j > i in lexicographic order - all crossing pairs for the default rows - or None; a dict:
+    crossing_pairs and coincident_pairs (both over i in ``rows``, j > i), faces_crossed (rows with a count > 0),
+    skipped_faces and status (the whole mesh), candidates (the (i, j), i in ``rows``, j != i, whose boxes overlap) and
+    brute_force (the ordered pairs of a row with another valid face))."""
+    v32 = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    valid, status = _valid_faces(v32, f)
+    F = len(f)
+    rows = np.arange(F, dtype=np.int64) if rows is None else np.asarray(rows, np.int64).reshape(-1)
+    corners = np.zeros((F, 3, 3), np.float32)
+    corners[valid] = v32[f[valid]]
+    mn, mx = corners.min(axis=1), corners.max(axis=1)
+    index = np.flatnonzero(valid)
+    face_counts = np.zeros(len(rows), np.int64)
+    found, n_coincident, n_candidates = [], 0, 0
+    # only to be quick: the valid faces and the rows in the order of their box minimum along x.  The rows of a chunk then
+    # see the faces whose minimum lies in [smallest minimum of the chunk - widest box, largest maximum of the chunk]: a face
+    # outside begins beyond every row's end or ends before every row's beginning.  The box test below decides.
+    index = index[np.argsort(mn[index, 0], kind="stable")]
+    start_x = mn[index, 0].astype(np.float64)
+    widest = float((mx[index, 0].astype(np.float64) - start_x).max()) * (1.0 + 2.0 ** -40) if len(index) else 0.0   # (rounding)
+    order = np.flatnonzero(valid[rows])
+    order = order[np.argsort(mn[rows[order], 0], kind="stable")]                         # positions in rows
+    chunk = 512
+    with np.errstate(over="ignore", invalid="ignore"):
+        for r0 in range(0, len(order), chunk):
+            where = order[r0:r0 + chunk]
+            r = rows[where]
+            j0 = np.searchsorted(start_x, float(mn[r, 0].min()) - widest, side="left")
+            j1 = np.searchsorted(start_x, float(mx[r, 0].max()), side="right")
+            window = index[j0:j1]
+            near = (mn[r, None, 0] <= mx[None, window, 0]) & (mn[None, window, 0] <= mx[r, None, 0])
+            ri, jj = np.nonzero(near)
+            i, j = r[ri], window[jj]
+            keep = i != j
+            for k in (1, 2):
+                keep &= (mn[i, k] <= mx[j, k]) & (mn[j, k] <= mx[i, k])
+            ri, i, j = ri[keep], i[keep], j[keep]
+            n_candidates += len(i)
+            S64, T64 = corners[i].astype(np.float64), corners[j].astype(np.float64)
+            S = tuple(tuple(S64[:, c, k] for k in range(3)) for c in range(3))
+            T = tuple(tuple(T64[:, c, k] for k in range(3)) for c in range(3))
+            crossing = _edges_cross_host(S, T) | _edges_cross_host(T, S)
+            m = np.all(S64[:, :, None, :] == T64[:, None, :, :], axis=3)                 # [N, corner of S, corner of T]
+            twins = np.zeros(len(i), bool)
+            for perm in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+                twins |= m[:, 0, perm[0]] & m[:, 1, perm[1]] & m[:, 2, perm[2]]
+            n_coincident += int((twins & (j > i)).sum())
+            face_counts += np.bincount(where[ri[crossing]], minlength=len(rows))
+            above = crossing & (j > i)
+            found.append(np.stack([i[above], j[above]], axis=1))
+    found = np.concatenate(found) if found else np.zeros((0, 2), np.int64)
+    found = found[np.lexsort((found[:, 1], found[:, 0]))]
+    n_rows_valid = int(valid[rows].sum())
+    record = dict(crossing_pairs=len(found), coincident_pairs=n_coincident, faces_crossed=int((face_counts > 0).sum()),
+                  skipped_faces=int(F - len(index)), status=int(status), candidates=int(n_candidates),
+                  brute_force=n_rows_valid * max(len(index) - 1, 0))
+    return face_counts, (found if pairs else None), record
+
+
+def _check_capacity(capacity):
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0):
+        raise ValueError("mesh_self_intersections: capacity must be an integer >= 0 or None, got %r" % (capacity,))
+
+
+@torch.no_grad()
+def mesh_self_intersections(mesh, pairs=False, capacity=None):
+    """Open3D's ``is_self_intersecting`` / ``get_self_intersecting_triangles``: which faces of ``mesh`` (a SimpleMesh) pass
+    through each other -> a MeshSelfIntersections: per face the number of other faces it crosses, with ``pairs`` the
+    crossing pairs (i, j), i < j, in lexicographic order, and the counts.  The semantics are mesh_self_intersections_host's:
+    float64 arithmetic on the float32 corners, boxes that overlap as part of the definition, strict sides - touching,
+    coplanar overlap and the contact of neighbours are not crossings; coincident pairs are counted apart.
+    A GPU mesh is searched on the device (zs_mesh_self_intersections: a uniform grid over the faces read through integer
+    reaches that skip no candidate - the counts of the test of all pairs) on the weld it carries or, if it has none yet, on
+    one weld_mesh call whose result it then keeps; the results are CUDA tensors and nothing is read back:
+    ``MeshSelfIntersections.check()`` reads the counts.  With ``capacity`` the pair list has that many rows (the first ones;
+    rows beyond the total stay -1; ``check()["truncated"]`` says whether some are missing).  With ``pairs`` and NO capacity
+    the call SYNCHRONISES: one counting call, a read of the 8-byte total, then the call that writes exactly that many rows.
+    A host mesh goes through the numpy checker."""
+    _check_capacity(capacity)
+    want_pairs = bool(pairs) or capacity is not None
+    if getattr(mesh, "device_triangles", None) is None:
+        face_counts, found, rec = mesh_self_intersections_host(mesh.vertices, mesh.faces, pairs=True)
+        examined = rec["brute_force"]
+        words = [rec["skipped_faces"], rec["status"], rec["crossing_pairs"] & 0xffffffff, rec["crossing_pairs"] >> 32,
+                 rec["coincident_pairs"] & 0xffffffff, rec["coincident_pairs"] >> 32, rec["faces_crossed"],
+                 examined & 0xffffffff, examined >> 32]
+        counts = np.array(words, np.int64).astype(np.uint32).view(np.int32)
+        if capacity is not None:
+            rows = np.full((int(capacity), 2), -1, np.int64)
+            rows[:min(int(capacity), len(found))] = found[:int(capacity)]
+            found = rows
+        return MeshSelfIntersections(face_counts, found if want_pairs else None, counts)
+    from .. import _lib
+    lib = _lib.load()
+    vertices, faces = _device_weld_of(mesh)
+    dev = vertices.device
+    n, n_verts = faces.shape[0], vertices.shape[0]
+    face_counts = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.zeros(9, dtype=torch.int32, device=dev)
+
+    def call(rows, cap):
+        nbytes = lib.zs_mesh_self_intersections_scratch_bytes(n, cap)
+        if nbytes == 0:
+            raise _lib.ZeroShapeHipError("mesh_self_intersections: %d faces and a capacity of %d exceed the kernels' limits" % (n, cap))
+        scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+        with _lib.on(dev):
+            _lib.check(lib.zs_mesh_self_intersections(_lib.ptr(vertices), _lib.ptr(faces), n, n_verts, _lib.ptr(face_counts),
+                                                      _lib.ptr(rows), cap, _lib.ptr(counts), _lib.ptr(scratch),
+                                                      _lib.current_stream_ptr(dev)), "zs_mesh_self_intersections")
+
+    if not want_pairs:
+        call(None, 0)
+        return MeshSelfIntersections(face_counts, None, counts)
+    if capacity is None:
+        call(None, 0)
+        lo, hi = (int(v) & 0xffffffff for v in counts[2:4].tolist())                     # the one read in between: 8 bytes
+        capacity = lo | (hi << 32)
+    rows = torch.full((int(capacity), 2), -1, dtype=torch.int32, device=dev)
+    call(rows if capacity > 0 else None, int(capacity))
+    return MeshSelfIntersections(face_counts, rows, counts)
+
+
+def self_intersections_option(opt):
+    """Whether ``--eval.mesh_self_intersections=true`` is set (opt-in, command line only: no yaml file carries it).  It
+    scores the delivered mesh itself, so it needs no smoothing or simplification."""
+    return bool(opt.eval.get("mesh_self_intersections", False))
+
+
+def _with_self_intersections(mesh, reference=None):
+    """``eval.mesh_self_intersections``: the delivered mesh gets its ``self_intersections`` (computed here, kept) and - where a
+    smoothing or simplification step made it from ``reference``, the mesh as it stood after filter_components -
+    ``self_intersections_before``, the record of that mesh: what the steps added.  -> mesh."""
+    if reference is not None and reference is not mesh:
+        mesh.self_intersections_before = reference.self_intersections
+    mesh.self_intersections                              # (the property computes the record and keeps it)
+    return mesh
+
+
+def _self_intersections_record(done):
+    c = done.check()
+    return dict(crossing_pairs=c["n_pairs"], faces_crossed=c["n_faces_crossed"], coincident_pairs=c["n_coincident"],
+                skipped_faces=c["skipped_faces"])
+
+
 def mesh_report(mesh):
     """What demo.py's ``--eval.mesh_report=true`` stores as JSON: the totals of a SimpleMesh (trimesh's names) and its
     per-component table; a mesh that mesh_vertex_colors coloured also reports its ``seen_area_fraction``, a mesh that
@@ -2706,7 +2979,10 @@ def mesh_report(mesh):
     MeshDeviation, set by the pipelines under ``eval.mesh_deviation``) that record - with the six distances also in
     marching-cubes cells (``*_cells``) when the record knows the cell edge; a mesh that carries a ``volume_iou`` (a
     MeshVolumeIoU, set by the pipelines under ``eval.mesh_iou``) that record; a mesh that carries a ``reprojection`` (a
-    MeshReprojection, set by the pipelines under ``eval.mesh_reprojection``) that record."""
+    MeshReprojection, set by the pipelines under ``eval.mesh_reprojection``) that record; a mesh whose ``self_intersections``
+    the pipelines computed under ``eval.mesh_self_intersections`` the entry ``self_intersections``: crossing_pairs,
+    faces_crossed, coincident_pairs (the one coplanar contact that is counted, apart from the crossings) and skipped_faces,
+    with the same four of the mesh before smoothing and simplification under ``before`` when such a step ran."""
     comps = mesh.components
     report = dict(vertices=int(comps.vertices.sum()), faces=int(comps.faces.sum()), components=comps.n_components,
                   area=mesh.area, volume=mesh.volume, euler_number=mesh.euler_number, is_watertight=mesh.is_watertight,
@@ -2731,6 +3007,11 @@ def mesh_report(mesh):
         if record["depth_max_pixel"] is not None:
             record["depth_max_pixel"] = list(record["depth_max_pixel"])
         report["reprojection"] = record
+    if getattr(mesh, "_self_intersections", None) is not None:
+        record = _self_intersections_record(mesh._self_intersections)
+        if getattr(mesh, "self_intersections_before", None) is not None:
+            record["before"] = _self_intersections_record(mesh.self_intersections_before)
+        report["self_intersections"] = record
     return report
 
 
@@ -3081,7 +3362,8 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
     sampled on what comes out: the metrics describe the mesh that is delivered.  With ``opt.eval.mesh_deviation`` (opt-in,
     _deviation_option) that mesh carries ``deviation``: how far the smoothing and the simplification moved the surface; with
     ``opt.eval.mesh_iou`` (opt-in, _iou_option) it carries ``volume_iou``: how much volume they added or removed, counted on
-    the level grid's own marching-cubes lattice."""
+    the level grid's own marching-cubes lattice; with ``opt.eval.mesh_self_intersections`` (opt-in,
+    self_intersections_option) it carries ``self_intersections``: which of its faces pass through each other."""
     device = getattr(opt, "device", "cuda")
     meshes, clouds = [], []
     for i, g in enumerate(level_grids):
@@ -3092,13 +3374,16 @@ def convert_to_explicit(opt, level_grids, isoval=0., to_pointcloud=False, seed=0
         cleaning, smoothing, simplifying = _component_options(opt), _smooth_options(opt), _simplify_options(opt)
         deviation_cell = _deviation_option(opt, smoothing, simplifying)
         iou_lattice = _iou_option(opt, smoothing, simplifying, G=vol.shape[0])
+        selfx = self_intersections_option(opt)
         if cleaning is None and smoothing is None and simplifying is None:
             tris, pts = extract_surface(vol, isoval, range_min, range_max,
                                         opt.eval.num_points if to_pointcloud else 0, seed + i)
             mesh = SimpleMesh(tris)                      # stays in HBM until a dump reads it
+            if selfx:
+                _with_self_intersections(mesh)
         else:                   # marching cubes, filter_components, smooth_mesh, simplify_mesh, then sampling with the same seed
             tris, _ = extract_surface(vol, isoval, range_min, range_max)
-            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell, iou_lattice)
+            mesh = _cleaned_and_smoothed(SimpleMesh(tris), cleaning, smoothing, simplifying, deviation_cell, iou_lattice, selfx)
             pts = sample_surface(mesh.device_triangles, opt.eval.num_points, seed + i) if to_pointcloud else None
         meshes.append(mesh)
         if to_pointcloud:

@@ -95,7 +95,7 @@ COMMAND_LINE_ONLY = ("eval.dump_results", "eval.min_component_area", "eval.drop_
                      "eval.color_fade", "eval.color_min_cos", "eval.color_supersample", "eval.mesh_report",
                      "eval.smooth_iterations", "eval.smooth_lambda", "eval.smooth_mu", "eval.smooth_free_boundary",
                      "eval.simplify_cells", "eval.simplify_position", "eval.mesh_deviation", "eval.mesh_iou",
-                     "eval.mesh_reprojection")
+                     "eval.mesh_reprojection", "eval.mesh_self_intersections")
 
 
 def override_options(opt, opt_over, key_stack=None, safe_check=False):
