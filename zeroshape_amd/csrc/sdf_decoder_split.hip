@@ -29,11 +29,12 @@
 //    One raw s_barrier per chunk (AStream below).  Ordering rules: cdna_hip_programming.md
 //    section 5 (counted vmcnt by the issuing wave, then a barrier the reader has passed; restage
 //    after an lgkmcnt-retired read + barrier).
-//  * LDS: [params window 16 KiB][A staging 2 x 16 KiB][4 x 28 KiB activation slabs] = 160 KiB
-//    (tile 7 of a slab-resident array lives in registers).  Params are paged in five windows
-//    per tile instead of two.  The slab holds what a GEMM re-reads as B operands per output
-//    tile: LN1's output (q, k, v) and the odd layers' inputs of impl_mlp.  LN2's output (fc1) and
-//    the even layers' inputs stay in registers (LN2 IN REGISTERS below).
+//  * LDS: [params window 16 KiB][A staging 2 x 16 KiB][4 x 28 KiB activation slabs] = 160 KiB.
+//    Params are paged in five windows per tile instead of two.  The slab holds the one array a
+//    GEMM still re-reads from LDS as B operands per output tile: LN1's output (q, k, v), tiles
+//    0..5 of it (24 of its 28 KiB; tiles 6 and 7 live in registers).  LN2's output (fc1) and both
+//    activation arrays of impl_mlp stay in registers (LN2 IN REGISTERS, IMPL_MLP IN REGISTERS
+//    below).
 //  * No asm register ring: LDS reads and MFMAs are builtins, scheduled and hazard-padded by
 //    hipcc (VGPR-form accumulators: -mllvm -amdgpu-mfma-vgpr-form, zeroshape_amd/build.py); only
 //    the DMA, the barrier and the prefetch pin are asm.
@@ -74,8 +75,22 @@ constexpr int NBUF = 2;
 constexpr int KB_TOTAL = G_TOTAL / 2;               // 4,928 K-blocks = 14,784 MFMAs per wave tile
 constexpr int PRM_WINDOW = 4096;                    // floats of params resident in LDS at a time
 constexpr int STAGE_FLOATS = NBUF * CHUNK_BYTES / 4;
-constexpr int SLAB_TILES = NT - 1;                  // tiles of an activation array kept in LDS (the last: registers)
+// IMPL_MLP IN REGISTERS (below) and LN2 IN REGISTERS leave the slab one user, LN1's output; -DZS_SPLIT_IMPL_SLAB and
+// -DZS_SPLIT_LN_SLAB build the forms before them (for A/B runs of two libraries: nothing selects them at run time)
+#ifndef ZS_SPLIT_IMPL_SLAB
+constexpr bool IMPL_REGS = true;
+#else
+constexpr bool IMPL_REGS = false;
+#endif
+#ifndef ZS_SPLIT_LN_SLAB
+constexpr bool LN2_REGS = true;
+#else
+constexpr bool LN2_REGS = false;
+#endif
+constexpr int SLAB_TILES = NT - 1;                  // tiles of an activation array the LDS has room for
 constexpr int SLAB_U4 = SLAB_TILES * 4 * 64;        // ... as packed (hi, lo) K-blocks: 28 KiB per wave
+// tiles actually kept there, the others in registers: with q/k/v the only reader the registers hold tile 6 as well
+constexpr int SLAB_USED = IMPL_REGS && LN2_REGS ? SLAB_TILES - 1 : SLAB_TILES;
 constexpr int ZTILES_F4 = NT * 4 * 64;              // one skip layer's fp32 feat partial products (workspace)
 static_assert(ZSLAB_F4 == 3 * ZTILES_F4, "the workspace slab holds three skip layers' feat partial products");
 static_assert(B0_TABLE_FLOATS == PRM_WINDOW, "block0_window_kernel / block0_stream_kernel index an image's table by PRM_WINDOW");
@@ -219,14 +234,14 @@ struct AStream {
     DEV void drain() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 };
 
-// The LDS-resident activation array of a wave: tiles 0..6 in the slab, tile 7 in registers (those
+// The LDS-resident activation array of a wave: tiles 0..SLAB_USED-1 in the slab, the others in registers (tile 7's
 // 4 KiB per wave are what lets the staging buffers hold 8 K-blocks, i.e. half the barriers).
 struct Slab {
     u32x4 *fl;  // this lane's view: [(tile * 4 + j * 2 + hl) * 64]
-    PT t7;
+    PT tr[NT - SLAB_USED];
     DEV void store(int tile, const PT &p) {
-        if (tile == SLAB_TILES) {
-            t7 = p;
+        if (tile >= SLAB_USED) {
+            tr[tile - SLAB_USED] = p;
         } else {
 #pragma unroll
             for (int q = 0; q < 4; q++) fl[(tile * 4 + q) * 64] = p.v[q];
@@ -380,28 +395,30 @@ DEV float NAME(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi
 ZS_KBLOCK_GELU(kblock_gelu, "v", "")
 ZS_KBLOCK_GELU(kblock_gelu_breg, "a", "s_nop 1\n\t")
 #undef ZS_KBLOCK_GELU
-#undef ZS_KBLOCK_MFMA_LO_HI
 // softplus100: 1 plain + exp | 2 plain + log | 1 plain
-DEV float kblock_softplus(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi, const u32x4 &blo, float x) {
-    float t, m;
-    const float c0 = -144.26950408889634074f;
-    asm volatile(
-#ifndef ZS_EXP_TWO_TERM
-                 "v_mfma_f32_32x32x16_f16 %[acc], %[alo], %[bh], %[acc]\n\t"
-#endif
-                 "v_mul_f32_e64 %[t], |%[x]|, %[c0]\n\t"
-                 "v_exp_f32_e32 %[t], %[t]\n\t"
-                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bl], %[acc]\n\t"
-                 "v_max_f32_e32 %[m], 0, %[x]\n\t"
-                 "v_add_f32_e32 %[t], 1.0, %[t]\n\t"
-                 "v_log_f32_e32 %[t], %[t]\n\t"
-                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bh], %[acc]\n\t"
-                 "s_nop 0\n\t"
-                 "v_fmac_f32_e32 %[m], 0x3be32166, %[t]"
-                 : [acc] "+v"(acc), [t] "=&v"(t), [m] "=&v"(m)
-                 : [alo] "v"(alo), [ahi] "v"(ahi), [bh] "v"(bhi), [bl] "v"(blo), [x] "v"(x), [c0] "s"(c0));
-    return m;
+#define ZS_KBLOCK_SOFTPLUS(NAME, BREG, LEAD) \
+DEV float NAME(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4 &bhi, const u32x4 &blo, float x) {             \
+    float t, m;                                                                                                            \
+    const float c0 = -144.26950408889634074f;                                                                              \
+    asm volatile(                                                                                                          \
+                 LEAD ZS_KBLOCK_MFMA_LO_HI                                                                                 \
+                 "v_mul_f32_e64 %[t], |%[x]|, %[c0]\n\t"                                                                   \
+                 "v_exp_f32_e32 %[t], %[t]\n\t"                                                                            \
+                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bl], %[acc]\n\t"                                               \
+                 "v_max_f32_e32 %[m], 0, %[x]\n\t"                                                                         \
+                 "v_add_f32_e32 %[t], 1.0, %[t]\n\t"                                                                       \
+                 "v_log_f32_e32 %[t], %[t]\n\t"                                                                            \
+                 "v_mfma_f32_32x32x16_f16 %[acc], %[ahi], %[bh], %[acc]\n\t"                                               \
+                 "s_nop 0\n\t"                                                                                             \
+                 "v_fmac_f32_e32 %[m], 0x3be32166, %[t]"                                                                   \
+                 : [acc] "+v"(acc), [t] "=&v"(t), [m] "=&v"(m)                                                             \
+                 : [alo] "v"(alo), [ahi] "v"(ahi), [bh] BREG(bhi), [bl] BREG(blo), [x] "v"(x), [c0] "s"(c0));              \
+    return m;                                                                                                              \
 }
+ZS_KBLOCK_SOFTPLUS(kblock_softplus, "v", "")
+ZS_KBLOCK_SOFTPLUS(kblock_softplus_breg, "a", "s_nop 1\n\t")
+#undef ZS_KBLOCK_SOFTPLUS
+#undef ZS_KBLOCK_MFMA_LO_HI
 
 // The asm K-blocks hide their MFMAs from hipcc, which therefore pads no wait states between the last of them and a VALU
 // read of the accumulator (the result of an 8-pass MFMA may be read 12 wait states after its issue; hipcc placed such a
@@ -443,7 +460,9 @@ DEV void mfma3_breg(f32x16 &acc, const u32x4 &ahi, const u32x4 &alo, const u32x4
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(ahi), "a"(bhi));
     side(kb, 2);
 }
-template <int KT, typename SIDE = NoSide>
+// VT: tiles 0..VT-1 of X are NOT pinned there - hipcc keeps them where it likes, the MFMAs take them from VGPRs
+// (impl_mlp's second array: the accumulator half has no room for all of it, IMPL_MLP IN REGISTERS below)
+template <int KT, int VT = 0, typename SIDE = NoSide>
 DEV void gemm_areg(AStream &s, const PT *X, f32x16 &acc, SIDE side = SIDE()) {  // starts chunk-aligned
 #pragma unroll
     for (int kt = 0; kt < KT; kt++)
@@ -452,7 +471,10 @@ DEV void gemm_areg(AStream &s, const PT *X, f32x16 &acc, SIDE side = SIDE()) {  
             u32x4 ahi, alo;
             s.step((kt * 2 + j) & (CK - 1), ahi, alo);
             pin(ahi, alo);
-            mfma3_breg(acc, ahi, alo, X[kt].v[2 * j], X[kt].v[2 * j + 1], kt * 2 + j, side);
+            if (kt < VT)
+                mfma3_gaps(acc, ahi, alo, X[kt].v[2 * j], X[kt].v[2 * j + 1], kt * 2 + j, side);
+            else
+                mfma3_breg(acc, ahi, alo, X[kt].v[2 * j], X[kt].v[2 * j + 1], kt * 2 + j, side);
         }
 }
 // ... with the ACCUMULATOR pinned in the accumulator half of the register file: the residual stream
@@ -487,11 +509,11 @@ DEV void gemm_one(AStream &s, const PT &X, f32x16 &acc, int pos0, int kb0 = 0, S
 }
 // 8 input tiles with the B operands read from the wave's LDS slab ([k-block][hi | lo][lane]),
 // one K-block ahead of their use
-// B operand of K-block kb of the slab-resident array (tile 7 lives in registers)
+// B operand of K-block kb of the slab-resident array (tiles SLAB_USED.. live in registers)
 DEV void slab_b(const Slab &sl, int kb, u32x4 &bh, u32x4 &bl) {
-    if (kb >= SLAB_TILES * 2) {
-        bh = sl.t7.v[(kb & 1) * 2];
-        bl = sl.t7.v[(kb & 1) * 2 + 1];
+    if (kb >= SLAB_USED * 2) {
+        bh = sl.tr[(kb >> 1) - SLAB_USED].v[(kb & 1) * 2];
+        bl = sl.tr[(kb >> 1) - SLAB_USED].v[(kb & 1) * 2 + 1];
     } else {
         bh = sl.fl[kb * KB_U4];
         bl = sl.fl[kb * KB_U4 + 64];
@@ -549,9 +571,9 @@ DEV void gemm_reg_act(AStream &s, const PT *X, f32x16 &acc, const f32x16 &cur, F
             tail(kb);
         }
 }
-// gemm_areg with the GELU of cur[kb] in the gaps of K-block kb
-template <typename FIN, typename TAIL>
-DEV void gemm_areg_gelu(AStream &s, const PT *X, f32x16 &acc, const f32x16 &cur, FIN fin, TAIL tail) {
+// gemm_areg with the activation ACT of cur[kb] in the gaps of K-block kb
+template <int ACT, int VT = 0, typename FIN, typename TAIL>
+DEV void gemm_areg_act(AStream &s, const PT *X, f32x16 &acc, const f32x16 &cur, FIN fin, TAIL tail) {
 #pragma unroll
     for (int kt = 0; kt < NT; kt++)
 #pragma unroll
@@ -559,7 +581,10 @@ DEV void gemm_areg_gelu(AStream &s, const PT *X, f32x16 &acc, const f32x16 &cur,
             u32x4 ahi, alo;
             const int kb = kt * 2 + j;
             s.step(kb & (CK - 1), ahi, alo);
-            const float r = kblock_gelu_breg(acc, ahi, alo, X[kt].v[2 * j], X[kt].v[2 * j + 1], cur[kb]);
+            const u32x4 &bh = X[kt].v[2 * j], &bl = X[kt].v[2 * j + 1];
+            const float r = kt < VT ? (ACT == 0 ? kblock_gelu(acc, ahi, alo, bh, bl, cur[kb]) : kblock_softplus(acc, ahi, alo, bh, bl, cur[kb]))
+                                    : (ACT == 0 ? kblock_gelu_breg(acc, ahi, alo, bh, bl, cur[kb])
+                                                : kblock_softplus_breg(acc, ahi, alo, bh, bl, cur[kb]));
             fin(kb, r);
             tail(kb);
         }
@@ -768,11 +793,6 @@ DEV void layer_norm_lds(const f32x16 *x, Slab &sl, const float *prm, int g_off, 
 // reach every accumulator in the same order: bit-identical results.  LN1's output (q, k, v: 24 passes in block 1) stays in
 // the slab: with it in registers, or only its tiles 4-7, hipcc spills (DESIGN 3b.4 has the numbers).
 // -DZS_SPLIT_LN_SLAB builds the slab form (for A/B runs of two libraries: nothing selects it at run time).
-#ifndef ZS_SPLIT_LN_SLAB
-constexpr bool LN2_REGS = true;
-#else
-constexpr bool LN2_REGS = false;
-#endif
 // layer_norm_lds with the eight packed tiles returned in xn
 DEV void layer_norm_reg(const f32x16 *x, PT *xn, const float *prm, int g_off, int b_off, int hi) {
     float mean, rstd;
@@ -1053,7 +1073,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
             auto fin = [&](int kb, float r) { e.feed(kb, r); };
             auto tail = [&](int kb) { if ((kb & 3) == 1) bi.step(kb & ~3); };
             if constexpr (LN2_REGS)
-                gemm_areg_gelu(s, xn, nxt, hid, fin, tail);
+                gemm_areg_act<0>(s, xn, nxt, hid, fin, tail);
             else
                 gemm_lds_act<0>(s, sl, nxt, hid, fin, tail);
 #pragma unroll
@@ -1086,9 +1106,47 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
         }
     }
     ZS_STAMP(10);
+    // IMPL_MLP IN REGISTERS.  The layers of impl_mlp alternate between two packed activation arrays: the even layers (0 and
+    // the skip layers 2, 4, 6) read hp and write hq, the odd layers read hq and write hp.  hq used to be the wave's slab -
+    // every output tile of an odd layer re-read its 14 K-blocks with two ds_read_b128 each, 896 reads and 112 stores per
+    // wave tile.  The residual stream y is dead here, so hq stays in registers beside hp and feat / sqrt(2) (fp): tiles
+    // IMPL_VT..7 pinned in the accumulator half like fp (mfma3_breg, kblock_softplus_breg), tiles 0..IMPL_VT-1 left to
+    // hipcc, which keeps them in VGPRs - fp and all of hq fill the 256 AGPRs, and the values that live across the whole
+    // tile, which hipcc parks there in this phase, then go to scratch (DESIGN 3b.5 has the forms tried).  For the same
+    // reason fp is packed in front of layer 0 and not behind it: feat in fp32 (128 registers) is dead before hq fills.
+    // The same values reach every accumulator in the same order: bit-identical results.
+    constexpr int IMPL_VT = 2;
     PT hp[NT];
+    PT hq[NT];  // IMPL_REGS
+    const float rsqrt2 = 0.70710678118654752440f;
+    PT fp[NT];
+    auto make_fp = [&]() {
+#pragma unroll
+        for (int kt = 0; kt < NT; kt++) {
+            float t[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) t[r] = h[kt * 16 + r] * rsqrt2;
+            fp[kt] = pack_tile(t);
+            if constexpr (IMPL_REGS) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) asm volatile("" : "+a"(fp[kt].v[q]));
+            }
+        }
+    };
+    if constexpr (IMPL_REGS) make_fp();
+    auto to_odd = [&](int tile, const PT &p) {   // an even layer's packed output tile -> the odd layers' input array
+        if constexpr (IMPL_REGS) {
+            hq[tile] = p;
+            if (tile >= IMPL_VT) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) asm volatile("" : "+a"(hq[tile].v[q]));
+            }
+        } else {
+            sl.store(tile, p);
+        }
+    };
 
-    // impl_mlp (implicit.py:168-184): inputs = cat[xyz, feat].  Layer 0: feat (regs) -> LDS
+    // impl_mlp (implicit.py:168-184): inputs = cat[xyz, feat].  Layer 0: feat (hp) -> hq
 #pragma unroll
     for (int kt = 0; kt < NT; kt++) hp[kt] = pack_tile(h + kt * 16);
     // (software pipeline over the output tiles: tile nt's GEMM carries tile nt-1's activation)
@@ -1107,13 +1165,13 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                                     [&](int kb) { if (nt + 1 < NT) ini.step(kb, px, py, pz); });
                 else
                     gemm_reg<NT, 0>(s, hp, acc, [&](int kb, int g) { if (g == 2) ini.step(kb, px, py, pz); });
-                if (nt > 0) sl.store(nt - 1, e.p);
+                if (nt > 0) to_odd(nt - 1, e.p);
                 prev = acc;
             } else {
                 mfma_settle(prev);
 #pragma unroll
                 for (int kb = 0; kb < 16; kb++) e.feed(kb, softplus100(prev[kb]));
-                sl.store(nt - 1, e.p);
+                to_odd(nt - 1, e.p);
             }
         }
     }
@@ -1123,19 +1181,11 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
     // K-blocks per output tile - the split stream interleaves [x part | feat part] per tile
     // (split_source_kblock) - so nothing is parked in memory (round 1 parked 96 KiB of fp32
     // partial products per wave tile: 12.8 GB per 129^3 launch)
-    const float rsqrt2 = 0.70710678118654752440f;
-    PT fp[NT];
-#pragma unroll
-    for (int kt = 0; kt < NT; kt++) {
-        float t[16];
-#pragma unroll
-        for (int r = 0; r < 16; r++) t[r] = h[kt * 16 + r] * rsqrt2;
-        fp[kt] = pack_tile(t);
-    }
+    if constexpr (!IMPL_REGS) make_fp();
     const float sx = px * rsqrt2, sy = py * rsqrt2, sz = pz * rsqrt2;
 
     ZS_STAMP(12);
-    // layer 1 (plain): LDS -> registers, pre-divided by sqrt(2) because layer 2 is a skip layer
+    // layer 1 (plain): hq -> hp, pre-divided by sqrt(2) because layer 2 is a skip layer
     {
         f32x16 prev;
         RowInit ini;
@@ -1146,11 +1196,22 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
             if (nt < NT) {
                 f32x16 acc = ini.v;
                 if (nt + 1 < NT) ini.start(prm, P_IMPL1 - W_IA, nt + 1, hi);
-                if (nt > 0)
-                    gemm_lds_act<1>(s, sl, acc, prev, [&](int kb, float r) { e.feed(kb, r * rsqrt2); },
-                                    [&](int kb) { if (nt + 1 < NT) ini.step(kb); });
-                else
-                    gemm_lds(s, sl, acc, 0, [&](int kb, int g) { if (g == 2) ini.step(kb); });
+                auto fin = [&](int kb, float r) { e.feed(kb, r * rsqrt2); };
+                auto tail = [&](int kb) { if (nt + 1 < NT) ini.step(kb); };
+                auto side = [&](int kb, int g) { if (g == 2) ini.step(kb); };
+                if constexpr (IMPL_REGS) {
+                    if (nt > 0) {
+                        mfma_settle(prev);   // prev's last MFMA (an asm K-block on hq[7]) is a few instructions back
+                        gemm_areg_act<1, IMPL_VT>(s, hq, acc, prev, fin, tail);
+                    } else {
+                        gemm_areg<NT, IMPL_VT>(s, hq, acc, side);
+                    }
+                } else {
+                    if (nt > 0)
+                        gemm_lds_act<1>(s, sl, acc, prev, fin, tail);
+                    else
+                        gemm_lds(s, sl, acc, 0, side);
+                }
                 if (nt > 0) hp[nt - 1] = e.p;
                 prev = acc;
             } else {
@@ -1167,7 +1228,7 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
     for (int i = 0; i < 3; i++) {
         if (i == 1) load_params(prm, prog_params, W_IB, P_USED - W_IB);
         const int pp = i == 0 ? P_IMPL_PAIR - W_IA : (i - 1) * P_IMPL_PAIR_STRIDE;
-        // skip layer 2+2i: registers (x / sqrt(2)) and feat / sqrt(2) -> LDS
+        // skip layer 2+2i: hp (x / sqrt(2)) and feat / sqrt(2) -> hq
         {
             f32x16 prev;
             XyzInit ini;
@@ -1187,16 +1248,16 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                     gemm_areg<NT>(s, fp, acc, [&](int kb, int g) {
                         if (g == 2 && nt + 1 < NT) ini.step(kb, sx, sy, sz);
                     });
-                    if (nt > 0) sl.store(nt - 1, e.p);
+                    if (nt > 0) to_odd(nt - 1, e.p);
                     prev = acc;
                 } else {
 #pragma unroll
                     for (int kb = 0; kb < 16; kb++) e.feed(kb, softplus100(prev[kb]));
-                    sl.store(nt - 1, e.p);
+                    to_odd(nt - 1, e.p);
                 }
             }
         }
-        // plain layer 3+2i: LDS -> registers (/ sqrt(2) when the next layer is a skip layer);
+        // plain layer 3+2i: hq -> hp (/ sqrt(2) when the next layer is a skip layer);
         // the last one feeds layer 8 (256 -> 1), evaluated in fp32 on the spot
         const float post = i < 2 ? rsqrt2 : 1.0f;
         {
@@ -1226,10 +1287,20 @@ DEV float decode_tile(const char *prog, float *prm, u32x4 *stage, unsigned stage
                         if (nt + 1 < NT) ini.step(kb);
                         w8.step(kb);
                     };
-                    if (nt > 0)
-                        gemm_lds_act<1>(s, sl, acc, prev, [&](int kb, float r) { finish(kb, r); }, tail);
-                    else
-                        gemm_lds(s, sl, acc, 0, [&](int kb, int g) { if (g == 2) tail(kb); });
+                    auto side = [&](int kb, int g) { if (g == 2) tail(kb); };
+                    if constexpr (IMPL_REGS) {
+                        if (nt > 0) {
+                            mfma_settle(prev);
+                            gemm_areg_act<1, IMPL_VT>(s, hq, acc, prev, finish, tail);
+                        } else {
+                            gemm_areg<NT, IMPL_VT>(s, hq, acc, side);
+                        }
+                    } else {
+                        if (nt > 0)
+                            gemm_lds_act<1>(s, sl, acc, prev, finish, tail);
+                        else
+                            gemm_lds(s, sl, acc, 0, side);
+                    }
                     if (nt > 0) hp[nt - 1] = e.p;
                     prev = acc;
                 } else {
